@@ -7,7 +7,12 @@ stream, greedy sampling, synthetic weights of the shapes/types a `-q q4_k` load 
 produces (no model files can reach the box), all weights / KV rings / codec state resident in HBM before
 the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds the passes that
+describe the headline rather than measure it (per-phase times, the serial loop, the event-timed roofline,
+the CPU baseline, the extra configurations). --dump-outputs writes what the last timed step returned to
+its caller (PCM, text and audio tokens) as DIR/<name>.npy, so that two builds can be compared.
 
 N > 1 is launched by `python -m torch.distributed.run --nproc-per-node N`: one process per GPU, each
 running an independent stream replica ("replicas only"); barrier + device
@@ -85,6 +90,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=125)    # the reference bench length (README.md:353)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="also run the descriptive passes after the timed steps: phase times + phase roofline, the serial loop, "
+                    "the event-timed kernel roofline, the CPU baseline and the extra configurations (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned (float32 PCM, float64 tokens) as DIR/<name>.npy")
     ap.add_argument("--context-fill", type=int, default=0, help="start the Temporal KV ring at this fill level")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -251,6 +259,7 @@ def main():
 
             def frame():
                 return L.moshi_hot_sts_pipeline_frame(m, None, C.byref(txt), aud64, out.ctypes.data)
+        returned = {"pcm": out, "text_token": txt, "audio_tokens": aud64}
     elif args.model == "stt_like":    # moshi-stt loop (tools/moshi-stt.cpp:552-719): Mimi encode (32 levels) + LM step with the VAD head
         codes = (C.c_int32 * 64)()
         aud64 = (C.c_int32 * 64)()
@@ -265,6 +274,7 @@ def main():
 
             def frame():
                 return L.moshi_hot_sts_pipeline_frame(m, pcm.ctypes.data, C.byref(txt), aud64, out.ctypes.data)
+        returned = {"text_token": txt, "audio_tokens": aud64} if pipelined else {"text_token": txt, "audio_tokens": aud64, "vad": vad}
     else:
         def frame_serial():
             return L.moshi_hot_sts_frame(m, pcm.ctypes.data, C.byref(txt), aud, out.ctypes.data)
@@ -276,6 +286,7 @@ def main():
 
             def frame():
                 return L.moshi_hot_sts_pipeline_frame(m, pcm.ctypes.data, C.byref(txt), aud, out.ctypes.data)
+        returned = {"pcm": out, "text_token": txt, "audio_tokens": aud}
 
     def barrier():
         L.ggml_backend_synchronize(be)
@@ -288,7 +299,7 @@ def main():
     if shard is not None and rank != 0:
         # a Depth-only rank: serve the owner's frames (warm-up, timed region, phase pass) until it says stop; the owner's clock is the job's
         shard.serve()
-        if args.shard == "depth":
+        if args.shard == "depth" and args.full:
             hop_us = shard_hop_latency(shard, dist, dist_group, L, be)
         reduce_max_time(dist, 0.0, group=dist_group)
         L.moshi_hot_free(m)
@@ -304,7 +315,7 @@ def main():
         L.ggml_backend_synchronize(be); device_sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        frame()
+        ret = frame()
         tokens.append(txt.value)
     if shard is None:
         barrier()
@@ -314,6 +325,13 @@ def main():
     if shard is None:
         dt = reduce_max_time(dist, dt, group=dist_group)
     fps = whole_job_rate(world, args.steps, dt) if shard is None else args.steps / dt   # shard: ONE stream over all ranks (strong scaling)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what the caller of the timed path received from its last step (the passes below overwrite these buffers)
+        dump = {k: np.array(v.value if hasattr(v, "value") else v, dtype=np.float32 if k == "pcm" else np.float64).reshape(-1) for k, v in returned.items()}
+        dump["step_return"] = np.array([ret], np.float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dump.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
     offset_end = L.moshi_hot_offset(m)
 
     # algorithmic HBM bytes per frame: every weight byte once + the filled KV slots
@@ -362,7 +380,7 @@ def main():
         "chained_matvecs_in_last_plan": int(st.chained_matvecs_in_last_plan),
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # where the frame goes (separate pass, synchronising around each phase; not part of the timed region)
         L.moshi_hot_set_timing(m, 1)
         for _ in range(10):
@@ -426,7 +444,7 @@ def main():
         args.no_cpu_baseline = True
     elif shard is not None:
         shard.stop_workers()
-        hop_us = shard_hop_latency(shard, dist, dist_group, L, be)
+        hop_us = shard_hop_latency(shard, dist, dist_group, L, be) if args.full else None
         reduce_max_time(dist, dt, group=dist_group)
         result["shard"] = {"kind": "depth codebook shard (SURVEY.md 8e)", "ranks": world, "messages_per_frame": 1 + cfg.dep_q,
                            "message_bytes": int(shard.msg_floats.value * 4), "broadcast_us": hop_us, "transport": shard.transport,
@@ -434,7 +452,7 @@ def main():
         args.no_roofline = True          # flag 8 re-plans graphs eagerly; the roofline line belongs to the default (unsharded) run
         args.no_cpu_baseline = True
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # dominant kernel = matvec_q4k_kernel (3.77 of 4.4 GB per frame). Its launches are timed in situ with HIP
         # start/stop events attached to each dispatch (flag 8: same plan, launched eagerly on the backend stream).
         L.ggml_backend_mi355x_set_flags(be, 8)
@@ -478,7 +496,7 @@ def main():
                     "launches_per_frame": int(kp.chain_launches // 3), "avg_launch_us": round(1e6 * kp.chain_seconds / kp.chain_launches, 3),
                     "algorithmic_bytes_per_launch": int(kp.chain_bytes // kp.chain_launches), "us_per_phase": round(1e6 * kp.chain_seconds / kp.chain_phases, 3)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the same frame loop on the host cores through the CPU oracle (a port of ggml's CPU semantics; the reference's
         # own ggml CPU backend cannot be built here or on the box). Bounded sample: ~10-30 s of CPU work.
         try:
@@ -521,7 +539,7 @@ def main():
     if rank == 0 and m is not None:
         # warm-up + timed + the phase / serial / roofline passes, on both model instances (profile summaries divide by it)
         result["frames_stepped_total"] = int(L.moshi_hot_offset(m)) + int(result.get("serial_loop", {}).get("frames_stepped_by_the_one_handle_model", 0))
-    if rank == 0 and world == 1 and shard is None and not args.no_extras and args.model == "moshika" and args.quant == "q4_k" and not args.sampled and not args.context_fill:
+    if rank == 0 and world == 1 and shard is None and args.full and not args.no_extras and args.model == "moshika" and args.quant == "q4_k" and not args.sampled and not args.context_fill:
         # not the headline: the same loop (a) with the reference's --bench sampling defaults, (b) from a nearly full ring, (c) at BASELINE configs[4]
         def quick(make_cfg, fill=0, steps=40):
             c2 = make_cfg()
@@ -573,7 +591,7 @@ def main():
                 result["extras"][name + "_frames_per_s"] = json.loads(line[-1])["value"] if child.returncode == 0 and line else None
             # the long-context line with its own roofline: this command from a ring holding 2 800 of 3 000 slots, in a child of its own (its phase pass and its
             # event-timed launches belong to THAT fill). A session longer than 4 minutes lives there. K / V bytes = 2 x layers x live slots x dim x 2 B per frame.
-            cmd = [sys.executable, os.path.abspath(__file__), "--context-fill", "2800", "--steps", "40", "--warmup", "6", "--no-cpu-baseline", "--no-extras"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--context-fill", "2800", "--steps", "40", "--warmup", "6", "--full", "--no-cpu-baseline", "--no-extras"]
             child = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             line = [l for l in child.stdout.splitlines() if l.startswith("{")]
             if child.returncode == 0 and line:

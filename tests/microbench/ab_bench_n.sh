@@ -3,6 +3,6 @@
 N=$1; shift
 for i in $(seq $N); do for L in "$@"; do
   export MI355X_LIB=$L
-  timeout 200 python bench.py --steps 60 --warmup 8 --no-cpu-baseline --no-roofline --no-extras | python -c "
+  timeout 200 python bench.py --full --steps 60 --warmup 8 --no-cpu-baseline --no-roofline --no-extras | python -c "
 import json,sys,os; d=json.loads(sys.stdin.read()); print(os.environ['MI355X_LIB'].split('/')[-2], d['value'], d['phase_us']['temporal'])"
 done; done

@@ -4,6 +4,6 @@
 for f in 180 260 350 500 800; do
   for sm in 160 256 384 512 768; do
     echo -n "fill $f single_max $sm: "
-    MI355X_ATTN_SINGLE_MAX=$sm python bench.py --context-fill $f --steps 12 --warmup 4 --no-extras --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['phase_us']['temporal'])"
+    MI355X_ATTN_SINGLE_MAX=$sm python bench.py --full --context-fill $f --steps 12 --warmup 4 --no-extras --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['phase_us']['temporal'])"
   done
 done

@@ -1,10 +1,11 @@
 """bench.py's output contract: ONE JSON line on stdout with the fields the driver reads (metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus `roofline` and, at N = 1, `cpu_baseline`."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full also `roofline`, the serial loop and, at N = 1, `cpu_baseline`."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_parses_its_arguments_and_hashes_its_sources():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "--serial" in out.stdout and "--shard" in out.stdout and "--gpus" in out.stdout
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
     sys.path.insert(0, ROOT)
     import bench
     sha = bench.source_sha()
@@ -25,7 +27,7 @@ def test_bench_parses_its_arguments_and_hashes_its_sources():
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--serial"]])
 def test_bench_prints_one_json_line_with_the_contract_fields(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "5", "--no-cpu-baseline", "--no-extras"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -56,6 +58,32 @@ def test_bench_prints_one_json_line_with_the_contract_fields(extra):
         assert d["value_serial"] == d["serial_loop"]["value"]  # what an unchanged reference tool gets, at the top level
         # the serial legs run a fixed, warmed-up 125 frames whatever --steps is (6 here): the driver's --steps 20 must not shorten what value_serial rests on
         assert d["serial_loop"]["steps"] == 125 and d["serial_loop"]["handles"] == 1 and d["serial_loop"]["warmup"] >= 30
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline only (no phase pass, serial loop, roofline, CPU baseline or extras); --dump-outputs writes what the
+    last timed step returned, and two runs with the same arguments write the same arrays."""
+    dumps = []
+    for i in range(2):
+        d_out = tmp_path / str(i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(d_out)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 3 and d["unit"] == "frames/s" and d["higher_is_better"] is True and "q4_k" in d["metric"]
+        assert 50 < d["value"] < 2000 and abs(d["ms_per_step"] * d["value"] - 1000) < 5
+        for k in ("phase_us", "serial_loop", "value_serial", "roofline", "cpu_baseline", "extras"):
+            assert k not in d, k
+        dumps.append({f.stem: np.load(f) for f in sorted(d_out.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"pcm", "text_token", "audio_tokens", "step_return"} and set(b) == set(a)
+    assert a["pcm"].dtype == np.float32 and a["pcm"].shape == (1920,) and np.isfinite(a["pcm"]).all()
+    assert a["audio_tokens"].dtype == np.float64 and a["step_return"][0] >= 1
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.gpu
