@@ -659,7 +659,7 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
 // A. mat-vec with fused activation prologue and residual epilogue. Returns the position at which the
 //    fused kernel must be emitted (the last node of the group), or -1.
 struct mv_group { mv_args a; int emit_pos; std::vector<int> members; };
-static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members);
+static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members, int64_t B = 1);
 
 static bool writes_through_alias(const ggml_tensor * n) {
     return n->view_src != NULL && !is_view_op(n->op);
@@ -819,7 +819,7 @@ static bool match_matvec(const analysis & an, int pos, mv_group & grp) {
 }
 
 // B. single-token attention block
-struct attn_group { attn_args a; int emit_pos; std::vector<int> members; const ggml_tensor * mask_node; };
+struct attn_group { attn_args a; int emit_pos; std::vector<int> members; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa; };   // B > 1: match_attention_streams
 
 static const ggml_tensor * strip_views(const ggml_tensor * t) {
     while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE)) t = t->src[0];
@@ -962,6 +962,122 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
     return true;
 }
 
+// B''. the same single-token attention block over B > 1 lockstep streams (moshi_hot_create_streams): q / k / v [D, 1, H, B], rings [D, C, H, B] written
+//      at one shared slot, one shared mask row and RoPE phase, output [D, H, 1, B]. One launch of B x H workgroups (k_attn_streams).
+static bool match_attention_streams(const analysis & an, int pos, attn_group & grp) {
+    const ggml_tensor * sm = an.g->nodes[pos];
+    if (sm->op != GGML_OP_SOFT_MAX || !sm->src[1]) return false;
+    const ggml_tensor * kq = sm->src[0], * mask = sm->src[1];
+    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1 || uses_of(an, sm) != 1) return false;
+    const ggml_tensor * kc = kq->src[0], * qo = kq->src[1];
+    if (kc->op != GGML_OP_SET_ROWS || kc->type != GGML_TYPE_BF16) return false;
+    const ggml_tensor * pv = sole_consumer(an, sm);
+    if (!pv || pv->op != GGML_OP_MUL_MAT || pv->src[1] != sm) return false;
+    const ggml_tensor * vt = pv->src[0];
+    if (vt->op != GGML_OP_CONT || vt->src[0]->op != GGML_OP_TRANSPOSE) return false;
+    const ggml_tensor * vc = vt->src[0]->src[0];
+    if (vc->op != GGML_OP_SET_ROWS || vc->type != GGML_TYPE_BF16) return false;
+    const ggml_tensor * x1 = sole_consumer(an, pv);
+    if (!x1 || x1->op != GGML_OP_PERMUTE) return false;
+    const ggml_tensor * x2 = sole_consumer(an, x1);
+    if (!x2 || x2->op != GGML_OP_CONT) return false;
+
+    const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], B = kc->ne[3];
+    if (B < 2 || qo->ne[0] != D || qo->ne[1] != 1 || qo->ne[2] != H || qo->ne[3] != B) return false;
+    if (vc->ne[0] != D || vc->ne[1] != C || vc->ne[2] != H || vc->ne[3] != B) return false;
+    if (mask->type != GGML_TYPE_F32 || mask->ne[0] != C || mask->ne[1] != 1 || ggml_nelements(mask) != C || !ggml_is_contiguous(mask)) return false;   // one shared row
+    if (D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
+    if (kc->src[1] != vc->src[1]) return false;
+    const ggml_tensor * idx = kc->src[1];
+    if (idx->type != GGML_TYPE_I32 || ggml_nelements(idx) != 1 || !ggml_is_contiguous(idx)) return false;   // one shared slot
+    if (kc->nb[0] != 2 || vc->nb[0] != 2) return false;
+
+    const ggml_tensor * ko = kc->src[0], * vrow = vc->src[0];
+    const ggml_tensor * qsrc = qo, * ksrc = ko, * rotr = nullptr, * roti = nullptr;
+    if (qo->op == GGML_OP_CONCAT) {
+        const ggml_tensor * rotr2, * roti2;
+        if (!match_rope(qo, &qsrc, &rotr, &roti) || !match_rope(ko, &ksrc, &rotr2, &roti2) || rotr != rotr2 || roti != roti2) return false;
+        if (rotr->type != GGML_TYPE_F32 || rotr->ne[0] != D / 2 || rotr->ne[1] != 1 || (const char *) roti->data != (const char *) rotr->data + D / 2 * 4) return false;
+        if (rotr->nb[0] != 4 || ggml_nelements(rotr) != D / 2) return false;   // one shared RoPE row
+    }
+    if (qsrc->type != GGML_TYPE_F32 || ksrc->type != GGML_TYPE_F32 || vrow->type != GGML_TYPE_F32) return false;
+    for (const ggml_tensor * t : { qsrc, ksrc, vrow }) if (t->ne[0] != D || t->ne[1] != 1 || t->ne[2] != H || t->ne[3] != B) return false;
+    sview qs, ks, vs;
+    if (!strided_resolve(qsrc, qs) || !strided_resolve(ksrc, ks) || !strided_resolve(vrow, vs)) return false;
+    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[0] != 4 || v->nb[2] % 4 != 0 || v->nb[3] % 4 != 0) return false;
+    if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != 1 || x2->ne[3] != B || !ggml_is_contiguous(x2)) return false;
+
+    // the interior of the block, as match_attention collects it
+    std::vector<const ggml_tensor *> stack = { x2 };
+    std::vector<int> members;
+    std::unordered_map<const ggml_tensor *, bool> seen;
+    int n_mm = 0, n_sm = 0, n_sr = 0;
+    const int lo = pos - 200 > 0 ? pos - 200 : 0;
+    while (!stack.empty()) {
+        const ggml_tensor * t = stack.back(); stack.pop_back();
+        if (seen[t]) continue;
+        seen[t] = true;
+        const int p = pos_of(an, t);
+        if (p < 0) continue;
+        if (t == mask || t == idx || t == rotr || t == roti) continue;
+        if ((const char *) t->data == nullptr) return false;
+        const bool is_input = (t->op == GGML_OP_MUL_MAT && t != kq && t != pv) || t->op == GGML_OP_TIMESTEP_EMBEDDING;
+        if (is_input) continue;
+        if (p < lo) return false;
+        switch (t->op) {
+            case GGML_OP_MUL_MAT: n_mm++; break;
+            case GGML_OP_SOFT_MAX: n_sm++; break;
+            case GGML_OP_SET_ROWS: n_sr++; break;
+            case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: case GGML_OP_CONT:
+            case GGML_OP_MUL: case GGML_OP_SUB: case GGML_OP_ADD: case GGML_OP_CONCAT: break;
+            default: return false;
+        }
+        members.push_back(p);
+        for (int s = 0; s < GGML_MAX_SRC; s++) if (t->src[s]) stack.push_back(t->src[s]);
+    }
+    if (n_mm != 2 || n_sm != 1 || n_sr != 2) return false;
+    std::unordered_map<int, bool> inside;
+    for (int p : members) inside[p] = true;
+    for (int i = 0; i < an.g->n_nodes; i++) {
+        if (inside.count(i)) continue;
+        const ggml_tensor * c = an.g->nodes[i];
+        for (int s = 0; s < GGML_MAX_SRC; s++) {
+            const ggml_tensor * t = c->src[s];
+            if (!t || t == x2) continue;
+            const int tp = pos_of(an, t);
+            if (tp >= 0 && inside.count(tp)) return false;
+        }
+    }
+    attn_args & a = grp.a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float *) qs.base; a.k = (const float *) ks.base; a.v = (const float *) vs.base;
+    a.q_hs = qs.nb[2] / 4; a.k_hs = ks.nb[2] / 4; a.v_hs = vs.nb[2] / 4;   // (T = 1: the row strides are never used)
+    a.rot = rotr ? (const float *) rotr->data : nullptr;
+    a.mask = (const float *) mask->data;
+    grp.mask_node = nullptr;
+    if (mask->op == GGML_OP_CONT && pos_of(an, mask) >= 0) {
+        const char * base = resolve_dense(mask);
+        if (base && base != (const char *) mask->data) { a.mask = (const float *) base; grp.mask_node = mask; }
+    }
+    a.index = (const int32_t *) idx->data;
+    a.kcache = (char *) kc->data; a.vcache = (char *) vc->data;
+    a.k_nb1 = (int64_t) kc->nb[1]; a.k_nb2 = (int64_t) kc->nb[2];
+    a.v_nb1 = (int64_t) vc->nb[1]; a.v_nb2 = (int64_t) vc->nb[2];
+    a.H = (int) H; a.D = (int) D; a.C = (int) C; a.T = 1;
+    a.scale = ggml_get_op_params_f32(sm, 0);
+    a.out = (float *) x2->data;
+    a.out_ts = H * D;
+    grp.B = (int) B;
+    grp.sa.a = a;
+    grp.sa.B = (int) B;
+    grp.sa.q_bs = qs.nb[3] / 4; grp.sa.k_bs = ks.nb[3] / 4; grp.sa.v_bs = vs.nb[3] / 4;
+    grp.sa.kc_bs = (int64_t) kc->nb[3]; grp.sa.vc_bs = (int64_t) vc->nb[3];
+    grp.sa.out_bs = H * D;
+    grp.members = members;
+    grp.emit_pos = pos_of(an, x2);
+    return true;
+}
+
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
 //     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue
 struct bmm_group { int emit_pos; std::vector<int> members; std::function<void(hipStream_t)> run; };
@@ -997,7 +1113,9 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
             const ggml_tensor * l = s0->src[0], * r = s1, * h = l->src[0];
             if (r->src[0] == h && is_f32_vec(h, 2 * K * Tn) && h->ne[0] == 2 * K && l->data == h->data && (const char *) r->data == (const char *) h->data + K * 4 &&
                 l->ne[0] == K && r->ne[0] == K && ggml_nelements(l) == K * Tn && ggml_nelements(r) == K * Tn &&
-                l->ne[1] == 1 && r->ne[1] == 1 && l->nb[2] == h->nb[1] && r->nb[2] == h->nb[1] && l->ne[2] == Tn && r->ne[2] == Tn) {
+                l->ne[1] == 1 && r->ne[1] == 1 &&
+                ((l->nb[2] == h->nb[1] && r->nb[2] == h->nb[1] && l->ne[2] == Tn && r->ne[2] == Tn) ||                                   // prefill: [F, 1, T]
+                 (l->ne[2] == 1 && r->ne[2] == 1 && l->nb[3] == h->nb[1] && r->nb[3] == h->nb[1] && l->ne[3] == Tn && r->ne[3] == Tn))) {  // streams: [F, 1, 1, B]
                 prologue = MV_GATE_SILU;
                 xp = (const float *) h->data;
                 x_cs = 2 * K;
@@ -1068,13 +1186,15 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
 // C. left-deep sum of (scaled) embedding rows ending at node `pos`
 struct embed_group { embed_sum_args a; std::vector<int> members; };
 
-static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members) {
+// B > 1: B columns - rows gathered by B indices [dim, B], times one scale per column [1, B]
+static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members, int64_t B) {
     const ggml_tensor * gr = e, * scale = nullptr;
     if (e->op == GGML_OP_MUL) {
         gr = e->src[0]; scale = e->src[1];
-        if (scale->type != GGML_TYPE_F32 || ggml_nelements(scale) != 1 || uses_of(an, gr) != 1) return false;
+        if (scale->type != GGML_TYPE_F32 || ggml_nelements(scale) != B || uses_of(an, gr) != 1) return false;
+        if (B > 1 && (!ggml_is_contiguous(scale) || scale->ne[0] != 1 || gr->ne[1] != B || !ggml_is_contiguous(gr))) return false;
         members.push_back(pos_of(an, e));
-    } else if (e->op == GGML_OP_CONT && e->src[0]->op == GGML_OP_PERMUTE && e->src[0]->src[0]->op == GGML_OP_GET_ROWS) {
+    } else if (B == 1 && e->op == GGML_OP_CONT && e->src[0]->op == GGML_OP_PERMUTE && e->src[0]->src[0]->op == GGML_OP_GET_ROWS) {
         // a single gathered row viewed as [1, K] (moshi_vq_decode, core_vq.h:100-109): same bytes
         const ggml_tensor * pm = e->src[0];
         gr = pm->src[0];
@@ -1083,10 +1203,10 @@ static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_s
     }
     if (gr->op != GGML_OP_GET_ROWS) return false;
     const ggml_tensor * tab = gr->src[0], * idx = gr->src[1];
-    if (ggml_nelements(idx) != 1 || idx->type != GGML_TYPE_I32 || !dense_rows(tab)) return false;
+    if (ggml_nelements(idx) != B || idx->type != GGML_TYPE_I32 || !dense_rows(tab) || (B > 1 && !ggml_is_contiguous(idx))) return false;
     switch (tab->type) { case GGML_TYPE_F32: case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_K: break; default: return false; }
     const int32_t * ip = (const int32_t *) idx->data;
-    if (idx->op == GGML_OP_CONT && uses_of(an, idx) == 1 && idx->src[0]->type == GGML_TYPE_I32 && idx->src[0]->data && pos_of(an, idx) >= 0) {
+    if (B == 1 && idx->op == GGML_OP_CONT && uses_of(an, idx) == 1 && idx->src[0]->type == GGML_TYPE_I32 && idx->src[0]->data && pos_of(an, idx) >= 0) {
         ip = (const int32_t *) idx->src[0]->data;   // a one-element copy: read the source
         members.push_back(pos_of(an, idx));
     }
@@ -1098,7 +1218,9 @@ static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_s
 static bool match_embed_sum(const analysis & an, int pos, embed_group & grp) {
     const ggml_tensor * top = an.g->nodes[pos];
     if (top->op != GGML_OP_ADD || top->view_src || top->type != GGML_TYPE_F32 || !ggml_is_contiguous(top)) return false;
-    if (!(top->ne[1] == 1 || top->ne[0] == 1) || top->ne[2] != 1 || top->ne[3] != 1) return false;
+    if (top->ne[2] != 1 || top->ne[3] != 1) return false;
+    // [K] (one row) or [K, B] (B columns: lockstep streams, prompt blocks - every term a row per column, see match_embed_term)
+    const int64_t B = top->ne[1] == 1 || top->ne[0] == 1 ? 1 : top->ne[1];
     // walk down the left spine of the chain of adds: adds[d] = adds[d + 1] + terms[d]
     std::vector<const ggml_tensor *> terms, adds;
     const ggml_tensor * cur = top;
@@ -1117,13 +1239,14 @@ static bool match_embed_sum(const analysis & an, int pos, embed_group & grp) {
     std::vector<embed_src> srcs(terms.size());
     std::vector<std::vector<int>> mem(terms.size());
     size_t f = 0;
-    while (f < terms.size() && match_embed_term(an, terms[f], srcs[f], mem[f])) f++;
+    while (f < terms.size() && match_embed_term(an, terms[f], srcs[f], mem[f], B)) f++;
     if (f < 2) return false;
     const ggml_tensor * base = f == terms.size() ? cur : adds[f];   // adds[f] = the partial sum below the first f rows
     embed_src base_src;
     std::vector<int> base_mem;
     bool base_is_row = false;
-    if (f == terms.size() && uses_of(an, cur) == 1 && match_embed_term(an, cur, base_src, base_mem)) base_is_row = true;
+    if (f == terms.size() && uses_of(an, cur) == 1 && match_embed_term(an, cur, base_src, base_mem, B)) base_is_row = true;
+    if (!base_is_row && B > 1) return false;
     if (!base_is_row) {
         if (base->type != GGML_TYPE_F32 || !ggml_is_contiguous(base) || !ggml_are_same_shape(base, top)) return false;
         // row 0 of a one-row F32 "table": any index is clamped to it (embed_sum_kernel), so the first row's index pointer serves
@@ -1132,7 +1255,8 @@ static bool match_embed_sum(const analysis & an, int pos, embed_group & grp) {
     if (f + 1 < 3 || f + 1 > EMBED_SUM_MAX) return false;
     memset(&grp.a, 0, sizeof(grp.a));
     grp.a.n = (int) f + 1;
-    grp.a.K = ggml_nelements(top);
+    grp.a.K = ggml_nelements(top) / B;
+    grp.a.B = (int) B;
     grp.a.out = (float *) top->data;
     grp.a.src[0] = base_src;
     std::vector<int> members = base_mem;
@@ -1634,7 +1758,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
         for (int i = 0; i < g->n_nodes; i++) {
             if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
             attn_group grp;
-            if (!match_attention(an, i, grp)) continue;
+            if (!match_attention(an, i, grp) && !match_attention_streams(an, i, grp)) continue;
             bool clash = false;
             for (int m : grp.members) if (an.skip[(size_t) m]) clash = true;
             if (clash) continue;
@@ -1844,7 +1968,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
                 // workgroup of this projection instead of launching it on its own (16 heads x 8 slots is ~nothing)
                 for (auto & ag : attn_groups) {
                     const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
+                    if (ag.emit_pos < 0 || ag.B > 1 || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
                     if (a.K != 1024 || at.H != 16 || ag.emit_pos > grp.emit_pos || uses_of(an, g->nodes[ag.emit_pos]) != 1) continue;
                     p->attn_copies.emplace_back(new attn_args(at));   // owned by the plan, passed by value at launch
                     a.prologue = MV_ATTN;
@@ -1859,7 +1983,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
                 bool merged = false;
                 for (auto & ag : attn_groups) {
                     const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
+                    if (ag.emit_pos < 0 || ag.B > 1 || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
                     if (!k_inproj_attn_supported(a, at, c->usable_cus)) continue;
                     // every reader of the projection's output must be inside the attention block
                     // (followed through layout-only nodes - a view / reshape / permute / transpose of the output is the output: a reader of such an alias that is
@@ -1981,6 +2105,11 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
         if (ag.emit_pos < 0) continue;
         const attn_args a = ag.a;
         unsigned * err = c->err_dev;
+        if (ag.B > 1) {   // lockstep streams: one launch for every (head, stream)
+            const attn_streams_args sa = ag.sa;
+            at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), [=](hipStream_t s) { k_attn_streams(s, sa, err); });
+            continue;
+        }
         if (a.T > 4) {
             // a block of T > 4 new rows (batched prompt prefill): one workgroup per head and group of 4 rows; first every row's K / V
             // goes into the ring, then all groups attend at once (causality is in the mask rows)

@@ -194,6 +194,12 @@ struct attn_args {
 size_t k_attn_decode_ws_size(const attn_args & a);
 bool k_attn_split_resident(const attn_args & a, int usable_cus);   // may a head be split over workgroups that wait for each other on this many compute units?
 void k_attn_decode(hipStream_t s, const attn_args & a, void * ws = nullptr, unsigned * err = nullptr);   // *err <- 1 if a head-wide wait timed out
+// Lockstep streams (moshi_hot_create_streams): the single-token attention block of B streams at one shared position - one workgroup per (head, stream),
+// each doing exactly what attn_decode_kernel's workgroup of that head does (attn_decode_body, same order of operations) on stream b's q / k / v rows,
+// ring and output row. `a` describes stream 0 (T = 1); stream b's pointers are a's plus b times the *_bs strides (floats for q / k / v / out, bytes for
+// the rings). The mask row, the RoPE table and the ring slot are shared.
+struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs; };
+void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err = nullptr);
 
 // in_proj + the attention that consumes it as ONE launch of 256 resident workgroups (inproj_attn_kernel): `a` is the RMS-normed Q4_K mat-vec whose output
 // holds `at`'s q | k | v. supported(): shapes, and whether the whole grid fits the compute units the stream may use (the parts of a head wait for each
@@ -209,7 +215,8 @@ void k_cross_attn(hipStream_t s, const xattn_args & a);
 
 // sum of (scaled) embedding rows, left-to-right
 #define EMBED_SUM_MAX 40      // terms of one fused embedding sum (tts: 32 audio codebooks + the demuxed text pair); the kernel is instantiated for 24 and 40
-struct embed_sum_args { embed_src src[EMBED_SUM_MAX]; int n; int64_t K; float * out; };
+// B > 1 (lockstep streams / prompt blocks): B columns - column b takes index[b] and scale[b] of every term and writes out[b * K ..] (0 = 1 column)
+struct embed_sum_args { embed_src src[EMBED_SUM_MAX]; int n; int64_t K; float * out; int B; };
 void k_embed_sum(hipStream_t s, const embed_sum_args & a);
 // one residual-VQ encode level (core_vq.h:27-56, 171-194): nearest centroid of `resid`, its index, and resid - centroid
 struct vq_level_args {

@@ -1764,6 +1764,42 @@ void k_attn_decode(hipStream_t s, const attn_args & a, void * ws, unsigned * err
     else      attn_decode_kernel<false, ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(b, w);
 }
 
+// Lockstep streams: workgroup (h, b) runs attn_decode_body for head h of stream b - the unsplit single-workgroup path of attn_decode_kernel, so a head
+// of every stream is computed exactly as the single-stream launch computes it (any fill, across the ring wrap). B x H workgroups in one launch.
+template <int NWA>
+__global__ void __launch_bounds__(NWA * 64) __attribute__((amdgpu_waves_per_eu(2)))
+attn_streams_kernel(attn_streams_args sa, attn_split_ws w) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t b = blockIdx.y;
+    attn_args a = sa.a;
+    a.q += b * sa.q_bs; a.k += b * sa.k_bs; a.v += b * sa.v_bs;
+    a.kcache += b * sa.kc_bs; a.vcache += b * sa.vc_bs;
+    a.out += b * sa.out_bs;
+    attn_decode_body<false, NWA, AT_PLAIN>(a, w, smem, (int) blockIdx.x, 0, 0);
+}
+void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err) {
+    const attn_args & a = sa.a;
+    GGML_ASSERT(sa.B >= 1 && a.T == 1 && a.n_groups <= 1 && !a.write_only && !a.row_split);
+    GGML_ASSERT(a.D % 8 == 0 && 64 % (a.D / 8) == 0 && a.D <= 2 * ATTN_NW_BASE * 64);
+    static const int wide_on = env_int("MI355X_ATTN_WIDE", 1);
+    const bool wide = wide_on && a.D <= 64 && a.C >= 128;   // (attn_decode_kernel's choice for the same head)
+    const size_t smem = attn_smem_bytes(a, false, wide);
+    GGML_ASSERT(smem <= 160 * 1024);
+    if (smem > 64 * 1024) {
+        static size_t granted[2] = { 0, 0 };
+        if (granted[wide] < smem) {
+            HIP_CHECK(hipFuncSetAttribute(wide ? (const void *) attn_streams_kernel<ATTN_NW_WIDE> : (const void *) attn_streams_kernel<ATTN_NW_BASE>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int) smem));
+            granted[wide] = smem;
+        }
+    }
+    static const int single_max = env_int("MI355X_ATTN_SINGLE_MAX", ATTN_SINGLE_MAX), big_min = env_int("MI355X_ATTN_BIG_MIN", ATTN_SPLIT_BIG_MIN);
+    const attn_split_ws w = { nullptr, nullptr, nullptr, 1, err, ATTN_SPLIT_SLOTS, single_max, big_min };
+    const dim3 grid((unsigned) a.H, (unsigned) sa.B);
+    if (wide) attn_streams_kernel<ATTN_NW_WIDE><<<grid, ATTN_NW_WIDE * 64, smem, s>>>(sa, w);
+    else      attn_streams_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(sa, w);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // merged launches of the Temporal layer: shared definitions (the kernel itself: inproj_attn_kernel below)
 // ---------------------------------------------------------------------------------------------------
@@ -2110,13 +2146,14 @@ template <int TYPE, int NMAX>
 __global__ void __launch_bounds__(64) embed_sum_kernel(embed_sum_args a) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.K) return;
+    const int b = (int) blockIdx.y;   // column (stream) b: index[b], scale[b], out[b * K ..]
     int64_t r[NMAX];
     float sc[NMAX], v[NMAX];
 #pragma unroll
     for (int t = 0; t < NMAX; t++) {
         const embed_src & e = a.src[t < a.n ? t : 0];
-        r[t] = *e.index;
-        sc[t] = e.scale ? *e.scale : 1.f;
+        r[t] = e.index[b];
+        sc[t] = e.scale ? e.scale[b] : 1.f;
     }
     if (TYPE == GGML_TYPE_Q4_0 || TYPE == GGML_TYPE_Q8_0) {
         constexpr int BB = TYPE == GGML_TYPE_Q4_0 ? 18 : 34;
@@ -2154,12 +2191,12 @@ __global__ void __launch_bounds__(64) embed_sum_kernel(embed_sum_args a) {
             acc = t == 0 ? x : acc + x;
         }
     }
-    a.out[i] = acc;
+    a.out[(int64_t) b * a.K + i] = acc;
 }
 void k_embed_sum(hipStream_t s, const embed_sum_args & a) {
     int type = a.n > 0 ? a.src[0].type : -1;
     for (int t = 1; t < a.n; t++) if (a.src[t].type != type) type = -1;
-    const int grid = (int) ((a.K + 63) / 64);
+    const dim3 grid((unsigned) ((a.K + 63) / 64), (unsigned) (a.B > 1 ? a.B : 1));
     // (every loop over the terms is unrolled to the instantiation's bound: sums of up to 24 terms - moshika 17, PersonaPlex 17 - keep the 24-term kernel)
 #define EMBED_LAUNCH(T) do { if (a.n <= 8) embed_sum_kernel<T, 8><<<grid, 64, 0, s>>>(a); else if (a.n <= 24) embed_sum_kernel<T, 24><<<grid, 64, 0, s>>>(a); else embed_sum_kernel<T, EMBED_SUM_MAX><<<grid, 64, 0, s>>>(a); } while (0)   // (8: the RVQ decode sums - 7 + 1 rows - ran 16 dead iterations per stage in the 24-term instance)
     switch (type) {

@@ -326,7 +326,7 @@ T apply_norm(Builder & c, const Norm & n, T x) {
     if (n.rms) {   // moshi_rms_norm (transformer.h:16-23) multiplies alpha * y, which ggml only broadcasts for one column; the batched
                    // prefill (T > 1, not a reference path) swaps the operands — same products
         T y = ggml_rms_norm(c, x, n.eps);
-        return x->ne[1] > 1 ? ggml_mul(c, y, n.w) : ggml_mul(c, n.w, y);
+        return x->ne[1] > 1 || x->ne[2] > 1 ? ggml_mul(c, y, n.w) : ggml_mul(c, n.w, y);   // (lockstep streams: [dim, 1, B], the same swap)
     }
     x = ggml_norm(c, x, n.eps);
     x = ggml_mul(c, x, n.w);
@@ -529,8 +529,9 @@ T transformer_layer(Builder & c, const Transformer & tr, Layer & L, int wi, T in
         T gx = nx;
         if (per_step_views) gx = ggml_view_3d(c, nx, nx->ne[0], 1, nx->ne[2], nx->nb[1], nx->nb[2], 0);   // transformer.h:132-138
         update = gating(c, L.gate_in[(size_t) wi], L.gate_out[(size_t) wi], gx);
-        // moshi_activation_gating returns [dim, 1, T]: addable to x only for T = 1, the reference's only LM shape; the batched prefill folds it back
-        if (x->ne[1] > 1) update = ggml_reshape_3d(c, update, update->ne[0], x->ne[1], x->ne[2]);
+        // moshi_activation_gating returns [dim, 1, T]: addable to x only for T = 1, the reference's only LM shape; the batched prefill folds it back,
+        // and so do lockstep streams ([dim, 1, 1, B] -> [dim, 1, B])
+        if (x->ne[1] > 1 || x->ne[2] > 1) update = ggml_reshape_3d(c, update, update->ne[0], x->ne[1], x->ne[2]);
     }
     if (L.layer_scale_2) update = ggml_mul(c, update, L.layer_scale_2);
     return ggml_add(c, x, update);
@@ -596,6 +597,25 @@ T sample_token(Builder & g, T logits, float temp, int top_k) {
     next = ggml_reshape_4d(g, next, next->ne[0], probs->ne[1], probs->ne[2], probs->ne[3]);
     T irows = ggml_permute(g, indices, 1, 0, 2, 3);
     return ggml_get_rows(g, ggml_cont(g, irows), next);
+}
+
+// moshi_sample_token over the batch dimension of lockstep streams: logits [n, 1, B] -> I32 [B], one token per column. The same op sequence as
+// sample_token with B columns instead of one; in sampled mode the noise is one [k, B] tensor, drawn in one sweep (column b = stream b).
+T sample_tokens_streams(Builder & g, T logits, float temp, int top_k) {
+    const int64_t n = logits->ne[0], B = ggml_nelements(logits) / n;
+    T l2 = ggml_reshape_2d(g, logits, n, B);
+    if (!(temp > 0.f)) return ggml_argmax(g, l2);
+    T probs = ggml_soft_max(g, ggml_scale(g, l2, 1.f / temp));                   // [n, B]
+    const int k = (int) n < top_k ? (int) n : top_k;
+    T indices = ggml_cont(g, ggml_argsort_top_k(g, probs, k));                    // [k, B]
+    T rows = ggml_cont(g, ggml_permute(g, ggml_reshape_3d(g, probs, n, 1, B), 1, 0, 2, 3));   // [1, n, B]
+    T picked = ggml_get_rows(g, rows, indices);                                   // [1, k, B]
+    T in2 = ggml_reshape_2d(g, picked, k, B);
+    T q = ggml_div(g, in2, g.exponential(k, B, 1.f));
+    T next = ggml_argmax(g, q);                                                   // [B]
+    T irows = ggml_cont(g, ggml_permute(g, ggml_reshape_3d(g, indices, k, 1, B), 1, 0, 2, 3));   // [1, k, B]
+    T tok = ggml_get_rows(g, irows, ggml_reshape_2d(g, next, 1, B));              // [1, 1, B]
+    return ggml_reshape_1d(g, tok, B);
 }
 
 // ---- Mimi ---------------------------------------------------------------------------------------------------
@@ -765,6 +785,8 @@ struct moshi_hot_model {
     bool tp_frame = false; T tp_in = nullptr; Builder * g_tp_pre = nullptr, * g_tp_import = nullptr, * g_tp_post = nullptr; int64_t tp_frames = 0;
     // delay ring (lm.h:715-743)
     int offset = 0; std::vector<std::vector<int>> cache; std::vector<int> initial; int max_delay = 0;
+    // lockstep streams (moshi_hot_create_streams): B > 1 = the batch dimension of every LM activation and KV ring; one delay ring per stream
+    int n_streams = 1; std::vector<std::vector<std::vector<int>>> s_cache;
 
     // Mimi
     Rvq rvq_first, rvq_rest;
@@ -786,11 +808,19 @@ struct moshi_hot_model {
     bool timing = false; double phase_us[4] = { 0, 0, 0, 0 }; int64_t phase_n[4] = { 0, 0, 0, 0 };
 };
 
+// the single-stream calls on a lockstep-streams model (moshi_hot_create_streams, n_streams > 1): refused (moshi_hot.h lists the return values)
+#define STREAMS_REFUSE(ret) do { if (m->n_streams > 1) return ret; } while (0)
+
 namespace {
 
 T state(moshi_hot_model * m, enum ggml_type type, int64_t n0, int64_t n1 = 1, int64_t n2 = 1) {
     T t = ggml_new_tensor_3d(m->st_ctx, type, n0, n1, n2);
     m->st_init.push_back({ t, std::vector<uint8_t>(ggml_nbytes(t), 0) });   // zero-filled (transformer.h:164-166, conv.h:112)
+    return t;
+}
+T state4(moshi_hot_model * m, enum ggml_type type, int64_t n0, int64_t n1, int64_t n2, int64_t n3) {   // a state with a batch dimension (lockstep streams)
+    T t = ggml_new_tensor_4d(m->st_ctx, type, n0, n1, n2, n3);
+    m->st_init.push_back({ t, std::vector<uint8_t>(ggml_nbytes(t), 0) });
     return t;
 }
 
@@ -836,8 +866,13 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
                 L.gate_out.push_back(W.add(p + "gating" + ws + ".linear_out.weight", wtype, ffn_hidden, dim, 1, qgen(upd / sqrtf((float) ffn_hidden))));
             }
         }
-        L.kcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
-        L.vcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
+        if (m->n_streams > 1 && !mimi_style) {   // moshi_kv_cache_state with batch_size = B (transformer.h:155-171)
+            L.kcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
+            L.vcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
+        } else {
+            L.kcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
+            L.vcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
+        }
         if (cross_len > 0) {   // lm_default.h:20-35; states filled by init() (transformer.h:335-339)
             L.norm_cross = { false, 0.0f, W.add(p + "norm_cross.weight", GGML_TYPE_F32, dim, 1, 1, ones),
                              W.add(p + "norm_cross.bias", GGML_TYPE_F32, dim, 1, 1, [](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, 0.02f); }) };
@@ -889,9 +924,10 @@ void make_rvq(moshi_hot_model * m, Rvq & rvq, const std::string & name, int n_la
 // moshi_lmmodel_forward_text_build + sampler (lm.h:555-584, 659-677, 853-869)
 T build_input_embedding(moshi_hot_model * m, Builder & g) {
     const moshi_hot_config & c = m->cfg;
-    auto embed = [&](T table) {   // moshi_scaled_embedding_build (lm_utils.h:157-170)
+    const int B = m->n_streams;
+    auto embed = [&](T table) {   // moshi_scaled_embedding_build (lm_utils.h:157-170); lockstep streams: B indices, one scale per stream
         const int i = (int) m->emb_idx.size();
-        T idx = m->tok_state && i <= c.dep_q ? ggml_view_1d(g, m->tok_state, 1, (size_t) i * 4) : g.tensor(GGML_TYPE_I32, 1), scale = g.tensor(GGML_TYPE_F32, 1);
+        T idx = m->tok_state && i <= c.dep_q ? ggml_view_1d(g, m->tok_state, 1, (size_t) i * 4) : g.tensor(GGML_TYPE_I32, B), scale = B > 1 ? g.tensor(GGML_TYPE_F32, 1, B) : g.tensor(GGML_TYPE_F32, 1);
         m->emb_idx.push_back(idx); m->emb_scale.push_back(scale);
         return ggml_mul(g, ggml_get_rows(g, table, idx), scale);
     };
@@ -906,6 +942,7 @@ T build_input_embedding(moshi_hot_model * m, Builder & g) {
     } else input = embed(m->text_emb);
     for (int k = 0; k < c.n_q; k++) input = ggml_add(g, input, embed(m->emb[(size_t) k]));
     if (c.condition_sum) input = ggml_add(g, m->cond_sum, input);   // lm.h:579-581
+    if (B > 1) input = ggml_reshape_3d(g, input, input->ne[0], 1, B);   // [dim, B] -> [dim, T = 1, B]
     m->g_transformer_in = input;
     return input;
 }
@@ -920,7 +957,7 @@ void build_temporal_graph(moshi_hot_model * m) {
     m->g_transformer_out = x;
     m->text_logits = linear(g, m->text_linear, x);
     g.expand(ggml_cpy(g, x, m->transformer_out));
-    m->sampler_out = sample_token(g, m->text_logits, c.temp_text, c.top_k_text);
+    m->sampler_out = m->n_streams > 1 ? sample_tokens_streams(g, m->text_logits, c.temp_text, c.top_k_text) : sample_token(g, m->text_logits, c.temp_text, c.top_k_text);
     g.expand(m->sampler_out);
     if (m->tok_state) g.expand(ggml_cpy(g, ggml_reshape_1d(g, m->sampler_out, 1), ggml_view_1d(g, m->tok_state, 1, 0)));
     g.alloc();
@@ -968,6 +1005,36 @@ void build_depth_graph(moshi_hot_model * m) {
         g.expand(ggml_cpy(g, next, view));
     }
     m->dep_tokens = ggml_view_1d(g, view, tokens->ne[0], (size_t) (-(int64_t) (c.dep_q - 1) * 4));
+    g.expand(m->dep_tokens);
+    g.alloc();
+}
+
+// the chained Depth graph of lockstep streams (n_streams = B > 1): the same steps as build_depth_graph over [dep_dim, 1, B] activations; step k's B
+// samples are the B indices of step k + 1's embedding (stream b's token feeds stream b's row). dep_tokens = I32 [dep_q, B] as B-wide rows per step.
+void build_depth_graph_streams(moshi_hot_model * m) {
+    const moshi_hot_config & c = m->cfg;
+    const int B = m->n_streams;
+    m->g_depth = new Builder(m->be, 256);
+    Builder & g = *m->g_depth;
+    m->dep_text_idx = g.tensor(GGML_TYPE_I32, B);
+    m->dep_text_scale = g.tensor(GGML_TYPE_F32, 1, B);
+    T last = ggml_mul(g, ggml_get_rows(g, m->depformer_text_emb, m->dep_text_idx), m->dep_text_scale);   // [E, B]
+    T tokens = g.tensor(GGML_TYPE_I32, (int64_t) B * c.dep_q);
+    T view = nullptr, next = nullptr;
+    for (int k = 0; k < c.dep_q; k++) {
+        if (k > 0) last = ggml_get_rows(g, m->depformer_emb[(size_t) (k - 1)], next);   // moshi_scaled_embedding_chained (lm_utils.h:208-217)
+        // moshi_lmmodel_forward_depformer_transform (lm.h:446-475)
+        T din = linear(g, m->depformer_in[(size_t) k], m->transformer_out);           // [dep_dim, 1, B]
+        last = ggml_cast(g, last, GGML_TYPE_F32);
+        din = ggml_add(g, din, ggml_reshape_3d(g, last, last->ne[0], 1, B));
+        T dout = transformer_inline(g, m->depth, din);
+        T logits = linear(g, m->linears[(size_t) k], dout);                          // [card, 1, B]
+        m->dep_logits.push_back(logits);
+        next = sample_tokens_streams(g, logits, c.temp, c.top_k);
+        view = k == 0 ? ggml_view_1d(g, tokens, B, 0) : ggml_view_1d(g, view, B, (size_t) B * 4);
+        g.expand(ggml_cpy(g, next, view));
+    }
+    m->dep_tokens = ggml_view_1d(g, view, tokens->ne[0], (size_t) (-(int64_t) (c.dep_q - 1) * B * 4));
     g.expand(m->dep_tokens);
     g.alloc();
 }
@@ -1061,8 +1128,20 @@ extern "C" void moshi_hot_config_personaplex(struct moshi_hot_config * c) {
     c->personaplex = 1;
 }
 
-static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path);
+static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams = 1);
 extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed) { return create_model(backend, cfg, seed, nullptr); }
+// lockstep streams (moshi_hot.h): the moshika-shaped LM only
+extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams) {
+    if (!cfg || n_streams < 1 || n_streams > 16) return nullptr;
+    if (n_streams == 1) return create_model(backend, cfg, seed, nullptr);
+    const moshi_hot_config & c = *cfg;
+    const bool ok = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && !c.extra_heads && !c.demux_second_stream &&
+                    !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len && c.tp_world == 0 &&
+                    c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream && c.dep_q > 0 && c.n_q > c.dep_q;
+    if (!ok) return nullptr;
+    return create_model(backend, cfg, seed, nullptr, n_streams);
+}
+extern "C" int moshi_hot_n_streams(moshi_hot_model_t * m) { return m->n_streams; }
 // the model's weights come from a GGUF file written by moshi_hot_save_gguf (the reference's `*.gguf` checkpoints: WeightLoader::from_gguf + load_gguf)
 extern "C" moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, const struct moshi_hot_config * cfg, const char * path) { return create_model(backend, cfg, 0, path); }
 // WeightLoader::save_gguf (loader.h:227-233): every tensor of the weight context, in context order
@@ -1078,10 +1157,11 @@ extern "C" int moshi_hot_tensor_file_name(const char * checkpoint_name, char * o
     if (out && n > 0) { strncpy(out, f.c_str(), (size_t) n - 1); out[n - 1] = 0; }
     return (int) f.size();
 }
-static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path) {
+static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams) {
     moshi_hot_model * m = new moshi_hot_model;
     m->cfg = *cfg;
     m->be = backend;
+    m->n_streams = n_streams;
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
     if (gguf_path) m->W->gguf_path = gguf_path;
@@ -1153,7 +1233,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         m->out_norm = { true, 1e-8f, W.add("lm.out_norm.alpha", GGML_TYPE_F32, c.dim, 1, 1, ones), nullptr };
         m->text_linear = W.add("lm.text_linear.weight", lt, c.dim, c.text_card, 1, qgen(1.f / sqrtf((float) c.dim)));
         }
-        m->transformer_out = state(m, GGML_TYPE_F32, c.dim);
+        m->transformer_out = m->n_streams > 1 ? state(m, GGML_TYPE_F32, c.dim, 1, m->n_streams) : state(m, GGML_TYPE_F32, c.dim);
         if (c.chain_depth) m->tok_state = state(m, GGML_TYPE_I32, 1 + c.dep_q);
         if (c.condition_sum) m->cond_sum = state(m, GGML_TYPE_F32, c.dim);
         if (c.cross_attention) m->cond_cross = state(m, GGML_TYPE_F32, c.dim, c.cross_len);
@@ -1201,6 +1281,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         m->cache.assign((size_t) (m->max_delay + 2 + (c.personaplex ? 1 : 0)), std::vector<int>((size_t) ncb, -2));
         m->initial.assign((size_t) ncb, c.card);
         m->initial[0] = c.text_card;
+        if (m->n_streams > 1) m->s_cache.assign((size_t) m->n_streams, m->cache);
     }
     if (c.enable_mimi_decoder || c.enable_mimi_encoder) {
         W.part = c.enable_mimi_decoder ? 3 : 2;
@@ -1296,12 +1377,12 @@ void mimi_encode_launch(moshi_hot_model * m, const float * pcm) {
 void mimi_encode_finish(moshi_hot_model * m, int32_t * codes) { ggml_backend_tensor_get(m->enc_codes, codes, 0, ggml_nbytes(m->enc_codes)); }
 }  // namespace
 
-extern "C" void moshi_hot_mimi_decode(moshi_hot_model_t * m, const int32_t * codes, float * pcm) {
+extern "C" void moshi_hot_mimi_decode(moshi_hot_model_t * m, const int32_t * codes, float * pcm) { STREAMS_REFUSE();
     PhaseTimer pt(m, 3);
     mimi_decode_launch(m, codes);
     mimi_decode_finish(m, pcm);
 }
-extern "C" void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, int32_t * codes) {
+extern "C" void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, int32_t * codes) { STREAMS_REFUSE();
     PhaseTimer pt(m, 0);
     mimi_encode_launch(m, pcm);
     mimi_encode_finish(m, codes);
@@ -1373,26 +1454,26 @@ void build_tp_segment(moshi_hot_model * m, int i) {
 }
 }  // namespace
 
-extern "C" void * moshi_hot_tp_msg(moshi_hot_model_t * m, int64_t * n) { GGML_ASSERT(m->tp_msg); if (n) *n = ggml_nelements(m->tp_msg); return m->tp_msg->data; }
-extern "C" void moshi_hot_tp_begin(moshi_hot_model_t * m, const float * x) {
+extern "C" void * moshi_hot_tp_msg(moshi_hot_model_t * m, int64_t * n) { STREAMS_REFUSE(nullptr); GGML_ASSERT(m->tp_msg); if (n) *n = ggml_nelements(m->tp_msg); return m->tp_msg->data; }
+extern "C" void moshi_hot_tp_begin(moshi_hot_model_t * m, const float * x) { STREAMS_REFUSE();
     GGML_ASSERT(m->tp_x);
     ggml_backend_tensor_set(m->tp_x, x, 0, (size_t) m->cfg.dim * 4);
     transformer_graph_step(*m->scratch, m->temporal_tp, 1);   // mask row -> g_bias (scratch cpy), RoPE phase, ring slot (transformer.h:1259-1289)
     m->scratch->compute_scratch();
 }
-extern "C" void moshi_hot_tp_segment(moshi_hot_model_t * m, int i) {
+extern "C" void moshi_hot_tp_segment(moshi_hot_model_t * m, int i) { STREAMS_REFUSE();
     GGML_ASSERT(i >= 0 && i <= 2 * m->cfg.num_layers);
     if ((int) m->g_tp.size() <= i || !m->g_tp[(size_t) i]) build_tp_segment(m, i);
     m->g_tp[(size_t) i]->compute();
 }
 // the partial-sum message through the backend's own transfer calls (a host-side stand-in for the all-reduce: tests that drive several ranks' models in one process)
-extern "C" void moshi_hot_tp_msg_read(moshi_hot_model_t * m, float * out) { GGML_ASSERT(m->tp_msg); ggml_backend_tensor_get(m->tp_msg, out, 0, ggml_nbytes(m->tp_msg)); }
-extern "C" void moshi_hot_tp_msg_write(moshi_hot_model_t * m, const float * in) { GGML_ASSERT(m->tp_msg); ggml_backend_tensor_set(m->tp_msg, in, 0, ggml_nbytes(m->tp_msg)); }
-extern "C" void moshi_hot_tp_end(moshi_hot_model_t * m, float * out) { ggml_backend_tensor_get(m->tp_x, out, 0, (size_t) m->cfg.dim * 4); }
+extern "C" void moshi_hot_tp_msg_read(moshi_hot_model_t * m, float * out) { STREAMS_REFUSE(); GGML_ASSERT(m->tp_msg); ggml_backend_tensor_get(m->tp_msg, out, 0, ggml_nbytes(m->tp_msg)); }
+extern "C" void moshi_hot_tp_msg_write(moshi_hot_model_t * m, const float * in) { STREAMS_REFUSE(); GGML_ASSERT(m->tp_msg); ggml_backend_tensor_set(m->tp_msg, in, 0, ggml_nbytes(m->tp_msg)); }
+extern "C" void moshi_hot_tp_end(moshi_hot_model_t * m, float * out) { STREAMS_REFUSE(); ggml_backend_tensor_get(m->tp_x, out, 0, (size_t) m->cfg.dim * 4); }
 // The whole tensor-parallel stack pass behind the C-ABI: 2 L + 1 segment graphs with an in-place sum of the F32[dim] partial over the ranks between them -
 // ncclAllReduce called from here on the backend's own stream (the communicator of moshi_hot_depth_shard_rccl_init: one per model, both sharded modes use it),
 // or the caller's function (host memory on the CPU device: gloo in tests/test_temporal_tp_cpu.py). No interpreter between the segments.
-extern "C" void moshi_hot_tp_set_transport(moshi_hot_model_t * m, moshi_hot_allreduce_t fn, void * user) { m->tp_allreduce = fn; m->tp_allreduce_user = user; }
+extern "C" void moshi_hot_tp_set_transport(moshi_hot_model_t * m, moshi_hot_allreduce_t fn, void * user) { STREAMS_REFUSE(); m->tp_allreduce = fn; m->tp_allreduce_user = user; }
 extern "C" int64_t moshi_hot_tp_reductions(moshi_hot_model_t * m) { return m->tp_reductions; }
 namespace {
 // the 2 L + 1 segment graphs with the in-place sum of the F32[dim] partial over the ranks between them
@@ -1469,25 +1550,25 @@ void tp_temporal_frame(moshi_hot_model * m) {   // rank 0, inside moshi_hot_lm_s
     m->g_tp_post->compute();
 }
 }  // namespace
-extern "C" void moshi_hot_tp_stack(moshi_hot_model_t * m, const float * x, float * out) {
+extern "C" void moshi_hot_tp_stack(moshi_hot_model_t * m, const float * x, float * out) { STREAMS_REFUSE();
     moshi_hot_tp_begin(m, x);
     tp_run_segments(m);
     moshi_hot_tp_end(m, out);
 }
-extern "C" void moshi_hot_tp_install(moshi_hot_model_t * m) {
+extern "C" void moshi_hot_tp_install(moshi_hot_model_t * m) { STREAMS_REFUSE();
     GGML_ASSERT(m->tp_x && m->tp_in && !m->cfg.chain_depth && "moshi_hot_tp_install: a model created with tp_world >= 1 and chain_depth = 0");
     // build_input_embedding appends to the model's embedding index / scale input lists: a Temporal graph built earlier would make them double
     GGML_ASSERT(!m->g_temporal && "moshi_hot_tp_install: call before the first LM step (the ordinary Temporal graph already owns the embedding inputs)");
     m->tp_frame = true;
 }
-extern "C" void moshi_hot_tp_stop(moshi_hot_model_t * m) {
+extern "C" void moshi_hot_tp_stop(moshi_hot_model_t * m) { STREAMS_REFUSE();
     const float more = 0.f;
     ggml_backend_tensor_set(m->tp_in, &more, (size_t) m->cfg.dim * 4, 4);
     ggml_backend_synchronize(m->be);   // flushes the queued upload: the broadcast below must carry THIS flag, not the previous frame's
     tp_broadcast_in(m);
     ggml_backend_synchronize(m->be);
 }
-extern "C" int64_t moshi_hot_tp_serve(moshi_hot_model_t * m) {
+extern "C" int64_t moshi_hot_tp_serve(moshi_hot_model_t * m) { STREAMS_REFUSE(-1);
     GGML_ASSERT(m->tp_x && m->tp_in);
     int64_t frames = 0;
     for (;;) {
@@ -1564,9 +1645,9 @@ void build_shard_import(moshi_hot_model * m, int k) {
 }
 }  // namespace
 
-extern "C" void * moshi_hot_depth_shard_msg(moshi_hot_model_t * m, int64_t * n) { GGML_ASSERT(m->shard_msg); if (n) *n = ggml_nelements(m->shard_msg); return m->shard_msg->data; }
-extern "C" void * moshi_hot_depth_shard_tout(moshi_hot_model_t * m, int64_t * n) { GGML_ASSERT(m->shard_tout); if (n) *n = ggml_nelements(m->shard_tout); return m->shard_tout->data; }
-extern "C" void moshi_hot_depth_shard_begin_export(moshi_hot_model_t * m, int32_t text_token, int more) {
+extern "C" void * moshi_hot_depth_shard_msg(moshi_hot_model_t * m, int64_t * n) { STREAMS_REFUSE(nullptr); GGML_ASSERT(m->shard_msg); if (n) *n = ggml_nelements(m->shard_msg); return m->shard_msg->data; }
+extern "C" void * moshi_hot_depth_shard_tout(moshi_hot_model_t * m, int64_t * n) { STREAMS_REFUSE(nullptr); GGML_ASSERT(m->shard_tout); if (n) *n = ggml_nelements(m->shard_tout); return m->shard_tout->data; }
+extern "C" void moshi_hot_depth_shard_begin_export(moshi_hot_model_t * m, int32_t text_token, int more) { STREAMS_REFUSE();
     const moshi_hot_config & c = m->cfg;
     if (!m->g_shard_begin) {
         m->g_shard_begin = new Builder(m->be, 4);
@@ -1585,7 +1666,7 @@ extern "C" void moshi_hot_depth_shard_begin_export(moshi_hot_model_t * m, int32_
         ggml_backend_tensor_set(m->shard_text_scale[0], &sc, 0, 4);
     }
 }
-extern "C" int moshi_hot_depth_shard_begin_import(moshi_hot_model_t * m) {
+extern "C" int moshi_hot_depth_shard_begin_import(moshi_hot_model_t * m) { STREAMS_REFUSE(-1);
     const moshi_hot_config & c = m->cfg;
     if (!m->g_shard_begin) {
         m->g_shard_begin = new Builder(m->be, 4);
@@ -1598,16 +1679,16 @@ extern "C" int moshi_hot_depth_shard_begin_import(moshi_hot_model_t * m) {
     if (flag != 0.f) m->g_shard_begin->compute();
     return flag != 0.f;
 }
-extern "C" void moshi_hot_depth_shard_step(moshi_hot_model_t * m, int k) {
+extern "C" void moshi_hot_depth_shard_step(moshi_hot_model_t * m, int k) { STREAMS_REFUSE();
     PhaseTimer pt(m, 2);
     if ((int) m->g_shard_step.size() <= k || !m->g_shard_step[(size_t) k]) build_shard_step(m, k);
     m->g_shard_step[(size_t) k]->compute();
 }
-extern "C" void moshi_hot_depth_shard_import(moshi_hot_model_t * m, int k) {
+extern "C" void moshi_hot_depth_shard_import(moshi_hot_model_t * m, int k) { STREAMS_REFUSE();
     if ((int) m->g_shard_import.size() <= k || !m->g_shard_import[(size_t) k]) build_shard_import(m, k);
     m->g_shard_import[(size_t) k]->compute();
 }
-extern "C" void moshi_hot_depth_shard_tokens(moshi_hot_model_t * m, int32_t * out, int n) { ggml_backend_tensor_get(m->shard_tokens, out, 0, (size_t) n * 4); }
+extern "C" void moshi_hot_depth_shard_tokens(moshi_hot_model_t * m, int32_t * out, int n) { STREAMS_REFUSE(); ggml_backend_tensor_get(m->shard_tokens, out, 0, (size_t) n * 4); }
 
 // ---- the sharded frame behind the C-ABI (the loop of lm.h:505-527 spread over ranks) ------------------------------------------
 namespace {
@@ -1646,7 +1727,7 @@ void shard_frame_hook(void * user, int32_t text_token, int32_t * audio) {
     moshi_hot_depth_shard_tokens(m, audio, m->cfg.dep_q);
 }
 }  // namespace
-extern "C" void moshi_hot_depth_shard_set_transport(moshi_hot_model_t * m, moshi_hot_bcast_t fn, void * user) { m->shard_bcast = fn; m->shard_bcast_user = user; }
+extern "C" void moshi_hot_depth_shard_set_transport(moshi_hot_model_t * m, moshi_hot_bcast_t fn, void * user) { STREAMS_REFUSE(); m->shard_bcast = fn; m->shard_bcast_user = user; }
 extern "C" int moshi_hot_depth_shard_rccl_unique_id(char * id128) {
     void * lib = rccl_open();
     if (!lib) return -1;
@@ -1657,7 +1738,7 @@ extern "C" int moshi_hot_depth_shard_rccl_unique_id(char * id128) {
     if (rc == 0) memcpy(id128, id.internal, 128);
     return rc;
 }
-extern "C" int moshi_hot_depth_shard_rccl_init(moshi_hot_model_t * m, int rank, int world, const char * id128) {
+extern "C" int moshi_hot_depth_shard_rccl_init(moshi_hot_model_t * m, int rank, int world, const char * id128) { STREAMS_REFUSE(-1);
     void * lib = rccl_open();
     if (!lib) return -1;
     auto init = (int (*)(void **, int, nccl_id, int)) dlsym(lib, "ncclCommInitRank");
@@ -1679,14 +1760,14 @@ extern "C" void moshi_hot_depth_shard_rccl_free(moshi_hot_model_t * m) {
     if (m->rccl_comm && m->rccl_comm_destroy) { ggml_backend_mi355x_make_current(m->be); ggml_backend_synchronize(m->be); m->rccl_comm_destroy(m->rccl_comm); }
     m->rccl_comm = nullptr;
 }
-extern "C" void moshi_hot_depth_shard_broadcast(moshi_hot_model_t * m, int which, int root) { shard_broadcast(m, which ? m->shard_tout : m->shard_msg, root); }
+extern "C" void moshi_hot_depth_shard_broadcast(moshi_hot_model_t * m, int which, int root) { STREAMS_REFUSE(); shard_broadcast(m, which ? m->shard_tout : m->shard_msg, root); }
 extern "C" int64_t moshi_hot_depth_shard_hops(moshi_hot_model_t * m) { return m->shard_hops; }
-extern "C" void moshi_hot_depth_shard_install(moshi_hot_model_t * m) { moshi_hot_set_depth_hook(m, shard_frame_hook, m); }
-extern "C" void moshi_hot_depth_shard_stop(moshi_hot_model_t * m) {
+extern "C" void moshi_hot_depth_shard_install(moshi_hot_model_t * m) { STREAMS_REFUSE(); moshi_hot_set_depth_hook(m, shard_frame_hook, m); }
+extern "C" void moshi_hot_depth_shard_stop(moshi_hot_model_t * m) { STREAMS_REFUSE();
     moshi_hot_depth_shard_begin_export(m, 0, 0);
     shard_broadcast(m, m->shard_tout, 0);
 }
-extern "C" int64_t moshi_hot_depth_shard_serve(moshi_hot_model_t * m) {
+extern "C" int64_t moshi_hot_depth_shard_serve(moshi_hot_model_t * m) { STREAMS_REFUSE(-1);
     int64_t frames = 0;
     for (;;) {
         shard_broadcast(m, m->shard_tout, 0);
@@ -1695,14 +1776,14 @@ extern "C" int64_t moshi_hot_depth_shard_serve(moshi_hot_model_t * m) {
         frames++;
     }
 }
-extern "C" int moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max_values) {
+extern "C" int moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max_values) { STREAMS_REFUSE(-1);
     // the host-side delay ring of moshi_lmgen (lm.h:819-824, 935-943), row-major [rows][n_q + 1]; returns the number of values (0 when dst is too small)
     const int rows = (int) m->cache.size(), cols = rows ? (int) m->cache[0].size() : 0;
     if (!dst || rows * cols > max_values) return dst ? 0 : rows * cols;
     for (int r = 0; r < rows; r++) for (int q = 0; q < cols; q++) dst[r * cols + q] = m->cache[(size_t) r][(size_t) q];
     return rows * cols;
 }
-extern "C" void moshi_hot_set_depth_hook(moshi_hot_model_t * m, moshi_hot_depth_hook_t fn, void * user) { m->depth_hook = fn; m->depth_hook_user = user; }
+extern "C" void moshi_hot_set_depth_hook(moshi_hot_model_t * m, moshi_hot_depth_hook_t fn, void * user) { STREAMS_REFUSE(); m->depth_hook = fn; m->depth_hook_user = user; }
 
 namespace {
 // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979): ring write, stream position, delayed read-out
@@ -1744,7 +1825,7 @@ int lm_finish(moshi_hot_model * m, int32_t text_token, std::vector<int32_t> audi
 }  // namespace
 
 namespace { void lm_finish_entry(moshi_hot_model * m, moshi_hot_model::InFlight & f); }
-extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens, int n_tokens, int32_t * text_token_out, int32_t * out_audio, float * vad) {
+extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens, int n_tokens, int32_t * text_token_out, int32_t * out_audio, float * vad) { STREAMS_REFUSE(-1);
     for (auto & o : m->inflight) lm_finish_entry(m, o);   // a blocking step behind run-ahead ones: those finish first (their results stay parked for lm_complete)
     const moshi_hot_config & c = m->cfg;
     const int ncb = c.n_q + 1, CT = (int) m->cache.size();
@@ -1896,7 +1977,7 @@ int lm_complete(moshi_hot_model * m, int32_t * text_token, int32_t * out_audio) 
 }
 }  // namespace
 
-extern "C" int moshi_hot_lm_step_run_ahead(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
+extern "C" int moshi_hot_lm_step_run_ahead(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) { STREAMS_REFUSE(-1);
     if (in_audio) lm_queue(m, in_audio);
     const size_t keep = in_audio ? 1 : 0;
     if (m->inflight.size() <= keep) return -1;          // nothing older to hand back yet
@@ -1908,7 +1989,69 @@ extern "C" int moshi_hot_lm_step(moshi_hot_model_t * m, const int32_t * in_audio
     return moshi_hot_lm_step_n(m, in_audio, m->cfg.n_q - io_dep_q, text_token_out, out_audio, nullptr);
 }
 
-extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float * embedding) {
+// moshi_lmgen_step (lm.h:778-979) of B lockstep streams: the host half runs per stream over its own delay ring, the Temporal and the Depth graph once
+// for all of them (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - moshi_hot_create_streams refuses those)
+extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
+    if (m->n_streams <= 1) return moshi_hot_lm_step(m, in_audio, text_token_out, out_audio);
+    const moshi_hot_config & c = m->cfg;
+    const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
+    if (!m->g_temporal) build_temporal_graph(m);
+    if (!m->g_depth) build_depth_graph_streams(m);
+    const int pos = m->offset % CT;
+    for (int b = 0; b < B; b++) {   // other speaker's codes enter each stream's delay ring (lm.h:819-824)
+        auto & cache = m->s_cache[(size_t) b];
+        for (int i = 0; i < needed; i++) cache[(size_t) ((m->offset + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
+    }
+    std::vector<int32_t> idx((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
+    std::vector<float> sc((size_t) B);
+    {
+    PhaseTimer pt(m, 1);
+    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed_step (lm.h:586-607) per stream: -1 -> scale 0, negative ids -> row 0
+        for (int b = 0; b < B; b++) {
+            int32_t id = m->offset <= c.delays[i] ? m->initial[(size_t) i] : m->s_cache[(size_t) b][(size_t) pos][(size_t) i];
+            sc[(size_t) b] = id == -1 ? 0.f : 1.f;
+            idx[(size_t) b] = id < 0 ? 0 : id;
+        }
+        ggml_backend_tensor_set(m->emb_idx[(size_t) i], idx.data(), 0, (size_t) B * 4);
+        ggml_backend_tensor_set(m->emb_scale[(size_t) i], sc.data(), 0, (size_t) B * 4);
+    }
+    transformer_graph_step(*m->scratch, m->temporal, 1);
+    m->scratch->compute_scratch();
+    m->g_temporal->compute();
+    ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
+    }
+    {
+    PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
+    for (int b = 0; b < B; b++) {
+        const int32_t id = text[(size_t) b];
+        sc[(size_t) b] = id == -1 ? 0.f : 1.f;
+        idx[(size_t) b] = id < 0 ? 0 : id;
+    }
+    ggml_backend_tensor_set(m->dep_text_idx, idx.data(), 0, (size_t) B * 4);
+    ggml_backend_tensor_set(m->dep_text_scale, sc.data(), 0, (size_t) B * 4);
+    m->g_depth->compute();
+    ggml_backend_tensor_get(m->dep_tokens, toks.data(), 0, toks.size() * 4);   // [dep_q][B]
+    }
+    // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per stream
+    m->offset++;
+    int ok = 1;
+    const int wpos = m->offset % CT;
+    for (int b = 0; b < B; b++) {
+        auto & cache = m->s_cache[(size_t) b];
+        cache[(size_t) wpos][0] = text[(size_t) b];
+        for (int q = 0; q < dep_q; q++) cache[(size_t) wpos][(size_t) (q + 1)] = toks[(size_t) q * B + b];
+        if (m->offset <= m->max_delay) { ok = 0; continue; }
+        text_token_out[b] = cache[(size_t) ((m->offset - m->max_delay + c.delays[0]) % CT)][0];
+        for (int i = 1; i < dep_q_1; i++) {
+            const int32_t v = cache[(size_t) ((m->offset - m->max_delay + c.delays[i]) % CT)][(size_t) i];
+            out_audio[(size_t) b * dep_q + (i - 1)] = v;
+            if (v == -1) ok = 0;
+        }
+    }
+    return ok;
+}
+
+extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float * embedding) { STREAMS_REFUSE();
     unstage_temporal(m);
     m->tok_state_for = -1;
     const moshi_hot_config & c = m->cfg;
@@ -1940,7 +2083,7 @@ extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float *
     m->offset++;
 }
 
-extern "C" void moshi_hot_set_conditions(moshi_hot_model_t * m, const float * sum, const float * cross) {
+extern "C" void moshi_hot_set_conditions(moshi_hot_model_t * m, const float * sum, const float * cross) { STREAMS_REFUSE();
     const moshi_hot_config & c = m->cfg;
     if (sum) { GGML_ASSERT(m->cond_sum); ggml_backend_tensor_set(m->cond_sum, sum, 0, (size_t) c.dim * 4); }
     if (cross) {
@@ -1949,7 +2092,7 @@ extern "C" void moshi_hot_set_conditions(moshi_hot_model_t * m, const float * su
         for (auto & L : m->temporal.layers) init_cross(*m->scratch, m->temporal, L, m->cond_cross);
     }
 }
-extern "C" void moshi_hot_set_text_hook(moshi_hot_model_t * m, moshi_hot_text_hook_t hook, void * user) { m->text_hook = hook; m->text_hook_user = user; }
+extern "C" void moshi_hot_set_text_hook(moshi_hot_model_t * m, moshi_hot_text_hook_t hook, void * user) { STREAMS_REFUSE(); m->text_hook = hook; m->text_hook_user = user; }
 
 // Batched prompt prefill: n_frames "provided" frames (every codebook given, lm.h:812-817) pushed through the Temporal stack as ONE
 // [dim, T] pass per chunk instead of T single-frame steps. The reference steps prompts frame by frame (lm.h:1063-1134) and discards
@@ -1957,7 +2100,7 @@ extern "C" void moshi_hot_set_text_hook(moshi_hot_model_t * m, moshi_hot_text_ho
 // what this leaves behind. The Depth graph is not run: every slot of its ring is rewritten by the next
 // frame before it is read. Falls back to single provided frames where a chunk would wrap the ring (the T > 1 mask table is only
 // causal before the wrap, torch.h:170-223).
-extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens, int n_frames, int chunk) {
+extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens, int n_frames, int chunk) { STREAMS_REFUSE();
     unstage_temporal(m);
     m->tok_state_for = -1;
     const moshi_hot_config & c = m->cfg;
@@ -2022,7 +2165,7 @@ static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] = { 3, 948, 243, 1178, 546, 1
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }
 
 // the same prompt frames through moshi_hot_prefill: identical state afterwards, a fraction of the time
-extern "C" void moshi_hot_personaplex_system_prompts_batched(moshi_hot_model_t * m, const int32_t * text_prompt, int n_text, int chunk) {
+extern "C" void moshi_hot_personaplex_system_prompts_batched(moshi_hot_model_t * m, const int32_t * text_prompt, int n_text, int chunk) { STREAMS_REFUSE();
     GGML_ASSERT(m->cfg.n_q + 1 == 17);
     std::vector<int32_t> frames((size_t) (12 + n_text) * 17);
     for (int f = 0; f < 12 + n_text; f++) {
@@ -2032,7 +2175,7 @@ extern "C" void moshi_hot_personaplex_system_prompts_batched(moshi_hot_model_t *
     moshi_hot_prefill(m, frames.data(), 12 + n_text, chunk);
 }
 
-extern "C" void moshi_hot_personaplex_system_prompts(moshi_hot_model_t * m, const int32_t * text_prompt, int n_text) {
+extern "C" void moshi_hot_personaplex_system_prompts(moshi_hot_model_t * m, const int32_t * text_prompt, int n_text) { STREAMS_REFUSE();
     GGML_ASSERT(m->cfg.n_q + 1 == 17);
     int32_t tokens[17], text, audio[MOSHI_HOT_MAX_CODEBOOKS];
     auto frame = [&](int32_t text_id) {
@@ -2046,7 +2189,7 @@ extern "C" void moshi_hot_personaplex_system_prompts(moshi_hot_model_t * m, cons
 }
 
 // one iteration of the moshi-sts --bench loop (tools/moshi-sts.cpp:770-808)
-extern "C" int moshi_hot_sts_frame(moshi_hot_model_t * m, const float * pcm_in, int32_t * text_token, int32_t * audio_tokens, float * pcm_out) {
+extern "C" int moshi_hot_sts_frame(moshi_hot_model_t * m, const float * pcm_in, int32_t * text_token, int32_t * audio_tokens, float * pcm_out) { STREAMS_REFUSE(-1);
     int32_t * codes = m->tokens_tmp.data();
     moshi_hot_mimi_encode(m, pcm_in, codes);
     if (!moshi_hot_lm_step(m, codes, text_token, audio_tokens)) return 0;
@@ -2058,12 +2201,12 @@ extern "C" int moshi_hot_sts_frame(moshi_hot_model_t * m, const float * pcm_in, 
 // frame k - 1 and encodes frame k + 1. Each graph sees exactly the inputs and states it sees in moshi_hot_sts_frame, in the same per-graph order
 // (encode 0, 1, 2 ...; decode 0, 1, 2 ...; LM 0, 1, 2 ...), so tokens and PCM are bit-identical; the hand-offs are host round trips (codes and
 // tokens are a few integers). Without a second stream the calls degenerate to the serial order.
-extern "C" void moshi_hot_sts_pipeline_begin(moshi_hot_model_t * m, const float * pcm0) {
+extern "C" void moshi_hot_sts_pipeline_begin(moshi_hot_model_t * m, const float * pcm0) { STREAMS_REFUSE();
     if (m->cfg.enable_mimi_encoder) moshi_hot_mimi_encode(m, pcm0, m->pipe_codes.data());     // (a model without encoder - tts - steps on no input codes)
     m->pipe_have_codes = true;
     m->pipe_have_tokens = false;
 }
-extern "C" int moshi_hot_sts_pipeline_frame(moshi_hot_model_t * m, const float * pcm_next, int32_t * text_token, int32_t * audio_tokens, float * pcm_prev) {
+extern "C" int moshi_hot_sts_pipeline_frame(moshi_hot_model_t * m, const float * pcm_next, int32_t * text_token, int32_t * audio_tokens, float * pcm_prev) { STREAMS_REFUSE(-1);
     GGML_ASSERT(m->pipe_have_codes && "moshi_hot_sts_pipeline_begin first");
     if (m->cfg.chain_depth == 2 && m->tok_state) {
         // run-ahead: the LM step of frame k is queued behind the one of frame k - 1 before that one's tokens are looked at; the tokens (and, as
@@ -2098,7 +2241,7 @@ extern "C" int moshi_hot_sts_pipeline_frame(moshi_hot_model_t * m, const float *
     if (ok) memcpy(m->pipe_tokens.data(), audio_tokens, (size_t) (m->cfg.personaplex ? 8 : m->cfg.dep_q) * sizeof(int32_t));
     return (ok ? 1 : 0) | (dec ? 2 : 0);
 }
-extern "C" int moshi_hot_sts_pipeline_end(moshi_hot_model_t * m, int32_t * text_token, int32_t * audio_tokens, float * pcm_last) {
+extern "C" int moshi_hot_sts_pipeline_end(moshi_hot_model_t * m, int32_t * text_token, int32_t * audio_tokens, float * pcm_last) { STREAMS_REFUSE(-1);
     if (m->cfg.chain_depth == 2 && m->tok_state) {
         int r = 0;
         while (!m->inflight.empty()) {           // at most one step is outstanding
@@ -2143,7 +2286,7 @@ extern "C" struct ggml_tensor * moshi_hot_weight(moshi_hot_model_t * m, const ch
 }
 extern "C" void moshi_hot_set_timing(moshi_hot_model_t * m, int on) { m->timing = on != 0; for (int i = 0; i < 4; i++) { m->phase_us[i] = 0; m->phase_n[i] = 0; } }
 extern "C" void moshi_hot_get_timing(moshi_hot_model_t * m, double * us_per_call) { for (int i = 0; i < 4; i++) us_per_call[i] = m->phase_n[i] ? m->phase_us[i] / (double) m->phase_n[i] : 0.0; }
-extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, const int32_t * audio_tokens) {
+extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, const int32_t * audio_tokens) { STREAMS_REFUSE();
     const int wpos = m->offset % (int) m->cache.size();
     m->cache[(size_t) wpos][0] = text_token;
     for (int q = 0; q < m->cfg.dep_q; q++) m->cache[(size_t) wpos][(size_t) (q + 1)] = audio_tokens[q];
@@ -2158,7 +2301,7 @@ extern "C" void moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset
 // The K (kv = 0) / V (kv = 1) ring of one layer as the bytes it holds (BF16 [D, C, H]), out of / into the model: parity runs that restart every frame from
 // another executor's state (tests/test_full_width_parity.py: teacher forcing per frame on the benchmark's own weights). Returns the ring's size in bytes;
 // copies min(nbytes, size) when buf is not NULL. which: 0 Temporal, 1 Depth.
-extern "C" int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int layer, int kv, void * buf, int64_t nbytes, int write) {
+extern "C" int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int layer, int kv, void * buf, int64_t nbytes, int write) { STREAMS_REFUSE(-1);
     Transformer & tr = which == 0 ? m->temporal : m->depth;
     if (layer < 0 || layer >= (int) tr.layers.size()) return -1;
     T t = kv == 0 ? tr.layers[(size_t) layer].kcache : tr.layers[(size_t) layer].vcache;
@@ -2172,7 +2315,7 @@ extern "C" int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int la
 }
 
 // identical pseudo-random BF16 rows in every slot of the K / V rings (tests: long-context attention against the oracle over a known cache)
-extern "C" void moshi_hot_fill_ring(moshi_hot_model_t * m, int which, int layer, uint64_t seed, float scale) {
+extern "C" void moshi_hot_fill_ring(moshi_hot_model_t * m, int which, int layer, uint64_t seed, float scale) { STREAMS_REFUSE();
     Transformer & tr = which == 0 ? m->temporal : m->depth;
     for (int l = 0; l < (int) tr.layers.size(); l++) {
         if (layer >= 0 && l != layer) continue;
@@ -2199,7 +2342,7 @@ extern "C" void moshi_hot_fill_ring(moshi_hot_model_t * m, int which, int layer,
 }
 
 extern "C" int moshi_hot_layer_probe(moshi_hot_model_t * m, int which, int layer, int weight_set, const float * x_in, int offset, float * x_out,
-                                     moshi_hot_node_visitor_t visit, void * user) {
+                                     moshi_hot_node_visitor_t visit, void * user) { STREAMS_REFUSE(-1);
     Transformer & tr = which == 0 ? m->temporal : m->depth;
     GGML_ASSERT(layer >= 0 && layer < (int) tr.layers.size());
     Layer & L = tr.layers[(size_t) layer];

@@ -41,6 +41,9 @@ SIGNATURES = {
     "moshi_hot_personaplex_system_prompts_batched": (None, [P, P, C.c_int, C.c_int]),
     "moshi_hot_create": (P, [P, C.POINTER(Config), C.c_uint64]),
     "moshi_hot_free": (None, [P]),
+    "moshi_hot_create_streams": (P, [P, C.POINTER(Config), C.c_uint64, C.c_int]),
+    "moshi_hot_lm_step_streams": (C.c_int, [P, P, P, P]),
+    "moshi_hot_n_streams": (C.c_int, [P]),
     "moshi_hot_save_gguf": (C.c_int, [P, C.c_char_p]),
     "moshi_hot_create_from_gguf": (P, [P, C.POINTER(Config), C.c_char_p]),
     "moshi_hot_tensor_file_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
