@@ -113,6 +113,28 @@ GGML_API moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, co
 GGML_API int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio);
 GGML_API int moshi_hot_n_streams(moshi_hot_model_t * m);
 
+// ---- stream slots: B independent conversations over one set of weights, admitted and retired mid-batch ----------------------------------------
+// A lockstep-streams model whose B columns each have a stream position of their own: slot b's mask row, RoPE phase and ring slot follow its own
+// position, so a conversation can start in any frame while the others run on. Same configurations as moshi_hot_create_streams, 2 <= n_slots <= 16;
+// anything else returns NULL (one conversation: moshi_hot_create). All slots start closed.
+// A closed slot still occupies its column: it is stepped frozen at its position, fed the initial tokens, writes only its own KV ring rows, and its
+// results are discarded. moshi_hot_read_last returns B rows and moshi_hot_n_streams returns B, as on a streams model. The single-stream calls and
+// moshi_hot_lm_step_streams refuse as on a streams model (moshi_hot_lm_step_streams returns -1); moshi_hot_set_context_fill does nothing.
+GGML_API moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots);
+// slot b starts a new conversation at stream position 0 with the delay ring of a fresh stream. Its KV ring rows are NOT cleared: the mask row of
+// position p admits ring slots 0..p only, each rewritten by the new conversation before it is admitted, so the previous occupant's rows are never
+// read. Returns 0, or -1 for a bad index or a model that is not a slots model.
+GGML_API int moshi_hot_slot_open(moshi_hot_model_t * m, int b);
+GGML_API int moshi_hot_slot_close(moshi_hot_model_t * m, int b);   // 0, or -1 as moshi_hot_slot_open
+// slot b's stream position: frames stepped since it was opened (unless moshi_hot_slot_set_fill moved it), -1 if it is closed or b is bad
+GGML_API int64_t moshi_hot_slot_position(moshi_hot_model_t * m, int b);
+// moshi_hot_set_context_fill for one slot (long-context tests and benchmarks): moves slot b's stream position only, not its delay ring
+GGML_API void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offset);
+// one frame of every slot. Layouts as moshi_hot_lm_step_streams; the codes of closed slots are ignored. status = B entries: 1 when slot b's outputs
+// are valid, 0 while its own delay ring fills, -1 when it is closed; the outputs of a slot whose status is not 1 are written as -1. Returns the
+// number of slots with status 1, or -1 on a model that is not a slots model. With no slot open it does no device work and returns 0.
+GGML_API int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio, int32_t * status);
+
 // mimi_encode_send + mimi_encode_receive (src/moshi.cpp:215-234): 1920 samples -> mimi_n_q codes
 GGML_API void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, int32_t * codes);
 // mimi_decode_send + mimi_decode_receive (src/moshi.cpp:273-292): mimi_n_q codes -> 1920 samples

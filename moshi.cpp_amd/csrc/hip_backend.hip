@@ -964,6 +964,8 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
 
 // B''. the same single-token attention block over B > 1 lockstep streams (moshi_hot_create_streams): q / k / v [D, 1, H, B], rings [D, C, H, B] written
 //      at one shared slot, one shared mask row and RoPE phase, output [D, H, 1, B]. One launch of B x H workgroups (k_attn_streams).
+//      Stream slots (moshi_hot_create_slots) give every stream its own position: a mask [C, 1, 1, B] (one contiguous row per stream), an index [1, 1, B]
+//      (one ring slot per stream) and RoPE halves [D/2, 1, 1, B] (one timestep-table row per stream) - the same launch with per-stream strides.
 static bool match_attention_streams(const analysis & an, int pos, attn_group & grp) {
     const ggml_tensor * sm = an.g->nodes[pos];
     if (sm->op != GGML_OP_SOFT_MAX || !sm->src[1]) return false;
@@ -985,20 +987,29 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], B = kc->ne[3];
     if (B < 2 || qo->ne[0] != D || qo->ne[1] != 1 || qo->ne[2] != H || qo->ne[3] != B) return false;
     if (vc->ne[0] != D || vc->ne[1] != C || vc->ne[2] != H || vc->ne[3] != B) return false;
-    if (mask->type != GGML_TYPE_F32 || mask->ne[0] != C || mask->ne[1] != 1 || ggml_nelements(mask) != C || !ggml_is_contiguous(mask)) return false;   // one shared row
+    if (mask->type != GGML_TYPE_F32 || mask->ne[0] != C || mask->ne[1] != 1 || !ggml_is_contiguous(mask)) return false;
+    const bool mask_per_stream = mask->ne[2] == 1 && mask->ne[3] == B && ggml_nelements(mask) == C * B;   // one row per stream (slots)
+    if (!mask_per_stream && ggml_nelements(mask) != C) return false;                                      // or one shared row
     if (D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
     if (kc->src[1] != vc->src[1]) return false;
     const ggml_tensor * idx = kc->src[1];
-    if (idx->type != GGML_TYPE_I32 || ggml_nelements(idx) != 1 || !ggml_is_contiguous(idx)) return false;   // one shared slot
+    if (idx->type != GGML_TYPE_I32 || !ggml_is_contiguous(idx)) return false;
+    const bool index_per_stream = idx->ne[0] == 1 && idx->ne[1] == 1 && idx->ne[2] == B && ggml_nelements(idx) == B;   // one ring slot per stream (slots)
+    if (!index_per_stream && ggml_nelements(idx) != 1) return false;                                                    // or one shared slot
     if (kc->nb[0] != 2 || vc->nb[0] != 2) return false;
 
     const ggml_tensor * ko = kc->src[0], * vrow = vc->src[0];
     const ggml_tensor * qsrc = qo, * ksrc = ko, * rotr = nullptr, * roti = nullptr;
+    int64_t rot_bs = 0;
     if (qo->op == GGML_OP_CONCAT) {
         const ggml_tensor * rotr2, * roti2;
         if (!match_rope(qo, &qsrc, &rotr, &roti) || !match_rope(ko, &ksrc, &rotr2, &roti2) || rotr != rotr2 || roti != roti2) return false;
         if (rotr->type != GGML_TYPE_F32 || rotr->ne[0] != D / 2 || rotr->ne[1] != 1 || (const char *) roti->data != (const char *) rotr->data + D / 2 * 4) return false;
-        if (rotr->nb[0] != 4 || ggml_nelements(rotr) != D / 2) return false;   // one shared RoPE row
+        if (rotr->nb[0] != 4) return false;
+        if (ggml_nelements(rotr) == D / 2) rot_bs = 0;                                                            // one shared RoPE row
+        else if (rotr->ne[2] == 1 && rotr->ne[3] == B && roti->type == GGML_TYPE_F32 && ggml_are_same_shape(rotr, roti) && roti->nb[3] == rotr->nb[3] &&
+                 (int64_t) rotr->nb[3] == D * 4) rot_bs = D;                                                       // one row of the [D, B] table per stream
+        else return false;
     }
     if (qsrc->type != GGML_TYPE_F32 || ksrc->type != GGML_TYPE_F32 || vrow->type != GGML_TYPE_F32) return false;
     for (const ggml_tensor * t : { qsrc, ksrc, vrow }) if (t->ne[0] != D || t->ne[1] != 1 || t->ne[2] != H || t->ne[3] != B) return false;
@@ -1073,8 +1084,57 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     grp.sa.q_bs = qs.nb[3] / 4; grp.sa.k_bs = ks.nb[3] / 4; grp.sa.v_bs = vs.nb[3] / 4;
     grp.sa.kc_bs = (int64_t) kc->nb[3]; grp.sa.vc_bs = (int64_t) vc->nb[3];
     grp.sa.out_bs = H * D;
+    grp.sa.mask_bs = mask_per_stream ? C : 0;
+    grp.sa.rot_bs = rot_bs;
+    grp.sa.index_bs = index_per_stream ? 1 : 0;
     grp.members = members;
     grp.emit_pos = pos_of(an, x2);
+    return true;
+}
+
+// B'''. stream slots' mask rows (moshi_hot.cpp transformer_graph_step_slots): for r = 0 .. n-1, in graph order, cont_r = cont(view of a dense row of the
+//      bias table, n_el floats at the slot's own column) and cpy(cont_r, view of dst at row r) - n >= 2 rows of one destination, consecutive and in order.
+//      Every source is read at the last cpy instead of at its cont: only layout nodes may sit between the members.
+struct row_copy_group { copy_rows_args a; int emit_pos; std::vector<int> members; };
+static bool match_row_copies(const analysis & an, int pos, row_copy_group & grp) {
+    const ggml_cgraph * g = an.g;
+    memset(&grp.a, 0, sizeof(grp.a));
+    grp.members.clear();
+    const ggml_tensor * dst_root = nullptr, * src_root = nullptr;
+    const char * dst0 = nullptr;
+    int64_t n_el = 0;
+    int rows = 0, i = pos;
+    while (i < g->n_nodes && rows < COPY_ROWS_MAX) {
+        const ggml_tensor * ct = g->nodes[i];
+        if (is_view_op(ct->op) && !an.skip[(size_t) i]) { i++; continue; }   // (the views that feed the next pair)
+        if (ct->op != GGML_OP_CONT || an.skip[(size_t) i] || uses_of(an, ct) != 1 || ct->view_src || ct->type != GGML_TYPE_F32 || !ct->data) break;
+        const ggml_tensor * sv = ct->src[0];
+        if (sv->type != GGML_TYPE_F32 || sv->op != GGML_OP_VIEW || !sv->view_src || !sv->data || sv->nb[0] != 4 || ggml_nelements(sv) != sv->ne[0]) break;
+        if (rows == 0) { n_el = sv->ne[0]; src_root = sv->view_src; }
+        if (sv->ne[0] != n_el || sv->view_src != src_root || ggml_nelements(ct) != n_el) break;
+        // the pair's cpy: the next node that is not a layout op
+        int j = i + 1;
+        while (j < g->n_nodes && is_view_op(g->nodes[j]->op)) j++;
+        if (j >= g->n_nodes || an.skip[(size_t) j]) break;
+        const ggml_tensor * cp = g->nodes[j];
+        if (cp->op != GGML_OP_CPY || cp->src[0] != ct || cp->type != GGML_TYPE_F32 || !ggml_is_contiguous(cp) || ggml_nelements(cp) != n_el || !cp->data) break;
+        const ggml_tensor * root = cp->view_src;
+        while (root && root->view_src) root = root->view_src;
+        if (!root || root == src_root) break;
+        if (rows == 0) { dst_root = root; dst0 = (const char *) cp->data; }
+        if (root != dst_root || (const char *) cp->data != dst0 + (size_t) rows * (size_t) n_el * 4) break;
+        if ((const char *) cp->data + n_el * 4 > (const char *) root->data + ggml_nbytes(root)) break;
+        grp.a.src[rows] = (const float *) sv->data;
+        grp.members.push_back(i);
+        grp.members.push_back(j);
+        grp.emit_pos = j;
+        rows++;
+        i = j + 1;
+    }
+    if (rows < 2) return false;
+    grp.a.dst = (float *) dst0;
+    grp.a.n = n_el;
+    grp.a.rows = rows;
     return true;
 }
 
@@ -1872,6 +1932,16 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             const embed_sum_args a = grp.a;
             at_pos[i].push_back([=](hipStream_t s) { k_embed_sum(s, a); });
             p->n_fused += (int) grp.members.size();
+        }
+        // a run of cpy(cont(window of a table), row r of dst) for r = 0, 1, .. (stream slots: the B mask rows, moshi_hot.cpp transformer_graph_step_slots):
+        // one launch for all rows instead of one per row
+        for (int i = 0; i < g->n_nodes; i++) {
+            row_copy_group rg;
+            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_CONT || !match_row_copies(an, i, rg)) continue;
+            for (int m : rg.members) an.skip[(size_t) m] = 1;
+            const copy_rows_args ra = rg.a;
+            at_pos[rg.emit_pos].push_back([=](hipStream_t s) { k_copy_rows(s, ra); });
+            p->n_fused += (int) rg.members.size();
         }
         // cpy(cont(x), dst): copy the strided source straight into dst (the per-step mask row: cont(view of the bias table) -> cpy into the graph input,
         // transformer.h:1259-1289 - two launches on the LM stream in front of every Temporal graph)

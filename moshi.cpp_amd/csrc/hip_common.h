@@ -197,9 +197,15 @@ void k_attn_decode(hipStream_t s, const attn_args & a, void * ws = nullptr, unsi
 // Lockstep streams (moshi_hot_create_streams): the single-token attention block of B streams at one shared position - one workgroup per (head, stream),
 // each doing exactly what attn_decode_kernel's workgroup of that head does (attn_decode_body, same order of operations) on stream b's q / k / v rows,
 // ring and output row. `a` describes stream 0 (T = 1); stream b's pointers are a's plus b times the *_bs strides (floats for q / k / v / out, bytes for
-// the rings). The mask row, the RoPE table and the ring slot are shared.
-struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs; };
+// the rings). The mask row, the RoPE row and the ring slot index are shared by all streams (lockstep: mask_bs = rot_bs = index_bs = 0) or one per
+// stream (stream slots, moshi_hot_create_slots: mask_bs = C, rot_bs = D floats, index_bs = 1), each workgroup then scanning its own stream's mask row.
+struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs, mask_bs, rot_bs, index_bs; };
 void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err = nullptr);
+// rows consecutive rows of n floats, row r copied from its own source src[r] (stream slots: the B mask rows, each a window of the bias table at the
+// slot's own column, transformer.h:1259-1289) - one launch instead of one per row
+#define COPY_ROWS_MAX 16
+struct copy_rows_args { const float * src[COPY_ROWS_MAX]; float * dst; int64_t n; int rows; };
+void k_copy_rows(hipStream_t s, const copy_rows_args & a);
 
 // in_proj + the attention that consumes it as ONE launch of 256 resident workgroups (inproj_attn_kernel): `a` is the RMS-normed Q4_K mat-vec whose output
 // holds `at`'s q | k | v. supported(): shapes, and whether the whole grid fits the compute units the stream may use (the parts of a head wait for each

@@ -1775,6 +1775,8 @@ attn_streams_kernel(attn_streams_args sa, attn_split_ws w) {
     a.q += b * sa.q_bs; a.k += b * sa.k_bs; a.v += b * sa.v_bs;
     a.kcache += b * sa.kc_bs; a.vcache += b * sa.vc_bs;
     a.out += b * sa.out_bs;
+    a.mask += b * sa.mask_bs; a.index += b * sa.index_bs;   // (stream slots: stream b's own mask row and ring slot; lockstep: strides 0)
+    if (a.rot) a.rot += b * sa.rot_bs;
     attn_decode_body<false, NWA, AT_PLAIN>(a, w, smem, (int) blockIdx.x, 0, 0);
 }
 void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err) {
@@ -1798,6 +1800,19 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
     const dim3 grid((unsigned) a.H, (unsigned) sa.B);
     if (wide) attn_streams_kernel<ATTN_NW_WIDE><<<grid, ATTN_NW_WIDE * 64, smem, s>>>(sa, w);
     else      attn_streams_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(sa, w);
+}
+
+// row r of the destination <- src[r]: workgroup (x, r) copies 256 floats of row r (the row pointer is uniform: a kernel-argument load)
+__global__ void __launch_bounds__(256) copy_rows_kernel(copy_rows_args a) {
+    const int r = (int) blockIdx.y;
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.rows || i >= a.n) return;
+    a.dst[(int64_t) r * a.n + i] = a.src[r][i];
+}
+void k_copy_rows(hipStream_t s, const copy_rows_args & a) {
+    GGML_ASSERT(a.rows >= 1 && a.rows <= COPY_ROWS_MAX && a.n >= 1);
+    const dim3 grid((unsigned) ((a.n + 255) / 256), (unsigned) a.rows);
+    copy_rows_kernel<<<grid, 256, 0, s>>>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------

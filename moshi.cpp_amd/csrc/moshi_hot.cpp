@@ -552,6 +552,41 @@ T transformer_graph_build(Builder & g, Transformer & tr, T x) {
     return x;
 }
 
+// transformer_graph_build for stream slots (moshi_hot_create_slots): x = [dim, 1, B], every column at a stream position of its own. The position
+// inputs gain the batch dimension: g_bias [C, 1, 1, B] (one mask row per slot), g_offset [B] (one RoPE phase per slot: the timestep table [D, B],
+// viewed as [D/2, 1, 1, B] halves that apply_rope's products broadcast over the heads) and g_indices [1, 1, B] (one ring slot per slot).
+T transformer_graph_build_slots(Builder & g, Transformer & tr, T x) {
+    const int64_t B = x->ne[2], C = tr.capacity, D = tr.dim / tr.heads;
+    create_bias_pattern(g.be, tr, 1);
+    tr.g_bias = g.tensor(GGML_TYPE_F32, C, 1, 1, B);
+    Rot rot;
+    if (tr.max_period) {
+        tr.g_offset = g.tensor(GGML_TYPE_F32, B);
+        T table = ggml_timestep_embedding(g, tr.g_offset, (int) D, tr.max_period);   // (the single stream's arange(1) + offset is offset exactly)
+        rot.rotr = ggml_view_4d(g, table, D / 2, 1, 1, B, table->nb[1], table->nb[1], table->nb[1], 0);
+        rot.roti = ggml_view_4d(g, table, D / 2, 1, 1, B, table->nb[1], table->nb[1], table->nb[1], table->nb[0] * (size_t) (D / 2));
+    }
+    tr.g_indices = g.tensor(GGML_TYPE_I32, 1, 1, B);
+    for (auto & L : tr.layers) x = transformer_layer(g, tr, L, 0, tr.g_indices, x, tr.g_bias, tr.max_period ? &rot : nullptr, false);
+    return x;
+}
+
+// transformer_graph_step of stream slots: slot b's mask row (bias_pattern_index at pos[b], copied into row b of g_bias by the scratch graph - the
+// device plan copies the B windows of the bias table in one launch), its RoPE phase and its ring slot pos[b] % C. tr.offset is not used.
+void transformer_graph_step_slots(Builder & scratch, Transformer & tr, const std::vector<int64_t> & pos) {
+    const int B = (int) pos.size(), C = tr.capacity;
+    std::vector<float> off((size_t) B);
+    std::vector<int32_t> idx((size_t) B);
+    for (int b = 0; b < B; b++) {
+        T bias = bias_pattern_index(scratch, tr, 1, (int) pos[(size_t) b]);
+        scratch.expand(ggml_cpy(scratch, bias, ggml_view_1d(scratch, tr.g_bias, C, (size_t) b * (size_t) C * 4)));
+        off[(size_t) b] = (float) pos[(size_t) b];
+        idx[(size_t) b] = (int32_t) (pos[(size_t) b] % C);
+    }
+    if (tr.g_offset) ggml_backend_tensor_set(tr.g_offset, off.data(), 0, off.size() * 4);
+    ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
+}
+
 // moshi_streaming_transformer_graph_step (transformer.h:1259-1289): refresh mask, rope offset, ring slots
 void transformer_graph_step(Builder & scratch, Transformer & tr, int Tn) {
     const int offset = tr.offset;
@@ -787,6 +822,9 @@ struct moshi_hot_model {
     int offset = 0; std::vector<std::vector<int>> cache; std::vector<int> initial; int max_delay = 0;
     // lockstep streams (moshi_hot_create_streams): B > 1 = the batch dimension of every LM activation and KV ring; one delay ring per stream
     int n_streams = 1; std::vector<std::vector<std::vector<int>>> s_cache;
+    // stream slots (moshi_hot_create_slots): one stream position per column. s_frames = frames stepped since the slot was opened (its delay ring's
+    // offset), s_pos = its stream position (mask row, RoPE phase, ring slot; moshi_hot_slot_set_fill moves it alone). A closed slot keeps both.
+    bool slots = false; std::vector<char> s_open; std::vector<int64_t> s_frames, s_pos;
 
     // Mimi
     Rvq rvq_first, rvq_rest;
@@ -951,7 +989,7 @@ void build_temporal_graph(moshi_hot_model * m) {
     m->g_temporal = new Builder(m->be, 256);
     Builder & g = *m->g_temporal;
     T input = build_input_embedding(m, g);
-    T x = transformer_graph_build(g, m->temporal, input);
+    T x = m->slots ? transformer_graph_build_slots(g, m->temporal, input) : transformer_graph_build(g, m->temporal, input);
     m->g_stack_out = x;
     x = apply_norm(g, m->out_norm, x);
     m->g_transformer_out = x;
@@ -1142,6 +1180,37 @@ extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, 
     return create_model(backend, cfg, seed, nullptr, n_streams);
 }
 extern "C" int moshi_hot_n_streams(moshi_hot_model_t * m) { return m->n_streams; }
+// stream slots (moshi_hot.h): a lockstep-streams model whose columns each keep a position of their own; every slot starts closed
+extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
+    if (n_slots < 2 || n_slots > 16) return nullptr;
+    moshi_hot_model_t * m = moshi_hot_create_streams(backend, cfg, seed, n_slots);
+    if (!m) return nullptr;
+    m->slots = true;   // (before the first step: build_temporal_graph reads it)
+    m->s_open.assign((size_t) n_slots, 0);
+    m->s_frames.assign((size_t) n_slots, 0);
+    m->s_pos.assign((size_t) n_slots, 0);
+    return m;
+}
+extern "C" int moshi_hot_slot_open(moshi_hot_model_t * m, int b) {
+    if (!m->slots || b < 0 || b >= m->n_streams) return -1;
+    m->s_open[(size_t) b] = 1;
+    m->s_frames[(size_t) b] = m->s_pos[(size_t) b] = 0;
+    m->s_cache[(size_t) b] = m->cache;   // a fresh stream's delay ring (create_model): -2 everywhere
+    return 0;
+}
+extern "C" int moshi_hot_slot_close(moshi_hot_model_t * m, int b) {
+    if (!m->slots || b < 0 || b >= m->n_streams) return -1;
+    m->s_open[(size_t) b] = 0;
+    return 0;
+}
+extern "C" int64_t moshi_hot_slot_position(moshi_hot_model_t * m, int b) {
+    if (!m->slots || b < 0 || b >= m->n_streams || !m->s_open[(size_t) b]) return -1;
+    return m->s_pos[(size_t) b];
+}
+extern "C" void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offset) {
+    if (!m->slots || b < 0 || b >= m->n_streams || offset < 0) return;
+    m->s_pos[(size_t) b] = offset;
+}
 // the model's weights come from a GGUF file written by moshi_hot_save_gguf (the reference's `*.gguf` checkpoints: WeightLoader::from_gguf + load_gguf)
 extern "C" moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, const struct moshi_hot_config * cfg, const char * path) { return create_model(backend, cfg, 0, path); }
 // WeightLoader::save_gguf (loader.h:227-233): every tensor of the weight context, in context order
@@ -1992,6 +2061,7 @@ extern "C" int moshi_hot_lm_step(moshi_hot_model_t * m, const int32_t * in_audio
 // moshi_lmgen_step (lm.h:778-979) of B lockstep streams: the host half runs per stream over its own delay ring, the Temporal and the Depth graph once
 // for all of them (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - moshi_hot_create_streams refuses those)
 extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
+    if (m->slots) return -1;   // (moshi_hot_lm_step_slots)
     if (m->n_streams <= 1) return moshi_hot_lm_step(m, in_audio, text_token_out, out_audio);
     const moshi_hot_config & c = m->cfg;
     const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
@@ -2049,6 +2119,86 @@ extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * 
         }
     }
     return ok;
+}
+
+// moshi_lmgen_step of B stream slots: moshi_hot_lm_step_streams with a position per slot. Each open slot's host half runs over its own delay ring at
+// its own offset (s_frames); a closed slot is fed the initial tokens at its frozen position and its results are dropped.
+extern "C" int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
+    if (!m->slots) return -1;
+    const moshi_hot_config & c = m->cfg;
+    const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
+    int n_open = 0;
+    for (int b = 0; b < B; b++) {
+        status[b] = m->s_open[(size_t) b] ? 0 : -1;
+        text_token_out[b] = -1;
+        for (int q = 0; q < dep_q; q++) out_audio[(size_t) b * dep_q + q] = -1;
+        n_open += m->s_open[(size_t) b];
+    }
+    if (!n_open) return 0;
+    if (!m->g_temporal) build_temporal_graph(m);
+    if (!m->g_depth) build_depth_graph_streams(m);
+    for (int b = 0; b < B; b++) {   // other speaker's codes enter each open slot's delay ring (lm.h:819-824)
+        if (!m->s_open[(size_t) b]) continue;
+        auto & cache = m->s_cache[(size_t) b];
+        const int64_t off = m->s_frames[(size_t) b];
+        for (int i = 0; i < needed; i++) cache[(size_t) ((off + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
+    }
+    std::vector<int32_t> idx((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
+    std::vector<float> sc((size_t) B);
+    {
+    PhaseTimer pt(m, 1);
+    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed_step (lm.h:586-607) per slot: -1 -> scale 0, negative ids -> row 0
+        for (int b = 0; b < B; b++) {
+            const int64_t off = m->s_frames[(size_t) b];
+            const int32_t id = !m->s_open[(size_t) b] || off <= c.delays[i] ? m->initial[(size_t) i] : m->s_cache[(size_t) b][(size_t) (off % CT)][(size_t) i];
+            sc[(size_t) b] = id == -1 ? 0.f : 1.f;
+            idx[(size_t) b] = id < 0 ? 0 : id;
+        }
+        ggml_backend_tensor_set(m->emb_idx[(size_t) i], idx.data(), 0, (size_t) B * 4);
+        ggml_backend_tensor_set(m->emb_scale[(size_t) i], sc.data(), 0, (size_t) B * 4);
+    }
+    transformer_graph_step_slots(*m->scratch, m->temporal, m->s_pos);
+    m->scratch->compute_scratch();
+    m->g_temporal->compute();
+    ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
+    }
+    {
+    PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
+    for (int b = 0; b < B; b++) {
+        const int32_t id = text[(size_t) b];
+        sc[(size_t) b] = id == -1 ? 0.f : 1.f;
+        idx[(size_t) b] = id < 0 ? 0 : id;
+    }
+    ggml_backend_tensor_set(m->dep_text_idx, idx.data(), 0, (size_t) B * 4);
+    ggml_backend_tensor_set(m->dep_text_scale, sc.data(), 0, (size_t) B * 4);
+    m->g_depth->compute();
+    ggml_backend_tensor_get(m->dep_tokens, toks.data(), 0, toks.size() * 4);   // [dep_q][B]
+    }
+    // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per open slot
+    int n_valid = 0;
+    std::vector<int32_t> aud((size_t) dep_q);
+    for (int b = 0; b < B; b++) {
+        if (!m->s_open[(size_t) b]) continue;
+        const int64_t off = ++m->s_frames[(size_t) b];
+        m->s_pos[(size_t) b]++;
+        auto & cache = m->s_cache[(size_t) b];
+        const size_t wpos = (size_t) (off % CT);
+        cache[wpos][0] = text[(size_t) b];
+        for (int q = 0; q < dep_q; q++) cache[wpos][(size_t) (q + 1)] = toks[(size_t) q * B + b];
+        if (off <= m->max_delay) continue;
+        const int32_t t = cache[(size_t) ((off - m->max_delay + c.delays[0]) % CT)][0];
+        bool ok = true;
+        for (int i = 1; i < dep_q_1; i++) {
+            aud[(size_t) (i - 1)] = cache[(size_t) ((off - m->max_delay + c.delays[i]) % CT)][(size_t) i];
+            if (aud[(size_t) (i - 1)] == -1) ok = false;
+        }
+        if (!ok) continue;
+        status[b] = 1;
+        text_token_out[b] = t;
+        for (int q = 0; q < dep_q; q++) out_audio[(size_t) b * dep_q + q] = aud[(size_t) q];
+        n_valid++;
+    }
+    return n_valid;
 }
 
 extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float * embedding) { STREAMS_REFUSE();
@@ -2293,6 +2443,7 @@ extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, 
     m->tok_state_for = -1;   // the device-side token state still holds the model's own samples
 }
 extern "C" void moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset) {
+    if (m->slots) return;   // (a position per slot: moshi_hot_slot_set_fill)
     unstage_temporal(m);
     m->temporal.offset = (int) offset;
     if (m->tp_x) m->temporal_tp.offset = (int) offset;   // tensor-parallel frame mode steps its own stack (head-sliced rings): same stream position
