@@ -95,26 +95,28 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 
 // ---- lockstep streams: B conversations stepped together over one set of weights ------------------------------------------------------------
 // The reference's batch dimension (moshi_kv_cache_state's batch_size, transformer.h:155-171, fixed to 1 at :326-328) made real: activations are
-// [dim, 1, B], the KV rings [D, capacity, H, B], the token inputs B per codebook. All B streams share the stream position, so the mask row, the RoPE
-// phase and the ring slot are common; each stream has its own delay ring (lm.h:715-743) and its own KV ring rows. Every weight is read once per step
-// for all B streams. n_streams == 1 builds exactly moshi_hot_create's model.
+// [dim, 1, B], the KV rings [D, capacity, H, B], the token inputs B per codebook. Each column holds one conversation with its own delay ring
+// (lm.h:715-743), its own KV ring rows, its frame count and its stream position. Every weight is read once per step for all B columns. A lockstep
+// model and a slots model (below) are this one model and step alike; they differ only in where a column's position comes from. Here every column
+// is open from creation and all B share one stream position, so the mask row, the RoPE phase and the ring slot are common.
+// n_streams == 1 builds exactly moshi_hot_create's model.
 // n_streams > 1 takes the moshika-shaped LM only: enable_lm = 1 with both codec halves off, personaplex = 0, no demux / cross-attention / condition_sum /
 // extra heads / low-rank embeddings / weight schedule / delay_steps, tp_world == 0, dep_shard_world <= 1, depth_only == 0, chain_depth == 0,
 // codec_stream == 0, and 1 <= n_streams <= 16. Anything else returns NULL.
 // On such a model moshi_hot_read_last("text_logits" | "transformer_out" | "dep_logits<k>") returns B consecutive rows (stream 0 first), and
-// moshi_hot_set_context_fill moves the shared stream position as ever. The single-stream frame calls (moshi_hot_lm_step*, moshi_hot_sts_*,
+// moshi_hot_set_context_fill moves the shared stream position, not the delay rings. The single-stream frame calls (moshi_hot_lm_step*, moshi_hot_sts_*,
 // moshi_hot_ring_bytes, moshi_hot_host_ring, moshi_hot_layer_probe) return -1, and the calls without a result (moshi_hot_mimi_*, moshi_hot_prefill,
 // moshi_hot_personaplex_system_prompts*, moshi_hot_lm_step_embedding, moshi_hot_fill_ring, moshi_hot_force_last, moshi_hot_set_conditions, the hooks,
 // moshi_hot_depth_shard_* and moshi_hot_tp_*) do nothing; moshi_hot_depth_shard_msg / _tout and moshi_hot_tp_msg return NULL.
 GGML_API moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams);
 // one frame of every stream (moshi_lmgen_step, lm.h:778-979, B times in lockstep): in_audio = B x (n_q - dep_q) codes (stream-major), text_token = B,
-// out_audio = B x dep_q (stream-major). Returns 1 when the outputs are valid, 0 while the delay ring fills (the same for every stream), -1 on a
-// single-stream model.
+// out_audio = B x dep_q (stream-major). Returns 1 when every stream's outputs are valid, else 0: while the delay rings fill (the same for every
+// stream; nothing is written) or when an audio token is -1 (every stream's outputs are written). -1 on a slots model; moshi_hot_lm_step when B = 1.
 GGML_API int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio);
 GGML_API int moshi_hot_n_streams(moshi_hot_model_t * m);
 
 // ---- stream slots: B independent conversations over one set of weights, admitted and retired mid-batch ----------------------------------------
-// A lockstep-streams model whose B columns each have a stream position of their own: slot b's mask row, RoPE phase and ring slot follow its own
+// The B-column model of moshi_hot_create_streams with a stream position per column: slot b's mask row, RoPE phase and ring slot follow its own
 // position, so a conversation can start in any frame while the others run on. Same configurations as moshi_hot_create_streams, 2 <= n_slots <= 16;
 // anything else returns NULL (one conversation: moshi_hot_create). All slots start closed.
 // A closed slot still occupies its column: it is stepped frozen at its position, fed the initial tokens, writes only its own KV ring rows, and its

@@ -587,16 +587,19 @@ void transformer_graph_step_slots(Builder & scratch, Transformer & tr, const std
     ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
 }
 
-// moshi_streaming_transformer_graph_step (transformer.h:1259-1289): refresh mask, rope offset, ring slots
-void transformer_graph_step(Builder & scratch, Transformer & tr, int Tn) {
-    const int offset = tr.offset;
-    tr.offset += Tn;
+// moshi_streaming_transformer_graph_step (transformer.h:1259-1289): refresh mask, rope offset, ring slots for the Tn positions from `offset` on
+void transformer_graph_step_at(Builder & scratch, Transformer & tr, int Tn, int offset) {
     T bias = bias_pattern_index(scratch, tr, Tn, offset);
     scratch.expand(ggml_cpy(scratch, bias, tr.g_bias));
     if (tr.g_offset) { const float f = (float) offset; ggml_backend_tensor_set(tr.g_offset, &f, 0, 4); }
     std::vector<int32_t> idx((size_t) Tn);
     for (int i = 0; i < Tn; i++) idx[(size_t) i] = (offset + i) % tr.capacity;
     ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
+}
+// the same at the stack's own stream position, which it advances
+void transformer_graph_step(Builder & scratch, Transformer & tr, int Tn) {
+    transformer_graph_step_at(scratch, tr, Tn, tr.offset);
+    tr.offset += Tn;
 }
 
 // moshi_streaming_transformer, non-graph overload with offsets baked at build time (transformer.h:1182-1215);
@@ -765,6 +768,7 @@ T rvq_encode(Builder & g, Rvq & rvq, T x, T * latent = nullptr) {
 // ---------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------
+enum class ModelKind { single, lockstep, slots };   // one stream (moshi_hot_create), or B > 1 columns at a shared / an own stream position
 struct moshi_hot_model {
     moshi_hot_config cfg;
     ggml_backend_t be;
@@ -820,11 +824,12 @@ struct moshi_hot_model {
     bool tp_frame = false; T tp_in = nullptr; Builder * g_tp_pre = nullptr, * g_tp_import = nullptr, * g_tp_post = nullptr; int64_t tp_frames = 0;
     // delay ring (lm.h:715-743)
     int offset = 0; std::vector<std::vector<int>> cache; std::vector<int> initial; int max_delay = 0;
-    // lockstep streams (moshi_hot_create_streams): B > 1 = the batch dimension of every LM activation and KV ring; one delay ring per stream
-    int n_streams = 1; std::vector<std::vector<std::vector<int>>> s_cache;
-    // stream slots (moshi_hot_create_slots): one stream position per column. s_frames = frames stepped since the slot was opened (its delay ring's
-    // offset), s_pos = its stream position (mask row, RoPE phase, ring slot; moshi_hot_slot_set_fill moves it alone). A closed slot keeps both.
-    bool slots = false; std::vector<char> s_open; std::vector<int64_t> s_frames, s_pos;
+    // B > 1 (moshi_hot_create_streams / moshi_hot_create_slots): B = the batch dimension of every LM activation and KV ring, one conversation per
+    // column. A column holds its delay ring, the frames stepped since it opened (the ring's offset) and its stream position (mask row, RoPE phase,
+    // ring slot; moshi_hot_set_context_fill / moshi_hot_slot_set_fill move it alone). Lockstep: every column open from creation, all at one position
+    // and advanced together. Slots: each column opened, closed and positioned on its own; a closed column keeps its frame count and position.
+    struct Column { std::vector<std::vector<int>> cache; int64_t frames = 0, pos = 0; bool open = false; };
+    int n_streams = 1; ModelKind kind = ModelKind::single; std::vector<Column> cols;
 
     // Mimi
     Rvq rvq_first, rvq_rest;
@@ -989,7 +994,7 @@ void build_temporal_graph(moshi_hot_model * m) {
     m->g_temporal = new Builder(m->be, 256);
     Builder & g = *m->g_temporal;
     T input = build_input_embedding(m, g);
-    T x = m->slots ? transformer_graph_build_slots(g, m->temporal, input) : transformer_graph_build(g, m->temporal, input);
+    T x = m->kind == ModelKind::slots ? transformer_graph_build_slots(g, m->temporal, input) : transformer_graph_build(g, m->temporal, input);
     m->g_stack_out = x;
     x = apply_norm(g, m->out_norm, x);
     m->g_transformer_out = x;
@@ -1166,50 +1171,50 @@ extern "C" void moshi_hot_config_personaplex(struct moshi_hot_config * c) {
     c->personaplex = 1;
 }
 
-static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams = 1);
+static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams = 1,
+                                        ModelKind kind = ModelKind::single);
 extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed) { return create_model(backend, cfg, seed, nullptr); }
-// lockstep streams (moshi_hot.h): the moshika-shaped LM only
-extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams) {
-    if (!cfg || n_streams < 1 || n_streams > 16) return nullptr;
-    if (n_streams == 1) return create_model(backend, cfg, seed, nullptr);
+// a B > 1 model of either kind (moshi_hot.h): the moshika-shaped LM only
+static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int B, ModelKind kind) {
+    if (!cfg || B < 2 || B > 16) return nullptr;
     const moshi_hot_config & c = *cfg;
     const bool ok = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && !c.extra_heads && !c.demux_second_stream &&
                     !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len && c.tp_world == 0 &&
                     c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream && c.dep_q > 0 && c.n_q > c.dep_q;
     if (!ok) return nullptr;
-    return create_model(backend, cfg, seed, nullptr, n_streams);
+    return create_model(backend, cfg, seed, nullptr, B, kind);
+}
+extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams) {
+    if (cfg && n_streams == 1) return create_model(backend, cfg, seed, nullptr);
+    return create_columns(backend, cfg, seed, n_streams, ModelKind::lockstep);
 }
 extern "C" int moshi_hot_n_streams(moshi_hot_model_t * m) { return m->n_streams; }
-// stream slots (moshi_hot.h): a lockstep-streams model whose columns each keep a position of their own; every slot starts closed
 extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
-    if (n_slots < 2 || n_slots > 16) return nullptr;
-    moshi_hot_model_t * m = moshi_hot_create_streams(backend, cfg, seed, n_slots);
-    if (!m) return nullptr;
-    m->slots = true;   // (before the first step: build_temporal_graph reads it)
-    m->s_open.assign((size_t) n_slots, 0);
-    m->s_frames.assign((size_t) n_slots, 0);
-    m->s_pos.assign((size_t) n_slots, 0);
-    return m;
+    return create_columns(backend, cfg, seed, n_slots, ModelKind::slots);
+}
+// slot b of a slots model, or NULL (a bad index or a model of another kind)
+static moshi_hot_model::Column * slot(moshi_hot_model_t * m, int b) {
+    return m->kind == ModelKind::slots && b >= 0 && b < m->n_streams ? &m->cols[(size_t) b] : nullptr;
 }
 extern "C" int moshi_hot_slot_open(moshi_hot_model_t * m, int b) {
-    if (!m->slots || b < 0 || b >= m->n_streams) return -1;
-    m->s_open[(size_t) b] = 1;
-    m->s_frames[(size_t) b] = m->s_pos[(size_t) b] = 0;
-    m->s_cache[(size_t) b] = m->cache;   // a fresh stream's delay ring (create_model): -2 everywhere
+    moshi_hot_model::Column * s = slot(m, b);
+    if (!s) return -1;
+    *s = { m->cache, 0, 0, true };   // a fresh stream's delay ring (create_model's: -2 everywhere) at stream position 0
     return 0;
 }
 extern "C" int moshi_hot_slot_close(moshi_hot_model_t * m, int b) {
-    if (!m->slots || b < 0 || b >= m->n_streams) return -1;
-    m->s_open[(size_t) b] = 0;
+    moshi_hot_model::Column * s = slot(m, b);
+    if (!s) return -1;
+    s->open = false;
     return 0;
 }
 extern "C" int64_t moshi_hot_slot_position(moshi_hot_model_t * m, int b) {
-    if (!m->slots || b < 0 || b >= m->n_streams || !m->s_open[(size_t) b]) return -1;
-    return m->s_pos[(size_t) b];
+    moshi_hot_model::Column * s = slot(m, b);
+    return s && s->open ? s->pos : -1;
 }
 extern "C" void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offset) {
-    if (!m->slots || b < 0 || b >= m->n_streams || offset < 0) return;
-    m->s_pos[(size_t) b] = offset;
+    moshi_hot_model::Column * s = slot(m, b);
+    if (s && offset >= 0) s->pos = offset;
 }
 // the model's weights come from a GGUF file written by moshi_hot_save_gguf (the reference's `*.gguf` checkpoints: WeightLoader::from_gguf + load_gguf)
 extern "C" moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, const struct moshi_hot_config * cfg, const char * path) { return create_model(backend, cfg, 0, path); }
@@ -1226,11 +1231,13 @@ extern "C" int moshi_hot_tensor_file_name(const char * checkpoint_name, char * o
     if (out && n > 0) { strncpy(out, f.c_str(), (size_t) n - 1); out[n - 1] = 0; }
     return (int) f.size();
 }
-static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams) {
+static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams,
+                                        ModelKind kind) {
     moshi_hot_model * m = new moshi_hot_model;
     m->cfg = *cfg;
     m->be = backend;
     m->n_streams = n_streams;
+    m->kind = kind;   // (build_temporal_graph reads it)
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
     if (gguf_path) m->W->gguf_path = gguf_path;
@@ -1350,7 +1357,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         m->cache.assign((size_t) (m->max_delay + 2 + (c.personaplex ? 1 : 0)), std::vector<int>((size_t) ncb, -2));
         m->initial.assign((size_t) ncb, c.card);
         m->initial[0] = c.text_card;
-        if (m->n_streams > 1) m->s_cache.assign((size_t) m->n_streams, m->cache);
+        if (m->n_streams > 1) m->cols.assign((size_t) m->n_streams, { m->cache, 0, 0, kind == ModelKind::lockstep });
     }
     if (c.enable_mimi_decoder || c.enable_mimi_encoder) {
         W.part = c.enable_mimi_decoder ? 3 : 2;
@@ -2058,145 +2065,104 @@ extern "C" int moshi_hot_lm_step(moshi_hot_model_t * m, const int32_t * in_audio
     return moshi_hot_lm_step_n(m, in_audio, m->cfg.n_q - io_dep_q, text_token_out, out_audio, nullptr);
 }
 
-// moshi_lmgen_step (lm.h:778-979) of B lockstep streams: the host half runs per stream over its own delay ring, the Temporal and the Depth graph once
-// for all of them (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - moshi_hot_create_streams refuses those)
-extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
-    if (m->slots) return -1;   // (moshi_hot_lm_step_slots)
-    if (m->n_streams <= 1) return moshi_hot_lm_step(m, in_audio, text_token_out, out_audio);
-    const moshi_hot_config & c = m->cfg;
-    const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
-    if (!m->g_temporal) build_temporal_graph(m);
-    if (!m->g_depth) build_depth_graph_streams(m);
-    const int pos = m->offset % CT;
-    for (int b = 0; b < B; b++) {   // other speaker's codes enter each stream's delay ring (lm.h:819-824)
-        auto & cache = m->s_cache[(size_t) b];
-        for (int i = 0; i < needed; i++) cache[(size_t) ((m->offset + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
+namespace {
+// the B token inputs of one embedding (moshi_lmmodel_text_token_embed_step, lm.h:586-607): -1 -> scale 0, negative ids -> row 0
+void set_token_inputs(T idx, T scale, const std::vector<int32_t> & ids) {
+    std::vector<int32_t> rows(ids.size());
+    std::vector<float> sc(ids.size());
+    for (size_t b = 0; b < ids.size(); b++) {
+        sc[b] = ids[b] == -1 ? 0.f : 1.f;
+        rows[b] = ids[b] < 0 ? 0 : ids[b];
     }
-    std::vector<int32_t> idx((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
-    std::vector<float> sc((size_t) B);
-    {
-    PhaseTimer pt(m, 1);
-    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed_step (lm.h:586-607) per stream: -1 -> scale 0, negative ids -> row 0
-        for (int b = 0; b < B; b++) {
-            int32_t id = m->offset <= c.delays[i] ? m->initial[(size_t) i] : m->s_cache[(size_t) b][(size_t) pos][(size_t) i];
-            sc[(size_t) b] = id == -1 ? 0.f : 1.f;
-            idx[(size_t) b] = id < 0 ? 0 : id;
-        }
-        ggml_backend_tensor_set(m->emb_idx[(size_t) i], idx.data(), 0, (size_t) B * 4);
-        ggml_backend_tensor_set(m->emb_scale[(size_t) i], sc.data(), 0, (size_t) B * 4);
-    }
-    transformer_graph_step(*m->scratch, m->temporal, 1);
-    m->scratch->compute_scratch();
-    m->g_temporal->compute();
-    ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
-    }
-    {
-    PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
-    for (int b = 0; b < B; b++) {
-        const int32_t id = text[(size_t) b];
-        sc[(size_t) b] = id == -1 ? 0.f : 1.f;
-        idx[(size_t) b] = id < 0 ? 0 : id;
-    }
-    ggml_backend_tensor_set(m->dep_text_idx, idx.data(), 0, (size_t) B * 4);
-    ggml_backend_tensor_set(m->dep_text_scale, sc.data(), 0, (size_t) B * 4);
-    m->g_depth->compute();
-    ggml_backend_tensor_get(m->dep_tokens, toks.data(), 0, toks.size() * 4);   // [dep_q][B]
-    }
-    // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per stream
-    m->offset++;
-    int ok = 1;
-    const int wpos = m->offset % CT;
-    for (int b = 0; b < B; b++) {
-        auto & cache = m->s_cache[(size_t) b];
-        cache[(size_t) wpos][0] = text[(size_t) b];
-        for (int q = 0; q < dep_q; q++) cache[(size_t) wpos][(size_t) (q + 1)] = toks[(size_t) q * B + b];
-        if (m->offset <= m->max_delay) { ok = 0; continue; }
-        text_token_out[b] = cache[(size_t) ((m->offset - m->max_delay + c.delays[0]) % CT)][0];
-        for (int i = 1; i < dep_q_1; i++) {
-            const int32_t v = cache[(size_t) ((m->offset - m->max_delay + c.delays[i]) % CT)][(size_t) i];
-            out_audio[(size_t) b * dep_q + (i - 1)] = v;
-            if (v == -1) ok = 0;
-        }
-    }
-    return ok;
+    ggml_backend_tensor_set(idx, rows.data(), 0, rows.size() * 4);
+    ggml_backend_tensor_set(scale, sc.data(), 0, sc.size() * 4);
 }
-
-// moshi_lmgen_step of B stream slots: moshi_hot_lm_step_streams with a position per slot. Each open slot's host half runs over its own delay ring at
-// its own offset (s_frames); a closed slot is fed the initial tokens at its frozen position and its results are dropped.
-extern "C" int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
-    if (!m->slots) return -1;
+// moshi_lmgen_step (lm.h:778-979) of a B > 1 model: the host half runs per column over the column's own delay ring, the Temporal and the Depth graph
+// once for all columns (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - create_columns refuses those). An open
+// column takes its codes from in_audio and advances one frame; a closed one is fed the initial tokens at its frozen position and is left as it is.
+// status[b]: -1 closed, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
+void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     const moshi_hot_config & c = m->cfg;
     const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
     int n_open = 0;
     for (int b = 0; b < B; b++) {
-        status[b] = m->s_open[(size_t) b] ? 0 : -1;
-        text_token_out[b] = -1;
-        for (int q = 0; q < dep_q; q++) out_audio[(size_t) b * dep_q + q] = -1;
-        n_open += m->s_open[(size_t) b];
+        status[b] = m->cols[(size_t) b].open ? 0 : -1;
+        n_open += m->cols[(size_t) b].open;
     }
-    if (!n_open) return 0;
+    if (!n_open) return;
     if (!m->g_temporal) build_temporal_graph(m);
     if (!m->g_depth) build_depth_graph_streams(m);
-    for (int b = 0; b < B; b++) {   // other speaker's codes enter each open slot's delay ring (lm.h:819-824)
-        if (!m->s_open[(size_t) b]) continue;
-        auto & cache = m->s_cache[(size_t) b];
-        const int64_t off = m->s_frames[(size_t) b];
-        for (int i = 0; i < needed; i++) cache[(size_t) ((off + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
+    for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring (lm.h:819-824)
+        auto & col = m->cols[(size_t) b];
+        if (!col.open) continue;
+        for (int i = 0; i < needed; i++) col.cache[(size_t) ((col.frames + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
     }
-    std::vector<int32_t> idx((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
-    std::vector<float> sc((size_t) B);
+    std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
     {
     PhaseTimer pt(m, 1);
-    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed_step (lm.h:586-607) per slot: -1 -> scale 0, negative ids -> row 0
+    for (int i = 0; i < ncb; i++) {
         for (int b = 0; b < B; b++) {
-            const int64_t off = m->s_frames[(size_t) b];
-            const int32_t id = !m->s_open[(size_t) b] || off <= c.delays[i] ? m->initial[(size_t) i] : m->s_cache[(size_t) b][(size_t) (off % CT)][(size_t) i];
-            sc[(size_t) b] = id == -1 ? 0.f : 1.f;
-            idx[(size_t) b] = id < 0 ? 0 : id;
+            const auto & col = m->cols[(size_t) b];
+            ids[(size_t) b] = !col.open || col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) (col.frames % CT)][(size_t) i];
         }
-        ggml_backend_tensor_set(m->emb_idx[(size_t) i], idx.data(), 0, (size_t) B * 4);
-        ggml_backend_tensor_set(m->emb_scale[(size_t) i], sc.data(), 0, (size_t) B * 4);
+        set_token_inputs(m->emb_idx[(size_t) i], m->emb_scale[(size_t) i], ids);
     }
-    transformer_graph_step_slots(*m->scratch, m->temporal, m->s_pos);
+    if (m->kind == ModelKind::lockstep) transformer_graph_step_at(*m->scratch, m->temporal, 1, (int) m->cols[0].pos);   // one shared position
+    else {
+        std::vector<int64_t> pos((size_t) B);
+        for (int b = 0; b < B; b++) pos[(size_t) b] = m->cols[(size_t) b].pos;
+        transformer_graph_step_slots(*m->scratch, m->temporal, pos);
+    }
     m->scratch->compute_scratch();
     m->g_temporal->compute();
     ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
     }
     {
     PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
-    for (int b = 0; b < B; b++) {
-        const int32_t id = text[(size_t) b];
-        sc[(size_t) b] = id == -1 ? 0.f : 1.f;
-        idx[(size_t) b] = id < 0 ? 0 : id;
-    }
-    ggml_backend_tensor_set(m->dep_text_idx, idx.data(), 0, (size_t) B * 4);
-    ggml_backend_tensor_set(m->dep_text_scale, sc.data(), 0, (size_t) B * 4);
+    set_token_inputs(m->dep_text_idx, m->dep_text_scale, text);
     m->g_depth->compute();
     ggml_backend_tensor_get(m->dep_tokens, toks.data(), 0, toks.size() * 4);   // [dep_q][B]
     }
-    // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per open slot
-    int n_valid = 0;
-    std::vector<int32_t> aud((size_t) dep_q);
+    // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per open column
     for (int b = 0; b < B; b++) {
-        if (!m->s_open[(size_t) b]) continue;
-        const int64_t off = ++m->s_frames[(size_t) b];
-        m->s_pos[(size_t) b]++;
-        auto & cache = m->s_cache[(size_t) b];
-        const size_t wpos = (size_t) (off % CT);
-        cache[wpos][0] = text[(size_t) b];
-        for (int q = 0; q < dep_q; q++) cache[wpos][(size_t) (q + 1)] = toks[(size_t) q * B + b];
+        auto & col = m->cols[(size_t) b];
+        if (!col.open) continue;
+        const int64_t off = ++col.frames;
+        col.pos++;
+        auto & row = col.cache[(size_t) (off % CT)];
+        row[0] = text[(size_t) b];
+        for (int q = 0; q < dep_q; q++) row[(size_t) (q + 1)] = toks[(size_t) q * B + b];
         if (off <= m->max_delay) continue;
-        const int32_t t = cache[(size_t) ((off - m->max_delay + c.delays[0]) % CT)][0];
-        bool ok = true;
-        for (int i = 1; i < dep_q_1; i++) {
-            aud[(size_t) (i - 1)] = cache[(size_t) ((off - m->max_delay + c.delays[i]) % CT)][(size_t) i];
-            if (aud[(size_t) (i - 1)] == -1) ok = false;
-        }
-        if (!ok) continue;
         status[b] = 1;
-        text_token_out[b] = t;
-        for (int q = 0; q < dep_q; q++) out_audio[(size_t) b * dep_q + q] = aud[(size_t) q];
-        n_valid++;
+        text_token_out[b] = col.cache[(size_t) ((off - m->max_delay + c.delays[0]) % CT)][0];
+        for (int i = 1; i < dep_q_1; i++) {
+            const int32_t v = col.cache[(size_t) ((off - m->max_delay + c.delays[i]) % CT)][(size_t) i];
+            out_audio[(size_t) b * dep_q + (i - 1)] = v;
+            if (v == -1) status[b] = 0;
+        }
+    }
+}
+}  // namespace
+
+// B lockstep streams: 1 when every stream's outputs are valid, else 0 (the outputs are written once the delay rings are full, -1 tokens included)
+extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
+    if (m->kind == ModelKind::slots) return -1;   // (moshi_hot_lm_step_slots)
+    if (m->kind == ModelKind::single) return moshi_hot_lm_step(m, in_audio, text_token_out, out_audio);
+    std::vector<int32_t> status((size_t) m->n_streams);
+    lm_step_columns(m, in_audio, text_token_out, out_audio, status.data());
+    for (int32_t s : status) if (s != 1) return 0;
+    return 1;
+}
+
+// B stream slots: the number of slots with status 1; the outputs of every other slot are -1
+extern "C" int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
+    if (m->kind != ModelKind::slots) return -1;
+    lm_step_columns(m, in_audio, text_token_out, out_audio, status);
+    int n_valid = 0;
+    for (int b = 0; b < m->n_streams; b++) {
+        if (status[b] == 1) { n_valid++; continue; }
+        text_token_out[b] = -1;
+        for (int q = 0; q < m->cfg.dep_q; q++) out_audio[(size_t) b * m->cfg.dep_q + q] = -1;
     }
     return n_valid;
 }
@@ -2407,7 +2373,7 @@ extern "C" int moshi_hot_sts_pipeline_end(moshi_hot_model_t * m, int32_t * text_
 }
 
 extern "C" float moshi_hot_sts_pipeline_vad(moshi_hot_model_t * m) { return m->pipe_vad; }
-extern "C" int64_t moshi_hot_offset(moshi_hot_model_t * m) { return m->offset; }
+extern "C" int64_t moshi_hot_offset(moshi_hot_model_t * m) { return m->kind == ModelKind::lockstep ? m->cols[0].frames : m->offset; }   // (slots: 0)
 extern "C" void moshi_hot_last_raw_tokens(moshi_hot_model_t * m, int32_t * text_token, int32_t * audio_tokens) {
     *text_token = m->last_text;
     for (size_t i = 0; i < m->last_audio.size(); i++) audio_tokens[i] = m->last_audio[i];
@@ -2443,7 +2409,8 @@ extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, 
     m->tok_state_for = -1;   // the device-side token state still holds the model's own samples
 }
 extern "C" void moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset) {
-    if (m->slots) return;   // (a position per slot: moshi_hot_slot_set_fill)
+    if (m->kind == ModelKind::slots) return;   // (a position per slot: moshi_hot_slot_set_fill)
+    if (m->kind == ModelKind::lockstep) { for (auto & col : m->cols) col.pos = offset; return; }   // (not the frame counts)
     unstage_temporal(m);
     m->temporal.offset = (int) offset;
     if (m->tp_x) m->temporal_tp.offset = (int) offset;   // tensor-parallel frame mode steps its own stack (head-sliced rings): same stream position

@@ -1,5 +1,4 @@
 """Helpers for stream-slot models (moshi_hot_create_slots / moshi_hot_lm_step_slots)."""
-import ctypes as C
 
 import numpy as np
 
@@ -10,14 +9,10 @@ L = hu.L
 lm_only = su.lm_only
 
 
-class Slots:
+class Slots(su.Streams):
     """B stream slots over one set of weights on a backend ("oracle" or "hip"); every slot starts closed."""
 
-    def __init__(self, kind, cfg, n_slots, seed=0):
-        self.cfg, self.B = cfg, n_slots
-        self.be = hu.make_backend(kind)
-        self.m = L.moshi_hot_create_slots(self.be, C.byref(cfg), seed, n_slots)
-        assert self.m, "moshi_hot_create_slots refused the configuration"
+    create = "moshi_hot_create_slots"
 
     def open(self, b):
         return L.moshi_hot_slot_open(self.m, b)
@@ -40,20 +35,6 @@ class Slots:
         st = np.full(B, -7, np.int32)
         r = L.moshi_hot_lm_step_slots(self.m, ia.ctypes.data, txt.ctypes.data, aud.ctypes.data, st.ctypes.data)
         return r, st.tolist(), txt.tolist(), aud.reshape(B, dq).tolist()
-
-    def read(self, what, n_per_slot):
-        out = np.zeros(self.B * n_per_slot, np.float32)
-        assert L.moshi_hot_read_last(self.m, what.encode(), out.ctypes.data, out.size) == 0
-        return out.reshape(self.B, n_per_slot)
-
-    def stats(self):
-        s = hu.pkg.Stats()
-        L.ggml_backend_mi355x_get_stats(self.be, C.byref(s))
-        return s
-
-    def free(self):
-        L.moshi_hot_free(self.m)
-        L.ggml_backend_free(self.be)
 
 
 def run_slots(slots, codes, events=None, logits=False, dep_logits=False, before_step=None):

@@ -16,11 +16,13 @@ def lm_only(cfg):
 class Streams:
     """B lockstep streams over one set of weights on a backend ("oracle" or "hip")."""
 
+    create = "moshi_hot_create_streams"
+
     def __init__(self, kind, cfg, n_streams, seed=0):
         self.cfg, self.B = cfg, n_streams
         self.be = hu.make_backend(kind)
-        self.m = L.moshi_hot_create_streams(self.be, C.byref(cfg), seed, n_streams)
-        assert self.m, "moshi_hot_create_streams refused the configuration"
+        self.m = getattr(L, self.create)(self.be, C.byref(cfg), seed, n_streams)
+        assert self.m, f"{self.create} refused the configuration"
 
     def step(self, codes):
         """codes: B lists of (n_q - dep_q) codes -> (ok, [B text tokens], [B lists of dep_q audio tokens])"""
