@@ -137,6 +137,38 @@ GGML_API void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offs
 // number of slots with status 1, or -1 on a model that is not a slots model. With no slot open it does no device work and returns 0.
 GGML_API int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio, int32_t * status);
 
+// ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
+// In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute
+// (src/context.h:456-480, moshi/utils/sampling.h:4-64). By default that noise comes from libc rand() in one sweep over the whole [k, B] tensor, so a
+// conversation's draws depend on B, on its column and on the frame it was admitted in. A SEEDED column draws from a counter-based source instead:
+//
+//   noise(seed, frame, site, rank) = -logf(u) / lambd                                  (lambd = 1 at every sampler site)
+//   u = (float) (2 * (z >> 41) + 1) * 2^-24                                             (an odd multiple of 2^-24: 0 < u < 1, the noise is finite and > 0)
+//   z = mix(mix(seed + 0x9E3779B97F4A7C15) ^ (frame * 0xD1342543DE82EF95 + (site << 32 | rank)))                       (64-bit wrap-around arithmetic)
+//   mix(x): x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  return x ^ (x >> 31)   (SplitMix64's output function)
+//
+// frame = the conversation's own frame count (frames stepped since the slot was opened; frames stepped by a lockstep or single-stream model), site = 0
+// for the text head and 1 + k for Depth step k, rank = the index into the top-k row. Nothing else enters: a conversation with a given seed gets the same
+// tokens in any column of any B beside any neighbours, and the tokens of a fresh single-stream model configured and seeded alike.
+struct moshi_hot_sampling { uint64_t seed; float temp, temp_text; int32_t top_k, top_k_text; };
+// Sets column b's sampling from its next frame on. Returns 0, or -1 (nothing changes) on a greedy model, for a bad column or for values out of range.
+//  * B > 1 (slots and lockstep models): temp > 0, temp_text > 0, 1 <= top_k <= config.top_k, 1 <= top_k_text <= config.top_k_text - the configuration's
+//    top-k values are the compiled maximum (the graph keeps that many rows; a column with fewer gets infinite noise in the ranks past its own, whose
+//    quotient is 0). top_k = 1 is the nearest thing to a greedy column. The setting belongs to the column, not the conversation: it survives
+//    moshi_hot_slot_close / _open, and a newly opened slot restarts at frame 0 of its seed, so the same seed replays the same conversation.
+//  * single-stream (b = 0): only the seed is free - temp, temp_text, top_k and top_k_text must equal the configuration's (its graphs keep them baked in).
+//    Supported on the moshika-shaped LM (with or without the codec) stepped by moshi_hot_lm_step, moshi_hot_lm_step_n, moshi_hot_sts_frame and the
+//    moshi_hot_sts_pipeline_* calls with chain_depth = 0. Returns -1 with chain_depth > 0 (moshi_hot_lm_step_run_ahead included), personaplex, extra
+//    heads, demux, low-rank embeddings, delay_steps, cross-attention, condition_sum, a weight schedule, a Depth shard, a Depth hook or a tensor-parallel
+//    stack. The text sample moshi_hot_lm_step_embedding computes and discards still draws from rand().
+// A column that was never set draws from rand() exactly as before: the sweep over the whole noise tensor is always drawn in full, in the same order, and
+// the rows of seeded columns are overwritten afterwards. A seeded column that is closed gets constant noise; its results are dropped.
+GGML_API int moshi_hot_set_sampling(moshi_hot_model_t * m, int b, const struct moshi_hot_sampling * s);
+// column b's current values (the configuration's until set; seed 0) and whether it has been seeded; -1 for a bad column
+GGML_API int moshi_hot_get_sampling(moshi_hot_model_t * m, int b, struct moshi_hot_sampling * s, int * seeded);
+// noise(seed, frame, site, rank) for rank = 0 .. n - 1 with lambd = 1 (tests)
+GGML_API void moshi_hot_sampling_noise(uint64_t seed, int64_t frame, int site, int n, float * out);
+
 // mimi_encode_send + mimi_encode_receive (src/moshi.cpp:215-234): 1920 samples -> mimi_n_q codes
 GGML_API void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, int32_t * codes);
 // mimi_decode_send + mimi_decode_receive (src/moshi.cpp:273-292): mimi_n_q codes -> 1920 samples

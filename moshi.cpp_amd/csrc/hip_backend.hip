@@ -1781,6 +1781,84 @@ static bool match_sampler(const analysis & an, int pos, step_group & grp) {
     return true;
 }
 
+// H2. the same sampler over the B columns of a B-column LM step (sample_tokens_streams of the frame driver), matched at its last computing node:
+//    out [1, 1, B] = get_rows(cont(permute(reshape(idx))), reshape(argmax(div(reshape(get_rows(cont(permute(reshape(p))), idx)), noise [k, B]))))
+//    with idx = cont(view(argsort_desc(p), k)) [k, B], p = soft_max(sc) [n, B], sc = scale(logits, 1 / temp) or mul(logits, inv_temp [1, B])
+// inv_temp must be a contiguous F32 graph INPUT (no node of the graph is it, views it or copies into it). A trailing cpy of the B tokens into an I32
+// vector (the chained Depth graph's token rows) becomes out2. One workgroup per column and none waits for another: no residency planning.
+static bool match_sampler_streams(const analysis & an, int pos, sample_streams_args & a, std::vector<int> & members) {
+    const ggml_tensor * out = an.g->nodes[pos];
+    if (out->op != GGML_OP_GET_ROWS || out->type != GGML_TYPE_I32 || out->ne[0] != 1 || out->ne[1] != 1 || out->ne[3] != 1 || !out->data) return false;
+    const int64_t B = out->ne[2];
+    if (B < 2 || B > SAMPLE_MAX_B) return false;
+    auto is = [&](const ggml_tensor * t, enum ggml_op op, int uses) { return t && t->op == op && pos_of(an, t) >= 0 && uses_of(an, t) == uses; };
+    members = { pos };
+    // a chain of single-use reshapes / views / permutes below t, collected as members; returns the first other node
+    auto through = [&](const ggml_tensor * t, bool permute) {
+        while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || (permute && t->op == GGML_OP_PERMUTE)) && pos_of(an, t) >= 0 && uses_of(an, t) == 1) {
+            members.push_back(pos_of(an, t)); t = t->src[0];
+        }
+        return t;
+    };
+    // the index side: cont(permute(reshape(idx)))
+    const ggml_tensor * cont2 = out->src[0];
+    if (!is(cont2, GGML_OP_CONT, 1)) return false;
+    members.push_back(pos_of(an, cont2));
+    const ggml_tensor * idx = through(cont2->src[0], true);
+    if (!is(idx, GGML_OP_CONT, 2) || idx->type != GGML_TYPE_I32 || idx->ne[1] != B || ggml_nelements(idx) != idx->ne[0] * B) return false;
+    const int64_t k = idx->ne[0];
+    const ggml_tensor * vw = idx->src[0];
+    if (!is(vw, GGML_OP_VIEW, 1) || !is(vw->src[0], GGML_OP_ARGSORT, 1) || vw->data != vw->src[0]->data || vw->ne[0] != k || vw->ne[1] != B) return false;
+    const ggml_tensor * srt = vw->src[0], * pr = srt->src[0];
+    if (srt->op_params[0] != GGML_SORT_ORDER_DESC || !is(pr, GGML_OP_SOFT_MAX, 2) || pr->src[1] != NULL) return false;
+    if (ggml_get_op_params_f32(pr, 0) != 1.0f || ggml_get_op_params_f32(pr, 1) != 0.0f) return false;
+    const int64_t n = pr->ne[0];
+    if (pr->ne[1] != B || ggml_nelements(pr) != n * B || vw->nb[1] != (size_t) n * 4) return false;
+    if (n > SAMPLE_MAX_N || k > SAMPLE_MAX_K || k < 1 || k > n) return false;
+    const ggml_tensor * sc = pr->src[0], * inv = nullptr;
+    if (is(sc, GGML_OP_SCALE, 1)) { if (ggml_get_op_params_f32(sc, 1) != 0.0f) return false; }
+    else if (is(sc, GGML_OP_MUL, 1)) {
+        inv = sc->src[1];
+        if (!inv || inv->type != GGML_TYPE_F32 || inv->ne[0] != 1 || inv->ne[1] != B || ggml_nelements(inv) != B || !ggml_is_contiguous(inv) || !inv->data) return false;
+        if (pos_of(an, inv) >= 0 || inv->view_src) return false;
+        for (int j = 0; j < an.g->n_nodes; j++) if (an.g->nodes[j]->view_src == inv) return false;   // (a view of it: something may write through it)
+    } else return false;
+    const ggml_tensor * logits = sc->src[0];
+    if (logits->type != GGML_TYPE_F32 || !ggml_is_contiguous(logits) || ggml_nelements(logits) != n * B || logits->ne[0] != n || !logits->data) return false;
+    members.insert(members.end(), { pos_of(an, idx), pos_of(an, vw), pos_of(an, srt), pos_of(an, pr), pos_of(an, sc) });
+    // the argmax side: reshape(argmax(div(reshape(get_rows(cont(permute(reshape(p))), idx)), noise)))
+    const ggml_tensor * am = through(out->src[1], false);
+    if (!is(am, GGML_OP_ARGMAX, 1) || ggml_nelements(am) != B) return false;
+    const ggml_tensor * q = am->src[0];
+    if (!is(q, GGML_OP_DIV, 1) || q->view_src || q->ne[0] != k || q->ne[1] != B || ggml_nelements(q) != k * B) return false;
+    const ggml_tensor * noise = q->src[1];
+    if (noise->type != GGML_TYPE_F32 || noise->ne[0] != k || ggml_nelements(noise) != k * B || !ggml_is_contiguous(noise) || !noise->data || pos_of(an, noise) >= 0) return false;
+    members.push_back(pos_of(an, am)); members.push_back(pos_of(an, q));
+    const ggml_tensor * picked = through(q->src[0], false);
+    if (!is(picked, GGML_OP_GET_ROWS, 1) || picked->src[1] != idx || picked->ne[0] != 1) return false;
+    members.push_back(pos_of(an, picked));
+    const ggml_tensor * c1 = picked->src[0];
+    if (!is(c1, GGML_OP_CONT, 1)) return false;
+    members.push_back(pos_of(an, c1));
+    if (through(c1->src[0], true) != pr) return false;
+    for (int m : members) if (m < 0) return false;
+    a.logits = (const float *) logits->data; a.n = (int) n; a.k = (int) k; a.B = (int) B;
+    a.scale = inv ? 0.f : ggml_get_op_params_f32(sc, 0); a.inv_temp = inv ? (const float *) inv->data : nullptr;
+    a.noise = (const float *) noise->data; a.out = (int32_t *) out->data; a.out2 = nullptr;
+    // a copy of the B tokens into an I32 vector (the chained Depth graph's token rows): written by the same launch
+    for (int j = pos + 1; j < an.g->n_nodes; j++) {
+        const ggml_tensor * cp = an.g->nodes[j];
+        if (cp->op != GGML_OP_CPY || cp->type != GGML_TYPE_I32 || ggml_nelements(cp) != B || !ggml_is_contiguous(cp) || !cp->data || an.skip[(size_t) j]) continue;
+        const ggml_tensor * src = cp->src[0];
+        std::vector<int> between;
+        while (src != out && src->op == GGML_OP_RESHAPE && pos_of(an, src) >= 0 && uses_of(an, src) == 1) { between.push_back(pos_of(an, src)); src = src->src[0]; }
+        if (src != out || !ggml_is_contiguous(cp->src[0])) continue;
+        a.out2 = (int32_t *) cp->data; members.push_back(j); members.insert(members.end(), between.begin(), between.end());
+        break;
+    }
+    return true;
+}
+
 // ---- plan construction --------------------------------------------------------------------------------------
 // Kernels whose workgroups wait for each other inside a launch (persistent chains, the fused attention + out_proj launch) need their WHOLE grid resident.
 // Two such launches from two streams of one device could interleave their dispatch and each keep the other's workgroups off the compute units, so only ONE
@@ -1876,6 +1954,19 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             p->sampler_copies.emplace_back(new sample_args(grp.smp));
             for (auto & f : grp.steps) at_pos[grp.emit_pos].push_back(pstep::special_step(f, 3, nullptr, nullptr, p->sampler_copies.back().get()));
             p->n_fused += (int) grp.members.size();
+        }
+        // the B-column form of the same samplers (B-column LM steps)
+        for (int i = g->n_nodes - 1; i >= 0 && !no_sampler; i--) {
+            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_GET_ROWS || g->nodes[i]->type != GGML_TYPE_I32) continue;
+            sample_streams_args sa;
+            std::vector<int> members;
+            if (!match_sampler_streams(an, i, sa, members)) continue;
+            bool clash = false;
+            for (int m : members) if (an.skip[(size_t) m]) clash = true;
+            if (clash) continue;
+            for (int m : members) an.skip[(size_t) m] = 1;
+            at_pos[i].push_back([=](hipStream_t s) { k_sample_topk_streams(s, sa); });
+            p->n_fused += (int) members.size();
         }
         // cross-attention over cached conditions (tts)
         static const bool no_xattn = getenv("MI355X_NO_CROSS_ATTN_FUSION") != nullptr;

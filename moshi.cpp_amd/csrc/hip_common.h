@@ -245,6 +245,11 @@ struct lowrank_embed_args { const char * table; int64_t row_bytes, n_rows; int t
 void k_lowrank_embed(hipStream_t s, const lowrank_embed_args & a);
 struct sample_args { const float * logits; int n; float scale; int k; const float * noise; int32_t * out; int32_t * out2; };   // out2: optional copy (the token vector slot)
 void k_sample_topk(hipStream_t s, const sample_args & a);
+// the same for the B columns of a B-column LM step, one workgroup per column: logits [n, B], noise [k, B], out / out2 = B tokens. inv_temp (may be NULL):
+// one scale per column (the graph's mul by a [1, B] input) instead of `scale`
+#define SAMPLE_MAX_B 16
+struct sample_streams_args { const float * logits; int n; float scale; const float * inv_temp; int k; const float * noise; int32_t * out; int32_t * out2; int B; };
+void k_sample_topk_streams(hipStream_t s, const sample_streams_args & a);
 #define VQ_LEVEL_WS_BYTES 4096
 void k_vq_level(hipStream_t s, const vq_level_args & a);
 // Consecutive levels of one RVQ stack (each level's residual is the previous level's output: core_vq.h:27-56 inside vq.h:97-114's loop) as ONE persistent

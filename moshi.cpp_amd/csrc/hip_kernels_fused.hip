@@ -2319,8 +2319,10 @@ __device__ unsigned long long g_smp_log[16];
 #endif
 // NPT: probabilities per thread (every loop over them is unrolled: the 2 048-logit audio heads get their own instantiation with 2 instead of 32)
 #define SMP_BIN_MAX 64   // the select stops as soon as the bin that holds the k-th largest value has at most this many members
+// The body of one column: the calling workgroup samples one token from a.logits[0 .. n) with a.noise[0 .. k) and a.scale. sample_topk_kernel runs it on
+// its only column, sample_topk_streams_kernel on column blockIdx.x (the way attn_streams_kernel reuses attn_decode_body).
 template <int SMP_THREADS, int SMP_NPT>
-__global__ void __launch_bounds__(SMP_THREADS) sample_topk_kernel(sample_args a) {
+__device__ __forceinline__ void sample_topk_body(const sample_args & a) {
     constexpr int NW = SMP_THREADS / 64;
     __shared__ float shf[NW];
     __shared__ double shd[NW];
@@ -2520,6 +2522,26 @@ __global__ void __launch_bounds__(SMP_THREADS) sample_topk_kernel(sample_args a)
         if (a.out2) *a.out2 = tok;
     }
     SMP_STAMP(5);
+}
+template <int SMP_THREADS, int SMP_NPT>
+__global__ void __launch_bounds__(SMP_THREADS) sample_topk_kernel(sample_args a) { sample_topk_body<SMP_THREADS, SMP_NPT>(a); }
+// B columns, one workgroup each (moshi_sample_token over the batch dimension of a B-column LM step): workgroup b takes logits row b, noise row b and
+// writes out[b] (and out2[b]). The scale is the shared float, or inv_temp[b] where the graph multiplies by a per-column [1, B] input: the same float
+// product x * s either way. Column by column the operations and their order are sample_topk_kernel's. No workgroup waits for another.
+template <int SMP_THREADS, int SMP_NPT>
+__global__ void __launch_bounds__(SMP_THREADS) sample_topk_streams_kernel(sample_streams_args s) {
+    const int b = blockIdx.x;
+    sample_args a;
+    a.logits = s.logits + (int64_t) b * s.n; a.n = s.n; a.k = s.k;
+    a.scale = s.inv_temp ? s.inv_temp[b] : s.scale;
+    a.noise = s.noise + (int64_t) b * s.k;
+    a.out = s.out + b; a.out2 = s.out2 ? s.out2 + b : nullptr;
+    sample_topk_body<SMP_THREADS, SMP_NPT>(a);
+}
+void k_sample_topk_streams(hipStream_t s, const sample_streams_args & a) {
+    GGML_ASSERT(a.n >= 1 && a.n <= SAMPLE_MAX_N && a.k >= 1 && a.k <= SAMPLE_MAX_K && a.k <= a.n && a.B >= 2 && a.B <= SAMPLE_MAX_B);
+    if (a.n <= 2 * 1024) sample_topk_streams_kernel<1024, 2><<<a.B, 1024, 0, s>>>(a);
+    else sample_topk_streams_kernel<1024, 32><<<a.B, 1024, 0, s>>>(a);
 }
 void k_sample_topk(hipStream_t s, const sample_args & a) {
     GGML_ASSERT(a.n >= 1 && a.n <= SAMPLE_MAX_N && a.k >= 1 && a.k <= SAMPLE_MAX_K && a.k <= a.n);

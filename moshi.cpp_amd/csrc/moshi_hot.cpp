@@ -42,6 +42,18 @@ uint64_t name_seed(uint64_t seed, const std::string & name) {
     return h;
 }
 
+// the counter-based noise source of moshi_hot_set_sampling (the formula is stated in moshi_hot.h): SplitMix64's output function over a key that
+// mixes the coordinates into the seed's hash; 0 < u < 1, so the noise is finite and > 0
+static inline uint64_t mix64(uint64_t z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; return z ^ (z >> 31); }
+static inline float sampling_noise(uint64_t seed, int64_t frame, int site, int rank, float lambd) {
+    const uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull);
+    const uint64_t z = mix64(h ^ ((uint64_t) frame * 0xD1342543DE82EF95ull + ((uint64_t) (uint32_t) site << 32 | (uint64_t) (uint32_t) rank)));
+    const float u = (float) (((z >> 41) << 1) + 1) * (1.0f / 16777216.0f);   // an odd multiple of 2^-24 (exact in float): 2^-24 <= u <= 1 - 2^-24
+    return -logf(u) / lambd;
+}
+// what upload_noise needs to know of one column (a conversation) of the model that owns the graph
+struct NoiseColumn { bool seeded = false, open = true; uint64_t seed = 0; int64_t frame = 0; int top_k = 0, top_k_text = 0; };
+
 // ---------------------------------------------------------------------------------------------------
 // graph context: persistent (built once, replayed) or scratch (rebuilt every frame)
 // mirrors the upload / alloc / compute protocol of src/context.h:227-653
@@ -53,9 +65,10 @@ struct Builder {
     ggml_backend_buffer_t buf = nullptr;
     struct upload { T t; std::vector<uint8_t> data; };
     std::vector<upload> consts;
-    struct noise { T t; float lambd; };
+    struct noise { T t; float lambd; int site; };   // site: 0 the text head, 1 + k Depth step k, -1 a sampler outside the frame protocol
     std::vector<noise> exponentials;
     std::vector<float> noise_tmp;
+    std::vector<NoiseColumn> noise_cols;   // filled by the model before compute() once a column has been seeded (moshi_hot_set_sampling); else empty
     struct download { T t; void * dst; size_t n; };
     std::vector<download> readbacks;   // ScratchContext::build_forward_expand(tensor, dst): read back after compute, before the buffer is freed (src/context.h:588-606)
 
@@ -76,7 +89,7 @@ struct Builder {
         std::vector<float> v((size_t) ggml_nelements(t), val);
         return constant(t, v.data());
     }
-    T exponential(int64_t n0, int64_t n1, float lambd) { T t = tensor(GGML_TYPE_F32, n0, n1); exponentials.push_back({ t, lambd }); return t; }
+    T exponential(int64_t n0, int64_t n1, float lambd, int site = -1) { T t = tensor(GGML_TYPE_F32, n0, n1); exponentials.push_back({ t, lambd, site }); return t; }
     // deferred scalar sets of a scratch context (src/context.h:562-586)
     void set_later(T t, const void * data, size_t n) { consts.push_back({ t, std::vector<uint8_t>((const uint8_t *) data, (const uint8_t *) data + n) }); }
 
@@ -94,6 +107,17 @@ struct Builder {
             const int64_t n = ggml_nelements(e.t);
             noise_tmp.resize((size_t) n);
             for (int64_t i = 0; i < n; i++) noise_tmp[(size_t) i] = -logf(rand() / (float) RAND_MAX) / e.lambd;   // src/context.h:475-476
+            // seeded columns: the sweep above is drawn in full as ever (the unseeded columns keep their draws), then a seeded column's row is replaced
+            // by its own stream - ranks past its top-k get +inf (q = p / inf = 0 there: the argmax stays inside the first top_k ranks); a seeded
+            // column that is closed gets a constant (its tokens are dropped)
+            const int64_t k = e.t->ne[0], nb = e.t->ne[1];
+            for (int64_t b = 0; e.site >= 0 && b < nb && b < (int64_t) noise_cols.size(); b++) {
+                const NoiseColumn & col = noise_cols[(size_t) b];
+                if (!col.seeded) continue;
+                const int64_t top = e.site == 0 ? col.top_k_text : col.top_k;
+                float * row = noise_tmp.data() + b * k;
+                for (int64_t r = 0; r < k; r++) row[r] = !col.open ? 1.f : r < top ? sampling_noise(col.seed, col.frame, e.site, (int) r, e.lambd) : INFINITY;
+            }
             ggml_backend_tensor_set(e.t, noise_tmp.data(), 0, (size_t) n * 4);
         }
     }
@@ -621,7 +645,7 @@ T transformer_inline(Builder & g, Transformer & tr, T x, T mask_override = nullp
 }
 
 // moshi_sample_token (moshi/utils/sampling.h:4-64)
-T sample_token(Builder & g, T logits, float temp, int top_k) {
+T sample_token(Builder & g, T logits, float temp, int top_k, int site = -1) {
     if (!(temp > 0.f)) return ggml_argmax(g, logits);
     T probs = ggml_soft_max(g, ggml_scale(g, logits, 1.f / temp));
     const int k = (int) probs->ne[0] < top_k ? (int) probs->ne[0] : top_k;
@@ -630,7 +654,7 @@ T sample_token(Builder & g, T logits, float temp, int top_k) {
     rows = ggml_get_rows(g, ggml_cont(g, rows), indices);
     probs = ggml_permute(g, rows, 1, 0, 2, 3);
     T in2 = ggml_reshape_2d(g, probs, probs->ne[0], probs->ne[1] * probs->ne[2] * probs->ne[3]);
-    T q = ggml_div(g, in2, g.exponential(in2->ne[0], in2->ne[1], 1.f));
+    T q = ggml_div(g, in2, g.exponential(in2->ne[0], in2->ne[1], 1.f, site));
     T next = ggml_argmax(g, q);
     next = ggml_reshape_4d(g, next, next->ne[0], probs->ne[1], probs->ne[2], probs->ne[3]);
     T irows = ggml_permute(g, indices, 1, 0, 2, 3);
@@ -638,18 +662,20 @@ T sample_token(Builder & g, T logits, float temp, int top_k) {
 }
 
 // moshi_sample_token over the batch dimension of lockstep streams: logits [n, 1, B] -> I32 [B], one token per column. The same op sequence as
-// sample_token with B columns instead of one; in sampled mode the noise is one [k, B] tensor, drawn in one sweep (column b = stream b).
-T sample_tokens_streams(Builder & g, T logits, float temp, int top_k) {
+// sample_token with B columns instead of one; in sampled mode the noise is one [k, B] tensor, drawn in one sweep (column b = stream b), and the
+// temperature is a per-column input: mul by inv_temp F32 [1, B] = 1.f / temp_b (the same float product as scale by 1.f / temp). k = the configuration's
+// top_k is the compiled maximum; a column with a smaller one gets infinite noise past it (Builder::upload_noise).
+T sample_tokens_streams(Builder & g, T logits, float temp, int top_k, T inv_temp, int site) {
     const int64_t n = logits->ne[0], B = ggml_nelements(logits) / n;
     T l2 = ggml_reshape_2d(g, logits, n, B);
     if (!(temp > 0.f)) return ggml_argmax(g, l2);
-    T probs = ggml_soft_max(g, ggml_scale(g, l2, 1.f / temp));                   // [n, B]
+    T probs = ggml_soft_max(g, inv_temp ? ggml_mul(g, l2, inv_temp) : ggml_scale(g, l2, 1.f / temp));   // [n, B]
     const int k = (int) n < top_k ? (int) n : top_k;
     T indices = ggml_cont(g, ggml_argsort_top_k(g, probs, k));                    // [k, B]
     T rows = ggml_cont(g, ggml_permute(g, ggml_reshape_3d(g, probs, n, 1, B), 1, 0, 2, 3));   // [1, n, B]
     T picked = ggml_get_rows(g, rows, indices);                                   // [1, k, B]
     T in2 = ggml_reshape_2d(g, picked, k, B);
-    T q = ggml_div(g, in2, g.exponential(k, B, 1.f));
+    T q = ggml_div(g, in2, g.exponential(k, B, 1.f, site));
     T next = ggml_argmax(g, q);                                                   // [B]
     T irows = ggml_cont(g, ggml_permute(g, ggml_reshape_3d(g, indices, k, 1, B), 1, 0, 2, 3));   // [1, k, B]
     T tok = ggml_get_rows(g, irows, ggml_reshape_2d(g, next, 1, B));              // [1, 1, B]
@@ -830,6 +856,12 @@ struct moshi_hot_model {
     // and advanced together. Slots: each column opened, closed and positioned on its own; a closed column keeps its frame count and position.
     struct Column { std::vector<std::vector<int>> cache; int64_t frames = 0, pos = 0; bool open = false; };
     int n_streams = 1; ModelKind kind = ModelKind::single; std::vector<Column> cols;
+    // per-conversation sampling (moshi_hot_set_sampling): one entry per column (one for a single-stream model), the configuration's values until set.
+    // A B > 1 sampled model's graphs take 1.f / temp of every column as inputs (inv_temp_text in the Temporal graph, inv_temp in the Depth graph),
+    // uploaded when a graph is built and after every change (sampling_dirty).
+    struct Sampling { moshi_hot_sampling s; bool seeded = false; };
+    std::vector<Sampling> sampling; bool any_seeded = false, sampling_dirty = true;
+    T inv_temp_text = nullptr, inv_temp = nullptr;
 
     // Mimi
     Rvq rvq_first, rvq_rest;
@@ -1000,7 +1032,8 @@ void build_temporal_graph(moshi_hot_model * m) {
     m->g_transformer_out = x;
     m->text_logits = linear(g, m->text_linear, x);
     g.expand(ggml_cpy(g, x, m->transformer_out));
-    m->sampler_out = m->n_streams > 1 ? sample_tokens_streams(g, m->text_logits, c.temp_text, c.top_k_text) : sample_token(g, m->text_logits, c.temp_text, c.top_k_text);
+    if (m->n_streams > 1 && c.temp_text > 0.f) { m->inv_temp_text = g.tensor(GGML_TYPE_F32, 1, m->n_streams); m->sampling_dirty = true; }
+    m->sampler_out = m->n_streams > 1 ? sample_tokens_streams(g, m->text_logits, c.temp_text, c.top_k_text, m->inv_temp_text, 0) : sample_token(g, m->text_logits, c.temp_text, c.top_k_text, 0);
     g.expand(m->sampler_out);
     if (m->tok_state) g.expand(ggml_cpy(g, ggml_reshape_1d(g, m->sampler_out, 1), ggml_view_1d(g, m->tok_state, 1, 0)));
     g.alloc();
@@ -1043,7 +1076,7 @@ void build_depth_graph(moshi_hot_model * m) {
         T dout = transformer_inline(g, m->depth, din);
         T logits = linear(g, m->linears[(size_t) k], dout);
         m->dep_logits.push_back(logits);
-        next = sample_token(g, logits, c.temp, c.top_k);
+        next = sample_token(g, logits, c.temp, c.top_k, 1 + k);
         view = k == 0 ? ggml_view_1d(g, tokens, 1, 0) : ggml_view_1d(g, view, 1, 4);
         g.expand(ggml_cpy(g, next, view));
     }
@@ -1063,6 +1096,7 @@ void build_depth_graph_streams(moshi_hot_model * m) {
     m->dep_text_scale = g.tensor(GGML_TYPE_F32, 1, B);
     T last = ggml_mul(g, ggml_get_rows(g, m->depformer_text_emb, m->dep_text_idx), m->dep_text_scale);   // [E, B]
     T tokens = g.tensor(GGML_TYPE_I32, (int64_t) B * c.dep_q);
+    if (c.temp > 0.f) { m->inv_temp = g.tensor(GGML_TYPE_F32, 1, B); m->sampling_dirty = true; }
     T view = nullptr, next = nullptr;
     for (int k = 0; k < c.dep_q; k++) {
         if (k > 0) last = ggml_get_rows(g, m->depformer_emb[(size_t) (k - 1)], next);   // moshi_scaled_embedding_chained (lm_utils.h:208-217)
@@ -1073,7 +1107,7 @@ void build_depth_graph_streams(moshi_hot_model * m) {
         T dout = transformer_inline(g, m->depth, din);
         T logits = linear(g, m->linears[(size_t) k], dout);                          // [card, 1, B]
         m->dep_logits.push_back(logits);
-        next = sample_tokens_streams(g, logits, c.temp, c.top_k);
+        next = sample_tokens_streams(g, logits, c.temp, c.top_k, m->inv_temp, 1 + k);
         view = k == 0 ? ggml_view_1d(g, tokens, B, 0) : ggml_view_1d(g, view, B, (size_t) B * 4);
         g.expand(ggml_cpy(g, next, view));
     }
@@ -1216,6 +1250,69 @@ extern "C" void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t of
     moshi_hot_model::Column * s = slot(m, b);
     if (s && offset >= 0) s->pos = offset;
 }
+// ---- per-conversation sampling (moshi_hot.h) ---------------------------------------------------------------------------------------------------
+extern "C" void moshi_hot_sampling_noise(uint64_t seed, int64_t frame, int site, int n, float * out) {
+    for (int r = 0; r < n; r++) out[r] = sampling_noise(seed, frame, site, r, 1.f);
+}
+static bool sampled_model(const moshi_hot_model * m) { return m->cfg.temp > 0.f && m->cfg.temp_text > 0.f; }
+// a single-stream model whose two persistent graphs hold every sampler of a frame: the moshika-shaped LM stepped by moshi_hot_lm_step* (blocking steps)
+static bool single_sampling_supported(const moshi_hot_model * m) {
+    const moshi_hot_config & c = m->cfg;
+    return c.enable_lm && !c.personaplex && !c.extra_heads && !c.demux_second_stream && !c.depformer_low_rank && !c.delay_steps && !c.cross_attention &&
+           !c.condition_sum && !c.dep_schedule_len && c.tp_world <= 1 && c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && c.dep_q > 0;
+}
+extern "C" int moshi_hot_set_sampling(moshi_hot_model_t * m, int b, const struct moshi_hot_sampling * s) {
+    const moshi_hot_config & c = m->cfg;
+    if (!s || !sampled_model(m) || b < 0 || b >= m->n_streams || b >= (int) m->sampling.size()) return -1;
+    if (m->n_streams == 1) {   // the graphs keep the configuration's baked 1 / temp and top-k: only the seed is free
+        if (!single_sampling_supported(m) || m->tp_frame || m->depth_hook) return -1;
+        if (s->temp != c.temp || s->temp_text != c.temp_text || s->top_k != c.top_k || s->top_k_text != c.top_k_text) return -1;
+    } else {
+        if (!(s->temp > 0.f) || !(s->temp_text > 0.f) || s->top_k < 1 || s->top_k > c.top_k || s->top_k_text < 1 || s->top_k_text > c.top_k_text) return -1;
+    }
+    m->sampling[(size_t) b].s = *s;
+    m->sampling[(size_t) b].seeded = true;
+    m->any_seeded = true;
+    m->sampling_dirty = true;
+    return 0;
+}
+extern "C" int moshi_hot_get_sampling(moshi_hot_model_t * m, int b, struct moshi_hot_sampling * s, int * seeded) {
+    if (b < 0 || b >= (int) m->sampling.size()) return -1;
+    if (s) *s = m->sampling[(size_t) b].s;
+    if (seeded) *seeded = m->sampling[(size_t) b].seeded ? 1 : 0;
+    return 0;
+}
+namespace {
+// before a frame's Temporal / Depth graphs run: the per-column 1 / temp inputs of a B > 1 sampled model (after a change only) and, once a column has
+// been seeded, every column's (seed, frame) for Builder::upload_noise
+void stage_sampling(moshi_hot_model * m) {
+    const int B = m->n_streams;
+    if (m->sampling_dirty) {
+        std::vector<float> inv((size_t) B);
+        if (m->inv_temp_text) {
+            for (int b = 0; b < B; b++) inv[(size_t) b] = 1.f / m->sampling[(size_t) b].s.temp_text;
+            ggml_backend_tensor_set(m->inv_temp_text, inv.data(), 0, (size_t) B * 4);
+        }
+        if (m->inv_temp) {
+            for (int b = 0; b < B; b++) inv[(size_t) b] = 1.f / m->sampling[(size_t) b].s.temp;
+            ggml_backend_tensor_set(m->inv_temp, inv.data(), 0, (size_t) B * 4);
+        }
+        m->sampling_dirty = false;
+    }
+    if (!m->any_seeded) return;
+    std::vector<NoiseColumn> cols((size_t) B);
+    for (int b = 0; b < B; b++) {
+        const auto & sp = m->sampling[(size_t) b];
+        NoiseColumn & nc = cols[(size_t) b];
+        nc.seeded = sp.seeded; nc.seed = sp.s.seed; nc.top_k = sp.s.top_k; nc.top_k_text = sp.s.top_k_text;
+        nc.open = B > 1 ? m->cols[(size_t) b].open : true;
+        nc.frame = B > 1 ? m->cols[(size_t) b].frames : (int64_t) m->offset;
+    }
+    if (m->g_temporal) m->g_temporal->noise_cols = cols;
+    if (m->g_depth) m->g_depth->noise_cols = cols;
+}
+}  // namespace
+
 // the model's weights come from a GGUF file written by moshi_hot_save_gguf (the reference's `*.gguf` checkpoints: WeightLoader::from_gguf + load_gguf)
 extern "C" moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, const struct moshi_hot_config * cfg, const char * path) { return create_model(backend, cfg, 0, path); }
 // WeightLoader::save_gguf (loader.h:227-233): every tensor of the weight context, in context order
@@ -1238,6 +1335,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     m->be = backend;
     m->n_streams = n_streams;
     m->kind = kind;   // (build_temporal_graph reads it)
+    m->sampling.assign((size_t) n_streams, { { 0, cfg->temp, cfg->temp_text, cfg->top_k, cfg->top_k_text }, false });
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
     if (gguf_path) m->W->gguf_path = gguf_path;
@@ -1487,6 +1585,7 @@ void depth_step(moshi_hot_model * m, int32_t text_token, std::vector<int32_t> & 
         if (!m->cfg.chain_depth) ggml_backend_tensor_set(m->dep_text_idx, &id, 0, 4);
         ggml_backend_tensor_set(m->dep_text_scale, &sc, 0, 4);
     }
+    if (m->any_seeded) stage_sampling(m);   // (the Depth graph may have been built after the Temporal graph ran)
     m->g_depth->compute();
     if (m->cfg.chain_depth && !m->temporal_staged) {
         // the next frame's Temporal step inputs do not depend on this frame's samples: queue them behind the Depth graph, off the host's critical path
@@ -1945,6 +2044,7 @@ extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens
         transformer_graph_step(*m->scratch, m->temporal, 1);
         m->scratch->compute_scratch();
     }
+    if (m->any_seeded) stage_sampling(m);
     m->g_temporal->compute();
     }
     if (m->after_temporal_launch) { m->after_temporal_launch(); m->after_temporal_launch = nullptr; }
@@ -2114,6 +2214,7 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
         transformer_graph_step_slots(*m->scratch, m->temporal, pos);
     }
     m->scratch->compute_scratch();
+    stage_sampling(m);
     m->g_temporal->compute();
     ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
     }

@@ -26,6 +26,25 @@ class Config(C.Structure):
         return 8 if self.personaplex else self.dep_q
 
 
+class Sampling(C.Structure):
+    """struct moshi_hot_sampling: one column's seed, temperatures and top-k values (moshi_hot_set_sampling)"""
+    _fields_ = [("seed", C.c_uint64), ("temp", C.c_float), ("temp_text", C.c_float), ("top_k", C.c_int32), ("top_k_text", C.c_int32)]
+
+
+def set_sampling(lib, model, b, seed, temp, temp_text, top_k, top_k_text):
+    """moshi_hot_set_sampling -> 0, or -1 when the model refuses"""
+    s = Sampling(seed, temp, temp_text, top_k, top_k_text)
+    return lib.moshi_hot_set_sampling(model, b, C.byref(s))
+
+
+def get_sampling(lib, model, b):
+    """moshi_hot_get_sampling -> (seed, temp, temp_text, top_k, top_k_text, seeded), or None for a bad column"""
+    s, seeded = Sampling(), C.c_int(0)
+    if lib.moshi_hot_get_sampling(model, b, C.byref(s), C.byref(seeded)) != 0:
+        return None
+    return (s.seed, s.temp, s.temp_text, s.top_k, s.top_k_text, bool(seeded.value))
+
+
 P = C.c_void_p
 SIGNATURES = {
     "moshi_hot_config_moshika": (None, [C.POINTER(Config)]),
@@ -50,6 +69,9 @@ SIGNATURES = {
     "moshi_hot_slot_position": (C.c_int64, [P, C.c_int]),
     "moshi_hot_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
     "moshi_hot_lm_step_slots": (C.c_int, [P, P, P, P, P]),
+    "moshi_hot_set_sampling": (C.c_int, [P, C.c_int, P]),
+    "moshi_hot_get_sampling": (C.c_int, [P, C.c_int, P, P]),
+    "moshi_hot_sampling_noise": (None, [C.c_uint64, C.c_int64, C.c_int, C.c_int, P]),
     "moshi_hot_save_gguf": (C.c_int, [P, C.c_char_p]),
     "moshi_hot_create_from_gguf": (P, [P, C.POINTER(Config), C.c_char_p]),
     "moshi_hot_tensor_file_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
