@@ -136,6 +136,21 @@ GGML_API void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offs
 // are valid, 0 while its own delay ring fills, -1 when it is closed; the outputs of a slot whose status is not 1 are written as -1. Returns the
 // number of slots with status 1, or -1 on a model that is not a slots model. With no slot open it does no device work and returns 0.
 GGML_API int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio, int32_t * status);
+// Slot prefill: admit conversations that already have a history. Job j advances open slot slots[j] by n_frames[j] provided frames (tokens[j]:
+// n_frames[j] x (n_q + 1), text first - what moshi_hot_prefill takes), leaving the slot as a fresh single-stream model is after moshi_hot_prefill over
+// the same frames: delay ring, frame count (the frame the seeded noise source sees), stream position, the slot's KV ring rows and its row of
+// transformer_out. The rows of all jobs are laid end to end in job order and cut into [dim, T] passes of at most `chunk` rows (< 1 or > 64: 64): a
+// job may span passes, a pass may hold several jobs - the weights stream once per pass whatever the number of jobs. Nothing outside the jobs' own
+// columns is touched. Returns the number of frames prefilled (0 with no device work for n_jobs == 0 or no frames at all), or -1 with no state changed
+// when the model is not a slots model, n_jobs > B, a slot index is bad, closed or named twice, or a job would pass the ring's end
+// (position + n_frames > context: the T > 1 mask is causal only before the wrap).
+GGML_API int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk);
+GGML_API int moshi_hot_slot_prefill(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk);   // one job
+// hold != 0: moshi_hot_lm_step_slots steps open slot b as it steps a closed one (fed the initial tokens at its frozen position, nothing of its column
+// advances; only ring row position % context of its own column is written, which the next prefill row or live frame rewrites before a mask row admits
+// it) and reports status -2 with outputs -1 - a long history can be prefilled one pass at a time between the frames of the live slots. hold == 0
+// releases it; moshi_hot_slot_open / _close clear the hold. Returns 0, or -1 for a bad index, a closed slot or a model that is not a slots model.
+GGML_API int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold);
 
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute

@@ -24,6 +24,7 @@
 #include <deque>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -336,7 +337,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -819,7 +820,8 @@ static bool match_matvec(const analysis & an, int pos, mv_group & grp) {
 }
 
 // B. single-token attention block
-struct attn_group { attn_args a; int emit_pos; std::vector<int> members; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa; };   // B > 1: match_attention_streams
+struct attn_group { attn_args a; int emit_pos; std::vector<int> members; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
+                    bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
 
 static const ggml_tensor * strip_views(const ggml_tensor * t) {
     while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE)) t = t->src[0];
@@ -867,7 +869,12 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
     const ggml_tensor * x1 = sole_consumer(an, pv);
     if (!x1 || x1->op != GGML_OP_PERMUTE) return false;
     const ggml_tensor * x2 = sole_consumer(an, x1);
-    if (!x2 || x2->op != GGML_OP_CONT) return false;
+    // the block's output: a dense copy of its own, or (slot prefill) a copy into the block's row range of a wider [D, H, T] tensor
+    const bool into_rows = x2 && x2->op == GGML_OP_CPY && x2->src[0] == x1 && x2->type == GGML_TYPE_F32;
+    if (!x2 || (x2->op != GGML_OP_CONT && !into_rows)) return false;
+    // the rings: whole [D, C, H] tensors, or (slot prefill) [D, C, H] views of one column of [D, C, H, B] rings
+    const bool column = kc->ne[3] == 1 && kc->view_src && kc->view_src->ne[3] > 1;
+    if (column != (vc->ne[3] == 1 && vc->view_src && vc->view_src->ne[3] > 1) || (into_rows && !column)) return false;
 
     const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], Tn = qo->ne[1];
     if (qo->ne[0] != D || Tn < 1 || Tn > 64 || qo->ne[2] != H || qo->ne[3] != 1) return false;   // B == 1; blocks longer than 4 rows (prompt prefill) run as consecutive launches of 4
@@ -919,9 +926,11 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
             case GGML_OP_SET_ROWS: n_sr++; break;
             case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: case GGML_OP_CONT:
             case GGML_OP_MUL: case GGML_OP_SUB: case GGML_OP_ADD: case GGML_OP_CONCAT: break;
+            case GGML_OP_CPY: if (t != x2) return false; break;
             default: return false;
         }
         members.push_back(p);
+        if (t == x2 && into_rows) { stack.push_back(t->src[0]); continue; }   // (the destination rows are not the block's: they lead to the previous job)
         for (int s = 0; s < GGML_MAX_SRC; s++) if (t->src[s]) stack.push_back(t->src[s]);
     }
     if (n_mm != 2 || n_sm != 1 || n_sr != 2) return false;
@@ -957,6 +966,7 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
     a.scale = ggml_get_op_params_f32(sm, 0);
     a.out = (float *) x2->data;
     a.out_ts = H * D;
+    grp.column = column;
     grp.members = members;
     grp.emit_pos = pos_of(an, x2);
     return true;
@@ -2129,7 +2139,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
                 // workgroup of this projection instead of launching it on its own (16 heads x 8 slots is ~nothing)
                 for (auto & ag : attn_groups) {
                     const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || ag.B > 1 || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
+                    if (ag.emit_pos < 0 || ag.B > 1 || ag.column || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
                     if (a.K != 1024 || at.H != 16 || ag.emit_pos > grp.emit_pos || uses_of(an, g->nodes[ag.emit_pos]) != 1) continue;
                     p->attn_copies.emplace_back(new attn_args(at));   // owned by the plan, passed by value at launch
                     a.prologue = MV_ATTN;
@@ -2144,7 +2154,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
                 bool merged = false;
                 for (auto & ag : attn_groups) {
                     const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || ag.B > 1 || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
+                    if (ag.emit_pos < 0 || ag.B > 1 || ag.column || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
                     if (!k_inproj_attn_supported(a, at, c->usable_cus)) continue;
                     // every reader of the projection's output must be inside the attention block
                     // (followed through layout-only nodes - a view / reshape / permute / transpose of the output is the output: a reader of such an alias that is
@@ -2262,6 +2272,49 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             p->n_fused += (int) members.size();
         }
     }
+    // slot prefill: the column groups of one layer of one pass (consecutive groups of one shape with nothing but layout nodes and their own members
+    // between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase
+    for (size_t gi = 0; gi < attn_groups.size(); ) {
+        if (!attn_groups[gi].column || attn_groups[gi].emit_pos < 0) { gi++; continue; }
+        const attn_args & a0 = attn_groups[gi].a;
+        std::set<int> inside(attn_groups[gi].members.begin(), attn_groups[gi].members.end());
+        size_t ge = gi + 1;
+        int lo = attn_groups[gi].emit_pos, hi = lo;
+        // the row strides of q / k / v mean nothing to a one-row job (strided_resolve leaves them 0): the jobs of more than one row must agree on them
+        const attn_args * rows = a0.T > 1 ? &a0 : nullptr;
+        while (ge < attn_groups.size() && ge - gi < ATTN_BLOCKS_MAX) {
+            const attn_group & n = attn_groups[ge];
+            const attn_args & b = n.a;
+            if (!n.column || n.emit_pos < 0 || b.H != a0.H || b.D != a0.D || b.C != a0.C || b.scale != a0.scale || b.out_ts != a0.out_ts || (b.rot != nullptr) != (a0.rot != nullptr) ||
+                (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts)) || b.q_hs != a0.q_hs || b.k_hs != a0.k_hs || b.v_hs != a0.v_hs ||
+                b.k_nb1 != a0.k_nb1 || b.k_nb2 != a0.k_nb2 || b.v_nb1 != a0.v_nb1 || b.v_nb2 != a0.v_nb2 || b.kcache == a0.kcache) break;
+            std::set<int> both = inside;
+            both.insert(n.members.begin(), n.members.end());
+            const int nlo = n.emit_pos < lo ? n.emit_pos : lo, nhi = n.emit_pos > hi ? n.emit_pos : hi;
+            bool clean = true;
+            for (int i = nlo + 1; i < nhi && clean; i++) if (!is_view_op(g->nodes[i]->op) && !both.count(i)) clean = false;
+            if (!clean) break;
+            inside.swap(both); lo = nlo; hi = nhi;
+            if (b.T > 1 && !rows) rows = &b;
+            ge++;
+        }
+        attn_blocks_args ba;
+        memset(&ba, 0, sizeof(ba));
+        ba.a = a0;
+        if (rows) { ba.a.q_ts = rows->q_ts; ba.a.k_ts = rows->k_ts; ba.a.v_ts = rows->v_ts; }
+        ba.n_jobs = (int) (ge - gi);
+        for (size_t k = gi; k < ge; k++) {
+            const attn_args & b = attn_groups[k].a;
+            ba.job[k - gi] = { b.q, b.k, b.v, b.kcache, b.vcache, b.mask, b.rot, b.index, b.out, b.T };
+            attn_groups[k].emit_pos = -1;
+        }
+        unsigned * err = c->err_dev;
+        auto & at = at_pos[hi];
+        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 0; k_attn_blocks(s, b, err); });
+        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 1; k_attn_blocks(s, b, err); });
+        p->n_attn_block_launches += 2; p->n_attn_block_jobs += ba.n_jobs;
+        gi = ge;
+    }
     for (auto & ag : attn_groups) {
         if (ag.emit_pos < 0) continue;
         const attn_args a = ag.a;
@@ -2300,7 +2353,10 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
                 fprintf(stderr, "plan %4d %-18s [%5lld %5lld %4lld %2lld] %s%s%s\n", i, ggml_op_name(n->op), (long long) n->ne[0], (long long) n->ne[1], (long long) n->ne[2],
                         (long long) n->ne[3], an.skip[(size_t) i] ? "fused" : (layout ? "-" : "GENERIC"), itd != at_pos.end() ? " <emit group>" : "", n->view_src ? " (alias)" : "");
         }
-        if (!an.skip[(size_t) i]) emit_generic(em, g->nodes[i]);
+        if (!an.skip[(size_t) i]) {
+            if (g->nodes[i]->op == GGML_OP_SOFT_MAX || g->nodes[i]->op == GGML_OP_SET_ROWS) p->n_generic_attn_nodes++;
+            emit_generic(em, g->nodes[i]);
+        }
         auto it = at_pos.find(i);
         if (it != at_pos.end()) for (auto & f : it->second) p->steps.push_back(f);
     }
@@ -2433,6 +2489,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
         c->stats.nodes_in_last_plan = p->n_nodes;
         c->stats.fused_nodes_in_last_plan = p->n_fused;
         c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
+        c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
         plan_free(c, p);   // workspaces return to the pool; reuse is stream-ordered
         return GGML_STATUS_SUCCESS;
     }
@@ -2472,6 +2529,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
     c->stats.nodes_in_last_plan = p->n_nodes;
     c->stats.fused_nodes_in_last_plan = p->n_fused;
     c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
+    c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
     return GGML_STATUS_SUCCESS;
 }
 

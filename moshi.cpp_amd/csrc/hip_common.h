@@ -201,6 +201,16 @@ void k_attn_decode(hipStream_t s, const attn_args & a, void * ws = nullptr, unsi
 // stream (stream slots, moshi_hot_create_slots: mask_bs = C, rot_bs = D floats, index_bs = 1), each workgroup then scanning its own stream's mask row.
 struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs, mask_bs, rot_bs, index_bs; };
 void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err = nullptr);
+// Slot prefill (moshi_hot_slots_prefill): the attention blocks of one layer of one [dim, T] pass - job j = T_j consecutive rows of the pass that belong
+// to one slot: its own rows of q / k / v, its own column of the [D, C, H, B] rings, its own mask block [C, T_j], RoPE rows, ring slots and output rows -
+// as ONE pair of launches (write_only = 1: every row's K / V into its ring; then 0: all rows attend). Workgroup (g, h, j) runs attn_decode_body on rows
+// 4 g .. 4 g + 3 of job j for head h exactly as k_attn_decode's T > 4 launches do for a single ring (a job of <= 4 rows is one group); workgroups past a
+// job's last group leave at once. No workgroup waits for another: the write-then-attend order is the launch boundary. `a` holds what the jobs share
+// (strides, H / D / C, scale); its per-job fields are filled from the table.
+#define ATTN_BLOCKS_MAX 16
+struct attn_block_job { const float * q, * k, * v; char * kcache, * vcache; const float * mask, * rot; const int32_t * index; float * out; int T; };
+struct attn_blocks_args { attn_args a; int n_jobs, write_only; attn_block_job job[ATTN_BLOCKS_MAX]; };
+void k_attn_blocks(hipStream_t s, const attn_blocks_args & a, unsigned * err = nullptr);
 // rows consecutive rows of n floats, row r copied from its own source src[r] (stream slots: the B mask rows, each a window of the bias table at the
 // slot's own column, transformer.h:1259-1289) - one launch instead of one per row
 #define COPY_ROWS_MAX 16

@@ -1802,6 +1802,53 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
     else      attn_streams_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(sa, w);
 }
 
+// Slot prefill: workgroup (g, h, j) runs attn_decode_body for head h on rows 4 g .. 4 g + 3 of job j of the table - what attn_decode_kernel's workgroup
+// (h, g) does in the T > 4 launches of a single ring, on the job's own rows, ring column, mask block, RoPE rows, ring slots and output rows. The job
+// index is uniform over the workgroup: its table entry is read from the kernel arguments by scalar loads.
+template <int NWA>
+__global__ void __launch_bounds__(NWA * 64) __attribute__((amdgpu_waves_per_eu(2)))
+attn_blocks_kernel(attn_blocks_args ba, attn_split_ws w) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const attn_block_job & jb = ba.job[blockIdx.z];
+    const int groups = (jb.T + ATTN_MAX_T - 1) / ATTN_MAX_T;
+    if ((int) blockIdx.x >= groups) return;   // (the grid is as wide as the longest job)
+    attn_args a = ba.a;
+    a.q = jb.q; a.k = jb.k; a.v = jb.v;
+    a.kcache = jb.kcache; a.vcache = jb.vcache;
+    a.mask = jb.mask; a.rot = jb.rot; a.index = jb.index; a.out = jb.out;
+    a.T = jb.T; a.n_groups = groups; a.write_only = ba.write_only; a.row_split = 0;
+    attn_decode_body<false, NWA, AT_PLAIN>(a, w, smem, (int) blockIdx.y, 0, (int) blockIdx.x);
+}
+void k_attn_blocks(hipStream_t s, const attn_blocks_args & ba, unsigned * err) {
+    const attn_args & a = ba.a;
+    GGML_ASSERT(ba.n_jobs >= 1 && ba.n_jobs <= ATTN_BLOCKS_MAX);
+    GGML_ASSERT(a.D % 8 == 0 && 64 % (a.D / 8) == 0 && ATTN_MAX_T * a.D <= 2 * ATTN_NW_BASE * 64);
+    int max_groups = 1;
+    for (int j = 0; j < ba.n_jobs; j++) {
+        GGML_ASSERT(ba.job[j].T >= 1 && ba.job[j].T <= 64);
+        const int g = (ba.job[j].T + ATTN_MAX_T - 1) / ATTN_MAX_T;
+        if (g > max_groups) max_groups = g;
+    }
+    static const int wide_on = env_int("MI355X_ATTN_WIDE", 1);
+    const bool wide = wide_on && a.D <= 64 && a.C >= 128;   // (attn_decode_kernel's choice for the same head)
+    attn_args sized = a; sized.n_groups = 2;                // LDS for ATTN_MAX_T rows per workgroup, whatever the job's tail
+    const size_t smem = attn_smem_bytes(sized, false, wide);
+    GGML_ASSERT(smem <= 160 * 1024);
+    if (smem > 64 * 1024) {
+        static size_t granted[2] = { 0, 0 };
+        if (granted[wide] < smem) {
+            HIP_CHECK(hipFuncSetAttribute(wide ? (const void *) attn_blocks_kernel<ATTN_NW_WIDE> : (const void *) attn_blocks_kernel<ATTN_NW_BASE>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int) smem));
+            granted[wide] = smem;
+        }
+    }
+    static const int single_max = env_int("MI355X_ATTN_SINGLE_MAX", ATTN_SINGLE_MAX), big_min = env_int("MI355X_ATTN_BIG_MIN", ATTN_SPLIT_BIG_MIN);
+    const attn_split_ws w = { nullptr, nullptr, nullptr, 1, err, ATTN_SPLIT_SLOTS, single_max, big_min };
+    const dim3 grid((unsigned) max_groups, (unsigned) a.H, (unsigned) ba.n_jobs);
+    if (wide) attn_blocks_kernel<ATTN_NW_WIDE><<<grid, ATTN_NW_WIDE * 64, smem, s>>>(ba, w);
+    else      attn_blocks_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(ba, w);
+}
+
 // row r of the destination <- src[r]: workgroup (x, r) copies 256 floats of row r (the row pointer is uniform: a kernel-argument load)
 __global__ void __launch_bounds__(256) copy_rows_kernel(copy_rows_args a) {
     const int r = (int) blockIdx.y;

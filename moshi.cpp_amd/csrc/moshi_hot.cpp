@@ -854,7 +854,7 @@ struct moshi_hot_model {
     // column. A column holds its delay ring, the frames stepped since it opened (the ring's offset) and its stream position (mask row, RoPE phase,
     // ring slot; moshi_hot_set_context_fill / moshi_hot_slot_set_fill move it alone). Lockstep: every column open from creation, all at one position
     // and advanced together. Slots: each column opened, closed and positioned on its own; a closed column keeps its frame count and position.
-    struct Column { std::vector<std::vector<int>> cache; int64_t frames = 0, pos = 0; bool open = false; };
+    struct Column { std::vector<std::vector<int>> cache; int64_t frames = 0, pos = 0; bool open = false, held = false; };   // held: moshi_hot_slot_hold
     int n_streams = 1; ModelKind kind = ModelKind::single; std::vector<Column> cols;
     // per-conversation sampling (moshi_hot_set_sampling): one entry per column (one for a single-stream model), the configuration's values until set.
     // A B > 1 sampled model's graphs take 1.f / temp of every column as inputs (inv_temp_text in the Temporal graph, inv_temp in the Depth graph),
@@ -1239,7 +1239,7 @@ extern "C" int moshi_hot_slot_open(moshi_hot_model_t * m, int b) {
 extern "C" int moshi_hot_slot_close(moshi_hot_model_t * m, int b) {
     moshi_hot_model::Column * s = slot(m, b);
     if (!s) return -1;
-    s->open = false;
+    s->open = s->held = false;
     return 0;
 }
 extern "C" int64_t moshi_hot_slot_position(moshi_hot_model_t * m, int b) {
@@ -1305,7 +1305,7 @@ void stage_sampling(moshi_hot_model * m) {
         const auto & sp = m->sampling[(size_t) b];
         NoiseColumn & nc = cols[(size_t) b];
         nc.seeded = sp.seeded; nc.seed = sp.s.seed; nc.top_k = sp.s.top_k; nc.top_k_text = sp.s.top_k_text;
-        nc.open = B > 1 ? m->cols[(size_t) b].open : true;
+        nc.open = B > 1 ? m->cols[(size_t) b].open && !m->cols[(size_t) b].held : true;   // (a held slot is stepped as a closed one)
         nc.frame = B > 1 ? m->cols[(size_t) b].frames : (int64_t) m->offset;
     }
     if (m->g_temporal) m->g_temporal->noise_cols = cols;
@@ -2180,21 +2180,22 @@ void set_token_inputs(T idx, T scale, const std::vector<int32_t> & ids) {
 // moshi_lmgen_step (lm.h:778-979) of a B > 1 model: the host half runs per column over the column's own delay ring, the Temporal and the Depth graph
 // once for all columns (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - create_columns refuses those). An open
 // column takes its codes from in_audio and advances one frame; a closed one is fed the initial tokens at its frozen position and is left as it is.
-// status[b]: -1 closed, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
+// A held slot (moshi_hot_slot_hold) is stepped as a closed one. status[b]: -1 closed, -2 held, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
 void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     const moshi_hot_config & c = m->cfg;
     const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
     int n_open = 0;
     for (int b = 0; b < B; b++) {
-        status[b] = m->cols[(size_t) b].open ? 0 : -1;
-        n_open += m->cols[(size_t) b].open;
+        const auto & col = m->cols[(size_t) b];
+        status[b] = !col.open ? -1 : col.held ? -2 : 0;
+        n_open += col.open && !col.held;
     }
     if (!n_open) return;
     if (!m->g_temporal) build_temporal_graph(m);
     if (!m->g_depth) build_depth_graph_streams(m);
     for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring (lm.h:819-824)
         auto & col = m->cols[(size_t) b];
-        if (!col.open) continue;
+        if (!col.open || col.held) continue;
         for (int i = 0; i < needed; i++) col.cache[(size_t) ((col.frames + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
     }
     std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
@@ -2203,7 +2204,7 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     for (int i = 0; i < ncb; i++) {
         for (int b = 0; b < B; b++) {
             const auto & col = m->cols[(size_t) b];
-            ids[(size_t) b] = !col.open || col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) (col.frames % CT)][(size_t) i];
+            ids[(size_t) b] = !col.open || col.held || col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) (col.frames % CT)][(size_t) i];
         }
         set_token_inputs(m->emb_idx[(size_t) i], m->emb_scale[(size_t) i], ids);
     }
@@ -2227,7 +2228,7 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979), per open column
     for (int b = 0; b < B; b++) {
         auto & col = m->cols[(size_t) b];
-        if (!col.open) continue;
+        if (!col.open || col.held) continue;
         const int64_t off = ++col.frames;
         col.pos++;
         auto & row = col.cache[(size_t) (off % CT)];
@@ -2378,7 +2379,156 @@ extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens,
     ggml_backend_mi355x_set_capture(m->be, 1);
 }
 
-static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] = { 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
+// ---- slot prefill (moshi_hot.h): provided frames of one or several slots as batched [dim, T] passes ------------------------------------------------
+namespace {
+// rows [row, row + n) of a pass belong to slot b, whose stream position before the pass is pos
+struct PassJob { int b, row, n; int64_t pos; T mask = nullptr, indices = nullptr; Rot rot; };
+
+// moshi_streaming_multihead_attention (attention() above) over the rows of a pass: ONE in_proj and ONE out_proj for all rows; between them job j's rows
+// of q / k / v run the single-stream op sequence against column b_j of the [D, C, H, B] rings (a [D, C, H] view), with the job's own ring slots, mask
+// block and RoPE rows, and leave their [D, H, T_j] result in rows [row_j, row_j + T_j) of one [D, H, T] tensor.
+T attention_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std::vector<PassJob> & jobs, bool rope) {
+    const int64_t H = tr.heads, D = tr.dim / tr.heads, C = tr.capacity, Tn = x->ne[1];
+    T projected = linear(c, L.in_proj[0], x);
+    const size_t row_nb = projected->nb[1], out_row = (size_t) (D * H) * 4;
+    T out = c.tensor(GGML_TYPE_F32, D, H, Tn);
+    int out_at = 0;   // the row `out` (the last job's copy, a view of the whole) starts at
+    for (const PassJob & j : jobs) {
+        auto rows = [&](size_t off) {
+            T t = ggml_cont(c, ggml_view_3d(c, projected, projected->ne[0] / 3, j.n, 1, row_nb, row_nb * (size_t) j.n, (size_t) j.row * row_nb + off));
+            t = ggml_reshape_4d(c, t, D, H, j.n, 1);
+            return ggml_permute(c, t, 0, 2, 1, 3);
+        };
+        T q = rows(0), k = rows(row_nb / 3), v = rows(row_nb * 2 / 3);
+        if (rope) apply_rope(c, q, k, j.rot);
+        T kring = ggml_view_3d(c, L.kcache, D, C, H, L.kcache->nb[1], L.kcache->nb[2], (size_t) j.b * L.kcache->nb[3]);
+        T vring = ggml_view_3d(c, L.vcache, D, C, H, L.vcache->nb[1], L.vcache->nb[2], (size_t) j.b * L.vcache->nb[3]);
+        k = ggml_set_rows(c, kring, k, j.indices);
+        v = ggml_set_rows(c, vring, v, j.indices);
+        T w = ggml_mul_mat(c, k, q);
+        w = ggml_soft_max_ext(c, w, j.mask, 1.f / sqrtf((float) D), 0.0f);
+        v = ggml_cont(c, ggml_transpose(c, v));
+        T o = ggml_mul_mat(c, v, w);
+        T dst = ggml_view_3d(c, out, D, H, j.n, (size_t) D * 4, out_row, (size_t) ((int64_t) (j.row - out_at) * (int64_t) out_row));
+        out = ggml_cpy(c, ggml_permute(c, o, 0, 2, 1, 3), dst);
+        out_at = j.row;
+    }
+    T all = ggml_view_3d(c, out, D * H, Tn, 1, out_row, out_row * (size_t) Tn, (size_t) (-(int64_t) out_at * (int64_t) out_row));
+    return linear(c, L.out_proj[0], all);
+}
+
+// transformer_layer over the rows of a pass (the Temporal stack of a B > 1 model: RMS norms, gated FFN, no cross-attention, no layer scales)
+T transformer_layer_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std::vector<PassJob> & jobs) {
+    T nx = apply_norm(c, L.norm1, x);
+    x = ggml_add(c, x, attention_jobs(c, tr, L, nx, jobs, tr.max_period != 0));
+    nx = apply_norm(c, L.norm2, x);
+    T update = gating(c, L.gate_in[0], L.gate_out[0], nx);
+    if (x->ne[1] > 1 || x->ne[2] > 1) update = ggml_reshape_3d(c, update, update->ne[0], x->ne[1], x->ne[2]);   // (transformer_layer's fold)
+    return ggml_add(c, x, update);
+}
+
+// one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
+void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames) {
+    const moshi_hot_config & c = m->cfg;
+    const int ncb = c.n_q + 1, CT = (int) m->cache.size(), C = m->temporal.capacity;
+    int Tn = 0;
+    for (const PassJob & j : jobs) Tn += j.n;
+    // host side of the provided frames (lm.h:812-817, 826-834, 933), per job: ring writes, model inputs, frame count
+    std::vector<std::vector<int32_t>> ids((size_t) ncb, std::vector<int32_t>((size_t) Tn));
+    std::vector<std::vector<float>> scales((size_t) ncb, std::vector<float>((size_t) Tn));
+    for (size_t ji = 0; ji < jobs.size(); ji++) {
+        PassJob & j = jobs[ji];
+        auto & col = m->cols[(size_t) j.b];
+        for (int t = 0; t < j.n; t++) {
+            const int32_t * tk = frames[ji] + (size_t) t * ncb;
+            for (int i = 0; i < ncb; i++) col.cache[(size_t) ((col.frames + c.delays[i]) % CT)][(size_t) i] = tk[i];
+            const int pos = (int) (col.frames % CT);
+            for (int i = 0; i < ncb; i++) {
+                const int32_t id = col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) pos][(size_t) i];
+                scales[(size_t) i][(size_t) (j.row + t)] = id == -1 ? 0.f : 1.f;
+                ids[(size_t) i][(size_t) (j.row + t)] = id < 0 ? 0 : id;
+            }
+            col.frames++;
+        }
+    }
+    PhaseTimer pt(m, 1);
+    Builder & s = *m->scratch;
+    T input = nullptr;
+    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed over Tn columns
+        T idx = s.i32s(ids[(size_t) i]);
+        T sc = s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), scales[(size_t) i].data());
+        T e = ggml_mul(s, ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[(size_t) (i - 1)], idx), sc);
+        input = input ? ggml_add(s, input, e) : e;
+    }
+    for (PassJob & j : jobs) {   // the job's mask block (causal from its position: no job passes the ring's end), ring slots and RoPE rows
+        std::vector<float> mv((size_t) C * (size_t) j.n);
+        std::vector<int32_t> idx((size_t) j.n);
+        for (int t = 0; t < j.n; t++) {
+            for (int cc = 0; cc < C; cc++) mv[(size_t) t * (size_t) C + (size_t) cc] = cc <= j.pos + t ? 0.0f : -INFINITY;
+            idx[(size_t) t] = (int32_t) ((j.pos + t) % C);
+        }
+        j.mask = s.constant(s.tensor(GGML_TYPE_F32, C, j.n), mv.data());
+        j.indices = s.i32s(idx);
+        if (m->temporal.max_period) j.rot = timestep_embedding(s, j.n, m->temporal.dim / m->temporal.heads, s.f32((float) j.pos), m->temporal.max_period);
+    }
+    T x = input;
+    for (auto & L : m->temporal.layers) x = transformer_layer_jobs(s, m->temporal, L, x, jobs);
+    for (const PassJob & j : jobs) {   // the slot's row of transformer_out as the last of its frames leaves it (lm.h:434, 847-849)
+        T last = ggml_view_2d(s, x, x->ne[0], 1, x->nb[1], (size_t) (j.row + j.n - 1) * x->nb[1]);
+        T dst = ggml_view_1d(s, m->transformer_out, x->ne[0], (size_t) j.b * m->transformer_out->nb[2]);
+        s.expand(ggml_cpy(s, apply_norm(s, m->out_norm, last), dst));
+        m->cols[(size_t) j.b].pos += j.n;
+    }
+    s.compute_scratch();
+}
+}  // namespace
+
+extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
+    if (m->kind != ModelKind::slots || n_jobs < 0 || n_jobs > m->n_streams) return -1;
+    const int ncb = m->cfg.n_q + 1;
+    int total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const moshi_hot_model::Column * s = slot(m, slots[j]);
+        if (!s || !s->open || n_frames[j] < 0 || (n_frames[j] > 0 && !tokens[j]) || s->pos + n_frames[j] > m->temporal.capacity) return -1;
+        for (int i = 0; i < j; i++) if (slots[i] == slots[j]) return -1;
+        total += n_frames[j];
+    }
+    if (!total) return 0;
+    if (chunk < 1 || chunk > 64) chunk = 64;   // the device's batched kernels take up to 64 rows per pass
+    ggml_backend_mi355x_set_capture(m->be, 0);   // same-shaped pass graphs reuse one plan; none is replayed often enough to pay for a hipGraph capture
+    std::vector<PassJob> jobs;
+    std::vector<const int32_t *> frames;
+    int rows = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        int done = 0;
+        while (done < n_frames[j]) {
+            const int Tj = n_frames[j] - done < chunk - rows ? n_frames[j] - done : chunk - rows;
+            PassJob pj; pj.b = slots[j]; pj.row = rows; pj.n = Tj; pj.pos = m->cols[(size_t) slots[j]].pos;
+            jobs.push_back(pj);
+            frames.push_back(tokens[j] + (size_t) done * ncb);
+            rows += Tj; done += Tj;
+            if (rows == chunk || (j == n_jobs - 1 && done == n_frames[j])) {
+                slots_prefill_pass(m, jobs, frames);
+                jobs.clear(); frames.clear(); rows = 0;
+            }
+        }
+    }
+    if (!jobs.empty()) slots_prefill_pass(m, jobs, frames);   // (the last jobs had no frames)
+    ggml_backend_mi355x_set_capture(m->be, 1);
+    return total;
+}
+extern "C" int moshi_hot_slot_prefill(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk) {
+    const int32_t sb = b;
+    return moshi_hot_slots_prefill(m, 1, &sb, &tokens, &n_frames, chunk);
+}
+extern "C" int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold) {
+    moshi_hot_model::Column * s = slot(m, b);
+    if (!s || !s->open) return -1;
+    s->held = hold != 0;
+    return 0;
+}
+
+static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }
 
 // the same prompt frames through moshi_hot_prefill: identical state afterwards, a fraction of the time
