@@ -122,6 +122,8 @@ struct ggml_mi355x_stats {
     int64_t attn_block_launches_in_last_plan;   // k_attn_blocks launches of the last plan (slot prefill: a write and an attend launch per layer of a pass) ...
     int64_t attn_block_jobs_in_last_plan;       // ... and the attention blocks (jobs) they hold, summed over the launch pairs
     int64_t generic_attention_nodes_in_last_plan;   // soft_max / set_rows nodes of the last plan that run as generic launches
+    int64_t ring_copy_launches_in_last_plan;    // k_ring_copy launches of the last plan (slot snapshots: every ring copy of a fork, a save or a load in one launch) ...
+    int64_t ring_copy_jobs_in_last_plan;        // ... and the cpy nodes (jobs) they hold
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

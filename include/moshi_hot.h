@@ -151,6 +151,26 @@ GGML_API int moshi_hot_slot_prefill(moshi_hot_model_t * m, int b, const int32_t 
 // it) and reports status -2 with outputs -1 - a long history can be prefilled one pass at a time between the frames of the live slots. hold == 0
 // releases it; moshi_hot_slot_open / _close clear the hold. Returns 0, or -1 for a bad index, a closed slot or a model that is not a slots model.
 GGML_API int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold);
+// Slot snapshots: fork, save and restore a conversation without recomputing it. A conversation's state is its column record (delay ring, frame count,
+// stream position), its sampling setting with the seeded flag, its row of transformer_out and the LIVE rows of its column of every Temporal K and V ring:
+// ring rows 0 .. n - 1 of every head with n = min(position, context) - before the wrap the mask admits no other row, after it all of them. The Depth rings
+// start afresh every frame (the chained Depth graph rewrites every row it reads) and carry nothing between frames: they are not part of a snapshot.
+// A snapshot works at any position, past the ring's end included (where moshi_hot_slots_prefill refuses), costs one copy of those rows instead of a
+// recomputation, and the restored or forked slot continues bit for bit - sampled conversations included, which prefill cannot reproduce. The calls block;
+// no other slot's rings, delay ring, position, hold or sampling state is touched. Each returns -1 and changes nothing on a model that is not a slots
+// model, for a bad index, and where a slot is not in the state the call requires.
+//  * fork: src open (a held slot counts as open), dst closed and != src. Afterwards dst is open, not held, and holds a copy of src's state: fed the same
+//    codes both slots produce the same conversation. A caller that wants sampled branches to diverge sets a new seed on dst (moshi_hot_set_sampling).
+//  * save: slot b open. Writes a self-describing blob - a magic, a format version, a fingerprint of the configuration (dim, heads, layers, context, n_q,
+//    dep_q, card, text_card, the delays, the ring type BF16, sampled or greedy), the host state, transformer_out, then per layer K and then V as
+//    H x n x D BF16 - and returns the bytes written; buf == NULL: the bytes needed now (they grow with the position until the ring is full). -1 when
+//    nbytes is too small. The slot is unchanged.
+//  * load: slot b closed; nbytes must be the blob's exact size (a truncated or oversized buffer is refused, as are a wrong magic, version or
+//    fingerprint). The blob may come from any column of a slots model of any B on any backend with the same fingerprint. Afterwards the slot is open,
+//    not held, and holds that conversation, its sampling setting included.
+GGML_API int     moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst);
+GGML_API int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes);
+GGML_API int     moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes);
 
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute

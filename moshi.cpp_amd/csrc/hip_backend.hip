@@ -337,7 +337,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -1148,6 +1148,59 @@ static bool match_row_copies(const analysis & an, int pos, row_copy_group & grp)
     return true;
 }
 
+// B''''. slot snapshots (moshi_hot.cpp slot_state_graph): a run of cpy(a, b) of one type between [D, n, H] row-range views - each head one contiguous run
+//      of n x D elements on both sides - at least one side inside ONE column of a [D, C, H, B] ring (B > 1), with nothing but layout nodes between the
+//      copies: one k_ring_copy launch for up to RING_COPY_MAX of them. A copy whose bases, head strides or run length are no multiples of 16 bytes, whose
+//      ranges overlap, or that touches what an earlier job of the run writes (or writes what one reads) is declined and stays a generic copy.
+struct ring_copy_group { ring_copy_args a; int emit_pos; std::vector<int> members; };
+struct byte_range { const char * lo, * hi; bool overlaps(const byte_range & o) const { return lo < o.hi && o.lo < hi; } };
+// t as H runs of contiguous bytes inside its root tensor: base, head stride, run length and the range they span
+static bool ring_copy_side(const ggml_tensor * t, const char ** base, int64_t * hs, int64_t * run, byte_range * span, bool * ring_column) {
+    const int64_t es = (int64_t) ggml_type_size(t->type);
+    if (!t->data || ggml_is_quantized(t->type) || t->ne[3] != 1 || (int64_t) t->nb[0] != es || (int64_t) t->nb[1] != t->ne[0] * es) return false;
+    const ggml_tensor * root = t;
+    while (root->view_src) root = root->view_src;
+    *base = (const char *) t->data; *hs = (int64_t) t->nb[2]; *run = t->ne[0] * t->ne[1] * es;
+    if (*hs < *run) return false;
+    span->lo = *base; span->hi = *base + (t->ne[2] - 1) * *hs + *run;
+    if (!root->data || span->lo < (const char *) root->data || span->hi > (const char *) root->data + ggml_nbytes(root)) return false;
+    // inside one column of a B-column ring?
+    *ring_column = false;
+    if (root != t && root->ne[3] > 1 && root->nb[3] > 0) {
+        const int64_t off = span->lo - (const char *) root->data, col = off / (int64_t) root->nb[3];
+        *ring_column = span->hi <= (const char *) root->data + (col + 1) * (int64_t) root->nb[3];
+    }
+    return ((uintptr_t) *base | (uintptr_t) *hs | (uintptr_t) *run) % 16 == 0;
+}
+static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & grp) {
+    const ggml_cgraph * g = an.g;
+    memset(&grp.a, 0, sizeof(grp.a));
+    grp.members.clear();
+    std::vector<byte_range> reads, writes;
+    for (int i = pos; i < g->n_nodes && grp.a.n_jobs < RING_COPY_MAX; i++) {
+        const ggml_tensor * cp = g->nodes[i];
+        if (is_view_op(cp->op) && !an.skip[(size_t) i]) continue;   // (the views that feed the next copy)
+        if (cp->op != GGML_OP_CPY || an.skip[(size_t) i] || uses_of(an, cp) != 0) break;
+        const ggml_tensor * a = cp->src[0];
+        if (a->type != cp->type || a->ne[0] != cp->ne[0] || a->ne[1] != cp->ne[1] || a->ne[2] != cp->ne[2] || cp->ne[2] < 2) break;
+        ring_copy_job jb; int64_t run_a = 0, run_b = 0; byte_range ra, rb; bool col_a = false, col_b = false; const char * dst = nullptr;
+        if (!ring_copy_side(a, &jb.src, &jb.src_hs, &run_a, &ra, &col_a) || !ring_copy_side(cp, &dst, &jb.dst_hs, &run_b, &rb, &col_b)) break;
+        if (run_a != run_b || !(col_a || col_b) || ra.overlaps(rb)) break;
+        if (grp.a.n_jobs && (cp->ne[2] != grp.a.H || run_a != grp.a.run_bytes)) break;
+        bool hazard = false;
+        for (const byte_range & w : writes) if (w.overlaps(ra) || w.overlaps(rb)) hazard = true;
+        for (const byte_range & r : reads) if (r.overlaps(rb)) hazard = true;
+        if (hazard) break;
+        jb.dst = (char *) dst;
+        grp.a.H = (int) cp->ne[2]; grp.a.run_bytes = run_a;
+        grp.a.job[grp.a.n_jobs++] = jb;
+        reads.push_back(ra); writes.push_back(rb);
+        grp.members.push_back(i);
+        grp.emit_pos = i;
+    }
+    return grp.a.n_jobs > 0;
+}
+
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
 //     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue
 struct bmm_group { int emit_pos; std::vector<int> members; std::function<void(hipStream_t)> run; };
@@ -1901,6 +1954,16 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
     static const bool no_attn_prologue = getenv("MI355X_NO_ATTN_PROLOGUE") != nullptr;
     static const bool no_argmax_epilogue = getenv("MI355X_NO_ARGMAX_EPILOGUE") != nullptr;
     if (fuse) {
+        // slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp slot_state_graph) - one launch for the whole run
+        for (int i = 0; i < g->n_nodes; i++) {
+            ring_copy_group rg;
+            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_CPY || !match_ring_copies(an, i, rg)) continue;
+            for (int m : rg.members) an.skip[(size_t) m] = 1;
+            const ring_copy_args ra = rg.a; const int cus = c->usable_cus;
+            at_pos[rg.emit_pos].push_back([=](hipStream_t s) { k_ring_copy(s, ra, cus); });
+            p->n_fused += (int) rg.members.size();
+            p->n_ring_copy_launches++; p->n_ring_copy_jobs += ra.n_jobs;
+        }
         // attention blocks first (they swallow set_rows / soft_max / two mul_mats); emitted after the mat-vec pass, which may
         // absorb a short-ring attention into the projection that consumes it
         for (int i = 0; i < g->n_nodes; i++) {
@@ -2490,6 +2553,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
         c->stats.fused_nodes_in_last_plan = p->n_fused;
         c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
         c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
+        c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
         plan_free(c, p);   // workspaces return to the pool; reuse is stream-ordered
         return GGML_STATUS_SUCCESS;
     }
@@ -2530,6 +2594,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
     c->stats.fused_nodes_in_last_plan = p->n_fused;
     c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
     c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
+    c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
     return GGML_STATUS_SUCCESS;
 }
 

@@ -216,6 +216,15 @@ void k_attn_blocks(hipStream_t s, const attn_blocks_args & a, unsigned * err = n
 #define COPY_ROWS_MAX 16
 struct copy_rows_args { const float * src[COPY_ROWS_MAX]; float * dst; int64_t n; int rows; };
 void k_copy_rows(hipStream_t s, const copy_rows_args & a);
+// Slot snapshots (moshi_hot_slot_fork / _save / _load): a run of same-type copies between [D, n, H] row-range views - ring rows [0, n) of every head
+// of one column of a [D, C, H, B] ring, or a contiguous staging tensor - as ONE launch. Job j = one cpy node: H runs of run_bytes = n x D x type size
+// contiguous bytes, run h at src + h * src_hs -> dst + h * dst_hs. The jobs of a launch share H and run_bytes; every base, stride and run is a multiple
+// of 16 bytes and no job's destination overlaps another job's source or destination (match_ring_copies declines anything else). The table goes by
+// value in the kernel arguments (64 x 32 bytes); a longer run of copies takes several launches. blocks_per_run is k_ring_copy's to choose.
+#define RING_COPY_MAX 64
+struct ring_copy_job { const char * src; char * dst; int64_t src_hs, dst_hs; };
+struct ring_copy_args { int n_jobs, H; int64_t run_bytes; int blocks_per_run; ring_copy_job job[RING_COPY_MAX]; };
+void k_ring_copy(hipStream_t s, const ring_copy_args & a, int usable_cus);
 
 // in_proj + the attention that consumes it as ONE launch of 256 resident workgroups (inproj_attn_kernel): `a` is the RMS-normed Q4_K mat-vec whose output
 // holds `at`'s q | k | v. supported(): shapes, and whether the whole grid fits the compute units the stream may use (the parts of a head wait for each

@@ -1862,6 +1862,42 @@ void k_copy_rows(hipStream_t s, const copy_rows_args & a) {
     copy_rows_kernel<<<grid, 256, 0, s>>>(a);
 }
 
+// Slot snapshots (moshi_hot_slot_fork / _save / _load): every K / V ring copy of one snapshot as ONE launch. Job j copies H runs of run_bytes contiguous
+// bytes (ring rows [0, n) of one head of one ring column, or the same rows in a contiguous staging tensor): run h from src + h * src_hs to
+// dst + h * dst_hs. A pure HBM stream: each run is cut into blocks_per_run pieces of whole 16-byte vectors, one workgroup per piece, a lane moving
+// 16 bytes per load and store (64 lanes = 1 KiB per wave instruction), four loads in flight per lane before the first store. Job and head are functions
+// of blockIdx alone, so the table entry arrives through scalar kernel-argument loads. Every offset is 64 bit (column 15 of a moshika ring starts 370 MB
+// into its tensor, a run at fill 2 800 is 700 KB). The planner guarantees 16-byte alignment of every base, stride and run, and disjoint ranges.
+__global__ void __launch_bounds__(256) ring_copy_kernel(ring_copy_args a) {
+    const int bpr = a.blocks_per_run;
+    const int run = (int) blockIdx.x / bpr, part = (int) blockIdx.x % bpr;
+    const int j = run / a.H, h = run % a.H;
+    const ring_copy_job & jb = a.job[j];
+    const uint4 * __restrict__ src = (const uint4 *) (jb.src + (int64_t) h * jb.src_hs);
+    uint4 * __restrict__ dst = (uint4 *) (jb.dst + (int64_t) h * jb.dst_hs);
+    const int64_t nvec = a.run_bytes >> 4, per = (nvec + bpr - 1) / bpr;
+    const int64_t begin = (int64_t) part * per, end = begin + per < nvec ? begin + per : nvec;
+    int64_t i = begin + threadIdx.x;
+    for (; i + 3 * 256 < end; i += 4 * 256) {
+        const uint4 v0 = src[i], v1 = src[i + 256], v2 = src[i + 512], v3 = src[i + 768];
+        dst[i] = v0; dst[i + 256] = v1; dst[i + 512] = v2; dst[i + 768] = v3;
+    }
+    for (; i < end; i += 256) dst[i] = src[i];
+}
+void k_ring_copy(hipStream_t s, const ring_copy_args & in, int usable_cus) {
+    GGML_ASSERT(in.n_jobs >= 1 && in.n_jobs <= RING_COPY_MAX && in.H >= 1 && in.run_bytes >= 16 && in.run_bytes % 16 == 0);
+    ring_copy_args a = in;
+    // eight workgroups per compute unit keep every unit streaming at a long fill; a piece is never shorter than 16 KB (four 16-byte vectors per lane), so a
+    // short run (n = 1: 256 bytes) is one workgroup, not split further
+    const int64_t runs = (int64_t) a.n_jobs * a.H, target = 8 * (int64_t) (usable_cus > 0 ? usable_cus : 256);
+    int64_t bpr = (target + runs - 1) / runs;
+    const int64_t most = (a.run_bytes + 16383) / 16384;
+    if (bpr > most) bpr = most;
+    if (bpr < 1) bpr = 1;
+    a.blocks_per_run = (int) bpr;
+    ring_copy_kernel<<<(unsigned) (runs * bpr), 256, 0, s>>>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // merged launches of the Temporal layer: shared definitions (the kernel itself: inproj_attn_kernel below)
 // ---------------------------------------------------------------------------------------------------

@@ -2528,6 +2528,132 @@ extern "C" int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold) {
     return 0;
 }
 
+// ---- slot snapshots (moshi_hot.h): fork, save and load a conversation's state without recomputing it ------------------------------------------------
+namespace {
+// The blob: this header, the delay ring (ring_rows x ring_cols int32, row-major), transformer_out (dim F32), zero padding to a multiple of 16 bytes,
+// then per Temporal layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous).
+struct SlotBlobHeader {
+    uint32_t magic, version;
+    uint64_t fingerprint;
+    int64_t total_bytes, frames, pos, n_rows;   // n_rows = min(pos, context): the live ring rows
+    int32_t ring_rows, ring_cols, seeded, reserved;
+    moshi_hot_sampling sampling;
+};
+const uint32_t SLOT_BLOB_MAGIC = 0x544C534Du, SLOT_BLOB_VERSION = 1;   // "MSLT"
+static_assert(sizeof(SlotBlobHeader) == 88, "the blob header has no padding");
+
+// FNV-1a over what a blob's bytes depend on: a blob only loads into a model that would have laid the same conversation out the same way
+uint64_t slot_fingerprint(const moshi_hot_model * m) {
+    const moshi_hot_config & c = m->cfg;
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&](int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; };
+    mix(c.dim); mix(c.num_heads); mix(c.num_layers); mix(c.context); mix(c.n_q); mix(c.dep_q); mix(c.card); mix(c.text_card);
+    for (int i = 0; i <= c.n_q; i++) mix(c.delays[i]);
+    mix(m->temporal.layers[0].kcache->type);
+    mix(sampled_model(m) ? 1 : 0);
+    return h;
+}
+int64_t slot_host_bytes(const moshi_hot_model * m) {   // everything in front of the ring rows
+    const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->cache.size() * (m->cfg.n_q + 1) * 4 + (int64_t) m->cfg.dim * 4;
+    return (n + 15) / 16 * 16;
+}
+int64_t slot_ring_bytes(const moshi_hot_model * m, int64_t n_rows) {
+    return 2 * (int64_t) m->temporal.layers.size() * (int64_t) m->cfg.dim * n_rows * 2;   // 2 x layers x H x n x D BF16
+}
+int64_t slot_live_rows(const moshi_hot_model * m, const moshi_hot_model::Column & col) { return col.pos < m->temporal.capacity ? col.pos : m->temporal.capacity; }
+
+// The device half as ONE scratch graph: per Temporal layer a cpy of K and a cpy of V between [D, n, H] views - ring rows [0, n) of every head of column
+// src (src < 0: of a contiguous BF16 staging tensor [D, n, H, 2 L], uploaded from rings_in first) into the same rows of column dst (dst < 0: into the
+// staging tensor, read back to rings_out) - and the row copy of transformer_out (staged through an F32[dim] tensor likewise). The device plan turns the
+// ring copies into one launch (hip_backend.hip match_ring_copies); the oracle and a plan without fusion run them as the generic strided copies they are.
+void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * tout_in, const void * rings_in, void * tout_out, void * rings_out) {
+    Builder & s = *m->scratch;
+    const Transformer & tr = m->temporal;
+    const int64_t dim = m->cfg.dim, H = tr.heads, D = dim / H;
+    const bool staged = src < 0 || dst < 0;
+    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
+    T tout_stage = staged ? s.tensor(GGML_TYPE_F32, dim) : nullptr;
+    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
+    auto tout_row = [&](int b) { return ggml_view_1d(s, m->transformer_out, dim, (size_t) b * m->transformer_out->nb[2]); };
+    int64_t j = 0;
+    if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
+        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
+        j++;
+        s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
+    }
+    s.expand(ggml_cpy(s, src >= 0 ? tout_row(src) : tout_stage, dst >= 0 ? tout_row(dst) : tout_stage));
+    ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph: a repeated fork of the same pair must not pay for a hipGraph capture
+    s.alloc();
+    if (src < 0) {
+        ggml_backend_tensor_set(tout_stage, tout_in, 0, (size_t) dim * 4);
+        if (stage) ggml_backend_tensor_set(stage, rings_in, 0, ggml_nbytes(stage));
+    }
+    s.compute();
+    if (dst < 0) {
+        ggml_backend_tensor_get(tout_stage, tout_out, 0, (size_t) dim * 4);
+        if (stage) ggml_backend_tensor_get(stage, rings_out, 0, ggml_nbytes(stage));
+    }
+    ggml_backend_synchronize(m->be);   // the calls block
+    s.release_scratch();
+    ggml_backend_mi355x_set_capture(m->be, 1);
+}
+}  // namespace
+
+extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) {
+    moshi_hot_model::Column * a = slot(m, src), * b = slot(m, dst);
+    if (!a || !b || src == dst || !a->open || b->open) return -1;
+    slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr);
+    *b = *a;
+    b->held = false;
+    m->sampling[(size_t) dst] = m->sampling[(size_t) src];
+    m->sampling_dirty = true;
+    return 0;
+}
+
+extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) {
+    const moshi_hot_model::Column * col = slot(m, b);
+    if (!col || !col->open || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m), total = host + slot_ring_bytes(m, n);
+    if (!buf) return total;
+    if (nbytes < total) return -1;
+    uint8_t * out = (uint8_t *) buf;
+    memset(out, 0, (size_t) host);
+    SlotBlobHeader h;
+    memset(&h, 0, sizeof(h));
+    h.magic = SLOT_BLOB_MAGIC; h.version = SLOT_BLOB_VERSION; h.fingerprint = slot_fingerprint(m);
+    h.total_bytes = total; h.frames = col->frames; h.pos = col->pos; h.n_rows = n;
+    h.ring_rows = (int32_t) col->cache.size(); h.ring_cols = m->cfg.n_q + 1;
+    h.seeded = m->sampling[(size_t) b].seeded ? 1 : 0; h.sampling = m->sampling[(size_t) b].s;
+    memcpy(out, &h, sizeof(h));
+    int32_t * ring = (int32_t *) (out + sizeof(h));
+    for (const auto & row : col->cache) for (int v : row) *ring++ = v;
+    slot_state_graph(m, b, -1, n, nullptr, nullptr, ring, out + host);
+    return total;
+}
+
+extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) {
+    moshi_hot_model::Column * col = slot(m, b);
+    if (!col || col->open || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    const uint8_t * in = (const uint8_t *) buf;
+    SlotBlobHeader h;
+    memcpy(&h, in, sizeof(h));
+    const moshi_hot_config & c = m->cfg;
+    const int64_t host = slot_host_bytes(m), C = m->temporal.capacity;
+    if (h.magic != SLOT_BLOB_MAGIC || h.version != SLOT_BLOB_VERSION || h.fingerprint != slot_fingerprint(m)) return -1;
+    if (h.pos < 0 || h.frames < 0 || h.n_rows != (h.pos < C ? h.pos : C) || h.ring_rows != (int32_t) m->cache.size() || h.ring_cols != c.n_q + 1) return -1;
+    if (h.total_bytes != host + slot_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
+    const moshi_hot_sampling & sp = h.sampling;
+    if (sampled_model(m) && (!(sp.temp > 0.f) || !(sp.temp_text > 0.f) || sp.top_k < 1 || sp.top_k > c.top_k || sp.top_k_text < 1 || sp.top_k_text > c.top_k_text)) return -1;
+    const int32_t * ring = (const int32_t *) (in + sizeof(h));
+    slot_state_graph(m, -1, b, h.n_rows, ring + (size_t) h.ring_rows * (size_t) h.ring_cols, in + host, nullptr, nullptr);
+    *col = { m->cache, h.frames, h.pos, true };
+    for (auto & row : col->cache) for (int & v : row) v = *ring++;
+    m->sampling[(size_t) b] = { sp, h.seeded != 0 && sampled_model(m) };
+    if (m->sampling[(size_t) b].seeded) m->any_seeded = true;
+    m->sampling_dirty = true;
+    return 0;
+}
+
 static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }
 

@@ -72,6 +72,9 @@ SIGNATURES = {
     "moshi_hot_slots_prefill": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "moshi_hot_slot_prefill": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
     "moshi_hot_slot_hold": (C.c_int, [P, C.c_int, C.c_int]),
+    "moshi_hot_slot_fork": (C.c_int, [P, C.c_int, C.c_int]),
+    "moshi_hot_slot_save": (C.c_int64, [P, C.c_int, P, C.c_int64]),
+    "moshi_hot_slot_load": (C.c_int, [P, C.c_int, P, C.c_int64]),
     "moshi_hot_set_sampling": (C.c_int, [P, C.c_int, P]),
     "moshi_hot_get_sampling": (C.c_int, [P, C.c_int, P, P]),
     "moshi_hot_sampling_noise": (None, [C.c_uint64, C.c_int64, C.c_int, C.c_int, P]),
