@@ -273,6 +273,7 @@ GGML_API void    moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offse
 // write the same pseudo-random BF16 rows (approximately N(0, scale^2), a function of seed / which / layer / position only) into EVERY slot of the K and V
 // rings (transformer.h:156-172) of one layer (layer >= 0) or of all layers (-1) of the Temporal (which = 0) or Depth (1) transformer: two executors
 // filled alike hold identical caches, so attention over hundreds or thousands of live slots can be compared node by node (tests only)
+GGML_API void    moshi_hot_fill_ring(moshi_hot_model_t * m, int which, int layer, uint64_t seed, float scale);
 // the reference's checkpoint path end to end (src/loader.h:85-99, 227-271): write every weight tensor of a model to a GGUF file / build a model whose
 // weights are read back from such a file (names, types and sizes checked against the configuration) instead of being generated
 GGML_API int     moshi_hot_save_gguf(moshi_hot_model_t * m, const char * path);
@@ -282,7 +283,6 @@ GGML_API moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, 
 GGML_API int     moshi_hot_tensor_file_name(const char * checkpoint_name, char * out, int n);
 // test hook: the host-side delay ring (rows x (n_q + 1) int32, row-major) -> dst; returns the value count (dst NULL: just the count)
 GGML_API int     moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max_values);
-GGML_API void    moshi_hot_fill_ring(moshi_hot_model_t * m, int which, int layer, uint64_t seed, float scale);
 // the K (kv = 0) / V (kv = 1) ring of one layer as its bytes (BF16 [D, C, H]), read out (write = 0) or overwritten (write = 1): parity runs that restart every
 // frame from another executor's state. Returns the ring's size in bytes (-1: no such ring); buf may be NULL to ask for the size. which: 0 Temporal, 1 Depth.
 GGML_API int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int layer, int kv, void * buf, int64_t nbytes, int write);

@@ -7,6 +7,7 @@
 // matchers key on and what the oracle executes node by node); the C++ around them is this project's own.
 // Weights are synthetic and deterministic (no model files can reach the build or the GPU box).
 #include "moshi_hot.h"
+#include "delay_ring.h"
 #include "gguf.h"
 #include "ggml-cpu.h"
 
@@ -848,13 +849,13 @@ struct moshi_hot_model {
     Transformer temporal_tp; T tp_x = nullptr, tp_msg = nullptr; std::vector<Builder *> g_tp;
     // tensor-parallel FRAME mode (moshi_hot_tp_install): the Temporal half of an LM step = embedding-sum graph -> broadcast of x -> the stack above -> head graph
     bool tp_frame = false; T tp_in = nullptr; Builder * g_tp_pre = nullptr, * g_tp_import = nullptr, * g_tp_post = nullptr; int64_t tp_frames = 0;
-    // delay ring (lm.h:715-743)
-    int offset = 0; std::vector<std::vector<int>> cache; std::vector<int> initial; int max_delay = 0;
+    // delay ring (delay_ring.h): the configuration's constants; the ring of a single-stream model (a B > 1 model's stays unbound: its rings are the columns')
+    DelayProtocol proto; DelayRing ring;
     // B > 1 (moshi_hot_create_streams / moshi_hot_create_slots): B = the batch dimension of every LM activation and KV ring, one conversation per
-    // column. A column holds its delay ring, the frames stepped since it opened (the ring's offset) and its stream position (mask row, RoPE phase,
-    // ring slot; moshi_hot_set_context_fill / moshi_hot_slot_set_fill move it alone). Lockstep: every column open from creation, all at one position
-    // and advanced together. Slots: each column opened, closed and positioned on its own; a closed column keeps its frame count and position.
-    struct Column { std::vector<std::vector<int>> cache; int64_t frames = 0, pos = 0; bool open = false, held = false; };   // held: moshi_hot_slot_hold
+    // column. A column holds its delay ring (with the frames stepped since it opened) and its stream position pos (mask row, RoPE phase, ring slot;
+    // moshi_hot_set_context_fill / moshi_hot_slot_set_fill move it alone): the B > 1 counterpart of temporal.offset, which these models do not use.
+    // Lockstep: all columns open from creation, at one position, advanced together. Slots: each opened, closed and positioned on its own; a closed one keeps its frame count and position.
+    struct Column { DelayRing ring; int64_t pos = 0; bool open = false, held = false; };   // held: moshi_hot_slot_hold
     int n_streams = 1; ModelKind kind = ModelKind::single; std::vector<Column> cols;
     // per-conversation sampling (moshi_hot_set_sampling): one entry per column (one for a single-stream model), the configuration's values until set.
     // A B > 1 sampled model's graphs take 1.f / temp of every column as inputs (inv_temp_text in the Temporal graph, inv_temp in the Depth graph),
@@ -883,7 +884,7 @@ struct moshi_hot_model {
     bool timing = false; double phase_us[4] = { 0, 0, 0, 0 }; int64_t phase_n[4] = { 0, 0, 0, 0 };
 };
 
-// the single-stream calls on a lockstep-streams model (moshi_hot_create_streams, n_streams > 1): refused (moshi_hot.h lists the return values)
+// the single-stream calls on a B > 1 model (moshi_hot_create_streams with n_streams > 1, moshi_hot_create_slots): refused (moshi_hot.h lists the return values)
 #define STREAMS_REFUSE(ret) do { if (m->n_streams > 1) return ret; } while (0)
 
 namespace {
@@ -1233,7 +1234,7 @@ static moshi_hot_model::Column * slot(moshi_hot_model_t * m, int b) {
 extern "C" int moshi_hot_slot_open(moshi_hot_model_t * m, int b) {
     moshi_hot_model::Column * s = slot(m, b);
     if (!s) return -1;
-    *s = { m->cache, 0, 0, true };   // a fresh stream's delay ring (create_model's: -2 everywhere) at stream position 0
+    s->ring.reset(); s->pos = 0; s->open = true; s->held = false;   // a fresh stream's delay ring at stream position 0
     return 0;
 }
 extern "C" int moshi_hot_slot_close(moshi_hot_model_t * m, int b) {
@@ -1306,7 +1307,7 @@ void stage_sampling(moshi_hot_model * m) {
         NoiseColumn & nc = cols[(size_t) b];
         nc.seeded = sp.seeded; nc.seed = sp.s.seed; nc.top_k = sp.s.top_k; nc.top_k_text = sp.s.top_k_text;
         nc.open = B > 1 ? m->cols[(size_t) b].open && !m->cols[(size_t) b].held : true;   // (a held slot is stepped as a closed one)
-        nc.frame = B > 1 ? m->cols[(size_t) b].frames : (int64_t) m->offset;
+        nc.frame = B > 1 ? m->cols[(size_t) b].ring.frames : m->ring.frames;
     }
     if (m->g_temporal) m->g_temporal->noise_cols = cols;
     if (m->g_depth) m->g_depth->noise_cols = cols;
@@ -1450,12 +1451,14 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
             }
         }
         // moshi_lmgen_state (lm.h:722-743)
-        const int ncb = c.n_q + 1;
-        for (int i = 0; i < ncb; i++) if (c.delays[i] > m->max_delay) m->max_delay = c.delays[i];
-        m->cache.assign((size_t) (m->max_delay + 2 + (c.personaplex ? 1 : 0)), std::vector<int>((size_t) ncb, -2));
-        m->initial.assign((size_t) ncb, c.card);
-        m->initial[0] = c.text_card;
-        if (m->n_streams > 1) m->cols.assign((size_t) m->n_streams, { m->cache, 0, 0, kind == ModelKind::lockstep });
+        DelayProtocol & p = m->proto;
+        p.n_q = c.n_q; p.dep_q = c.dep_q; p.io_dep_q = c.personaplex ? 8 : c.dep_q;   // lm.h:802-805
+        p.delays.assign(c.delays, c.delays + p.cols());
+        for (int d : p.delays) if (d > p.max_delay) p.max_delay = d;
+        p.rows = p.max_delay + 2 + (c.personaplex ? 1 : 0);
+        p.initial.assign((size_t) p.cols(), c.card); p.initial[0] = c.text_card;
+        DelayRing fresh; fresh.p = &p; fresh.reset();
+        if (m->n_streams > 1) m->cols.assign((size_t) m->n_streams, { fresh, 0, kind == ModelKind::lockstep }); else m->ring = fresh;
     }
     if (c.enable_mimi_decoder || c.enable_mimi_encoder) {
         W.part = c.enable_mimi_decoder ? 3 : 2;
@@ -1953,40 +1956,21 @@ extern "C" int64_t moshi_hot_depth_shard_serve(moshi_hot_model_t * m) { STREAMS_
 }
 extern "C" int moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max_values) { STREAMS_REFUSE(-1);
     // the host-side delay ring of moshi_lmgen (lm.h:819-824, 935-943), row-major [rows][n_q + 1]; returns the number of values (0 when dst is too small)
-    const int rows = (int) m->cache.size(), cols = rows ? (int) m->cache[0].size() : 0;
-    if (!dst || rows * cols > max_values) return dst ? 0 : rows * cols;
-    for (int r = 0; r < rows; r++) for (int q = 0; q < cols; q++) dst[r * cols + q] = m->cache[(size_t) r][(size_t) q];
-    return rows * cols;
+    const int n = (int) m->ring.rows.size();
+    if (dst && n <= max_values) m->ring.export_rows(dst);
+    return !dst || n <= max_values ? n : 0;
 }
 extern "C" void moshi_hot_set_depth_hook(moshi_hot_model_t * m, moshi_hot_depth_hook_t fn, void * user) { STREAMS_REFUSE(); m->depth_hook = fn; m->depth_hook_user = user; }
 
 namespace {
 // the half of moshi_lmgen_step that follows the sampling (lm.h:930-979): ring write, stream position, delayed read-out
 int lm_finish(moshi_hot_model * m, int32_t text_token, std::vector<int32_t> audio, bool provided, bool replace, int32_t * text_token_out, int32_t * out_audio, float * vad, bool newer_step_queued = false) {
-    const moshi_hot_config & c = m->cfg;
-    const int CT = (int) m->cache.size();
-    const int dep_q = c.personaplex ? 8 : c.dep_q, dep_q_1 = dep_q + 1;
     m->last_text = text_token; m->last_audio = audio;
-    m->offset++;
-    if (!provided) {                      // lm.h:935-943
-        const int wpos = m->offset % CT;
-        m->cache[(size_t) wpos][0] = text_token;
-        for (int q = 0; q < c.dep_q; q++) {
-            // Run-ahead: the NEXT step has already been queued and has put the other speaker's delay-0 codes into this very row (lm.h:819-824); in the
-            // serial order this write comes first and those codes land on top of it. Leave them: the ring then holds what the serial loop's holds.
-            if (newer_step_queued && q + 1 >= dep_q_1 && c.delays[q + 1] == 0) continue;
-            m->cache[(size_t) wpos][(size_t) (q + 1)] = audio[(size_t) q];
-        }
-    }
-    if (m->offset <= m->max_delay || replace) return 0;       // lm.h:950
-    int idx = (m->offset - m->max_delay + c.delays[0]) % CT;   // lm.h:954-959
-    *text_token_out = m->cache[(size_t) idx][0];
-    for (int i = 1; i < dep_q_1; i++) {
-        idx = (m->offset - m->max_delay + c.delays[i]) % CT;
-        audio[(size_t) (i - 1)] = m->cache[(size_t) idx][(size_t) i];
-    }
-    for (int i = 0; i < dep_q; i++) out_audio[i] = audio[(size_t) i];
-    for (int32_t x : audio) if (x == -1) return 0;             // all lm->dep_q entries, the tail holding this frame's raw samples (lm.h:961-964)
+    m->ring.commit(text_token, audio.data(), provided, newer_step_queued);
+    const DelayRing::ReadOut r = replace ? DelayRing::ReadOut::filling : m->ring.read_out(text_token_out, audio.data());
+    if (r == DelayRing::ReadOut::filling) return 0;            // lm.h:950
+    for (int i = 0; i < m->proto.io_dep_q; i++) out_audio[i] = audio[(size_t) i];
+    if (r != DelayRing::ReadOut::valid) return 0;
     if (vad) {                                                 // lm.h:966-976
         if (m->extra_heads.size() > 2) {
             Builder & s = *m->scratch;
@@ -2003,22 +1987,12 @@ namespace { void lm_finish_entry(moshi_hot_model * m, moshi_hot_model::InFlight 
 extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens, int n_tokens, int32_t * text_token_out, int32_t * out_audio, float * vad) { STREAMS_REFUSE(-1);
     for (auto & o : m->inflight) lm_finish_entry(m, o);   // a blocking step behind run-ahead ones: those finish first (their results stay parked for lm_complete)
     const moshi_hot_config & c = m->cfg;
-    const int ncb = c.n_q + 1, CT = (int) m->cache.size();
-    const int dep_q = c.personaplex ? 8 : c.dep_q, dep_q_1 = dep_q + 1;   // lm.h:802-805
-    const int needed = ncb - dep_q - 1;
-    bool provided = false;
-    if (needed > 0) {
-        if (n_tokens == ncb) {           // every codebook given: prompt frames (lm.h:812-817)
-            for (int i = 0; i < ncb; i++) m->cache[(size_t) ((m->offset + c.delays[i]) % CT)][(size_t) i] = tokens[i];
-            provided = true;
-        } else {                         // other speaker's codes enter the delay ring (lm.h:819-824)
-            GGML_ASSERT(n_tokens >= needed);
-            for (int i = 0; i < needed; i++) m->cache[(size_t) ((m->offset + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = tokens[i];
-        }
-    }
-    const int pos = m->offset % CT;
-    std::vector<int> input((size_t) ncb);
-    for (int i = 0; i < ncb; i++) input[(size_t) i] = m->offset <= c.delays[i] ? m->initial[(size_t) i] : m->cache[(size_t) pos][(size_t) i];
+    DelayRing & ring = m->ring;
+    const int ncb = c.n_q + 1, needed = m->proto.needed();
+    const int offset = (int) ring.frames;   // this frame's index, for the hooks and delay_steps
+    const bool provided = needed > 0 && n_tokens == ncb;   // every codebook given: prompt frames
+    if (provided) ring.feed_provided(tokens);
+    else if (needed > 0) { GGML_ASSERT(n_tokens >= needed); ring.feed_user(tokens, ring.frames); }   // other speaker's codes
 
     if (m->tp_frame) tp_build_frame_graphs(m);
     else if (!m->g_temporal) build_temporal_graph(m);
@@ -2028,14 +2002,12 @@ extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens
     GGML_ASSERT(!(c.chain_depth && (m->text_hook || m->depth_hook)) && "chain_depth: the text token never visits the host between the two graphs");
     {
     PhaseTimer pt(m, 1);
-    // moshi_lmmodel_text_token_embed_step (lm.h:586-607): -1 -> scale 0, negative ids -> row 0
     for (int i = 0; i < ncb; i++) {
-        int32_t id = input[(size_t) i];
+        const int32_t id = ring.input(i, ring.frames);
         if (i == 0 && c.demux_second_stream) { demux_set(c, id, m->emb_idx[0], m->emb_right_idx, m->emb_right_scale); continue; }
-        const float sc = id == -1 ? 0.f : 1.f;
-        if (id < 0) id = 0;
-        ggml_backend_tensor_set(m->emb_idx[(size_t) i], &id, 0, 4);
-        ggml_backend_tensor_set(m->emb_scale[(size_t) i], &sc, 0, 4);
+        const TokenInput in = token_input(id);
+        ggml_backend_tensor_set(m->emb_idx[(size_t) i], &in.row, 0, 4);
+        ggml_backend_tensor_set(m->emb_scale[(size_t) i], &in.scale, 0, 4);
     }
     if (m->tp_frame) tp_temporal_frame(m);
     else {
@@ -2050,10 +2022,10 @@ extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens
     if (m->after_temporal_launch) { m->after_temporal_launch(); m->after_temporal_launch = nullptr; }
     if (!chain) ggml_backend_tensor_get(m->sampler_out, &text_token, 0, 4);
     }
-    if (m->text_hook) text_token = m->text_hook(m->text_hook_user, m->offset, text_token);   // on_text_hook (lm.h:880-900)
+    if (m->text_hook) text_token = m->text_hook(m->text_hook_user, offset, text_token);   // on_text_hook (lm.h:880-900)
 
     std::vector<int32_t> audio((size_t) c.dep_q, 0);   // int_audio_tokens.resize(lm->dep_q) (lm.h:902)
-    const bool replace = m->offset < c.delay_steps;    // depformer_replace_tokens (src/moshi.cpp:905)
+    const bool replace = offset < c.delay_steps;       // depformer_replace_tokens (src/moshi.cpp:905)
     if (c.dep_q > 0) {
         if (!replace) {
             if (m->depth_hook) m->depth_hook(m->depth_hook_user, text_token, audio.data()); else depth_step(m, text_token, audio);
@@ -2061,9 +2033,9 @@ extern "C" int moshi_hot_lm_step_n(moshi_hot_model_t * m, const int32_t * tokens
         }
         else for (auto & a : audio) a = -1;            // lm.h:910-913
         if (c.delay_steps)                             // on_audio_hook (lm.h:915-921)
-            for (int q = 0; q < c.dep_q; q++) if (m->offset < c.delays[q + 1] + c.delay_steps) audio[(size_t) q] = -1;
+            for (int q = 0; q < c.dep_q; q++) if (offset < c.delays[q + 1] + c.delay_steps) audio[(size_t) q] = -1;
     }
-    m->tok_state_for = provided ? -1 : m->offset + 1;
+    m->tok_state_for = provided ? -1 : offset + 1;
     return lm_finish(m, text_token, audio, provided, replace, text_token_out, out_audio, vad);
 }
 
@@ -2097,12 +2069,12 @@ void lm_finish_entry(moshi_hot_model * m, moshi_hot_model::InFlight & f) {
 void lm_queue(moshi_hot_model * m, const int32_t * user_codes) {
     const moshi_hot_config & c = m->cfg;
     // (PersonaPlex: the Depth chain samples all 16 codebooks, the protocol takes the other speaker's 8 and hands back the model's 8, lm.h:802-805)
-    const int ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q_1 = (c.personaplex ? 8 : c.dep_q) + 1, needed = ncb - dep_q_1;
+    const int ncb = c.n_q + 1, dep_q_1 = m->proto.io_dep_q + 1, needed = m->proto.needed();
     // column i of the input row comes from the device-side token state when the Depth chain samples it and the host would read that sample back: the
     // model's own columns always; one of the other speaker's only where the sample of step q - 1 lands on the ring row AFTER the code received at step
     // q - 1 (delay >= 1: the code went to that row first). With delay 0 the code received at step q overwrites the sample: host value.
     auto from_device = [&](int i) { return i < dep_q_1 || (i <= c.dep_q && c.delays[i] > 0); };
-    int q = m->offset;                                   // this step's stream position: completed steps + those still running
+    int q = (int) m->ring.frames;                        // this step's stream position: completed steps + those still running
     for (auto & o : m->inflight) if (!o.done) q++;
     bool steady = run_ahead_config(m) && !m->timing && m->g_temporal && m->g_depth && m->tok_state_for == q;
     for (int i = 0; steady && i < ncb; i++) if (from_device(i) && q <= c.delays[i]) steady = false;   // an initial token is still due on such a column
@@ -2115,17 +2087,14 @@ void lm_queue(moshi_hot_model * m, const int32_t * user_codes) {
         f.done = true;
         return;
     }
-    // other speaker's codes enter the delay ring at step q (lm.h:819-824); their columns of the input row go up from the host as ever
+    // other speaker's codes enter the delay ring at step q; their columns of the input row go up from the host as ever
     f.steady = true;
-    for (int i = 0; i < needed; i++) m->cache[(size_t) ((q + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = user_codes[i];
-    const int pos = q % CT;
+    m->ring.feed_user(user_codes, q);
     for (int i = 0; i < ncb; i++) {
-        int32_t id = q <= c.delays[i] ? m->initial[(size_t) i] : m->cache[(size_t) pos][(size_t) i];
-        float sc = id == -1 ? 0.f : 1.f;
-        if (id < 0) id = 0;
-        if (from_device(i)) sc = 1.f;                                   // sampled ids are never -1
-        else ggml_backend_tensor_set(m->emb_idx[(size_t) i], &id, 0, 4);
-        ggml_backend_tensor_set(m->emb_scale[(size_t) i], &sc, 0, 4);
+        TokenInput in = token_input(m->ring.input(i, q));
+        if (from_device(i)) in.scale = 1.f;                             // sampled ids are never -1
+        else ggml_backend_tensor_set(m->emb_idx[(size_t) i], &in.row, 0, 4);
+        ggml_backend_tensor_set(m->emb_scale[(size_t) i], &in.scale, 0, 4);
     }
     if (m->temporal_staged) m->temporal_staged = false;
     else { transformer_graph_step(*m->scratch, m->temporal, 1); m->scratch->compute_scratch(); }
@@ -2147,7 +2116,7 @@ int lm_complete(moshi_hot_model * m, int32_t * text_token, int32_t * out_audio) 
     moshi_hot_model::InFlight & f = m->inflight.front();
     lm_finish_entry(m, f);
     const int ok = f.ok;
-    if (ok) { *text_token = f.out_text; memcpy(out_audio, f.out_audio.data(), (size_t) (m->cfg.personaplex ? 8 : m->cfg.dep_q) * sizeof(int32_t)); }
+    if (ok) { *text_token = f.out_text; memcpy(out_audio, f.out_audio.data(), (size_t) m->proto.io_dep_q * sizeof(int32_t)); }
     m->inflight.pop_front();
     return ok;
 }
@@ -2161,21 +2130,49 @@ extern "C" int moshi_hot_lm_step_run_ahead(moshi_hot_model_t * m, const int32_t 
 }
 
 extern "C" int moshi_hot_lm_step(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
-    const int io_dep_q = m->cfg.personaplex ? 8 : m->cfg.dep_q;
-    return moshi_hot_lm_step_n(m, in_audio, m->cfg.n_q - io_dep_q, text_token_out, out_audio, nullptr);
+    return moshi_hot_lm_step_n(m, in_audio, m->proto.needed(), text_token_out, out_audio, nullptr);
 }
 
 namespace {
-// the B token inputs of one embedding (moshi_lmmodel_text_token_embed_step, lm.h:586-607): -1 -> scale 0, negative ids -> row 0
+// the B token inputs of one embedding
 void set_token_inputs(T idx, T scale, const std::vector<int32_t> & ids) {
-    std::vector<int32_t> rows(ids.size());
-    std::vector<float> sc(ids.size());
-    for (size_t b = 0; b < ids.size(); b++) {
-        sc[b] = ids[b] == -1 ? 0.f : 1.f;
-        rows[b] = ids[b] < 0 ? 0 : ids[b];
-    }
+    std::vector<int32_t> rows(ids.size()); std::vector<float> sc(ids.size());
+    for (size_t b = 0; b < ids.size(); b++) { const TokenInput in = token_input(ids[b]); rows[b] = in.row; sc[b] = in.scale; }
     ggml_backend_tensor_set(idx, rows.data(), 0, rows.size() * 4);
     ggml_backend_tensor_set(scale, sc.data(), 0, sc.size() * 4);
+}
+// the front end of a batched [dim, T] pass over provided frames, shared by moshi_hot_prefill and the slot prefill:
+struct PassInputs {   // per embedding, one id and one scale per row of the pass
+    std::vector<std::vector<int32_t>> ids; std::vector<std::vector<float>> scales;
+    PassInputs(int ncb, int Tn) : ids((size_t) ncb, std::vector<int32_t>((size_t) Tn)), scales((size_t) ncb, std::vector<float>((size_t) Tn)) {}
+    void set(int i, int row, TokenInput in) { ids[(size_t) i][(size_t) row] = in.row; scales[(size_t) i][(size_t) row] = in.scale; }
+};
+// host side of n provided frames of one ring (lm.h:812-817, 826-834, 933), filling rows [row0, row0 + n) of the pass: ring writes, model inputs, frame count
+void provided_frames(DelayRing & ring, const int32_t * tokens, int n, int row0, PassInputs & in) {
+    const int ncb = ring.p->cols();
+    for (int t = 0; t < n; t++) {
+        ring.feed_provided(tokens + (size_t) t * ncb);
+        for (int i = 0; i < ncb; i++) in.set(i, row0 + t, token_input(ring.input(i, ring.frames)));
+        ring.commit(0, nullptr, true);
+    }
+}
+// moshi_lmmodel_text_token_embed over the Tn rows of a pass, plus the condition sum of a model that has one (no B > 1 model does)
+T embedding_sum_rows(moshi_hot_model * m, Builder & s, const PassInputs & in, int Tn) {
+    T input = nullptr;
+    for (size_t i = 0; i < in.ids.size(); i++) {
+        T idx = s.i32s(in.ids[i]);
+        T sc = s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), in.scales[i].data());
+        T e = ggml_mul(s, ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[i - 1], idx), sc);
+        input = input ? ggml_add(s, input, e) : e;
+    }
+    return m->cfg.condition_sum ? ggml_add(s, m->cond_sum, input) : input;
+}
+// the [C, n] block of the bias table for n rows from stream position pos on, as an uploaded constant (before the ring's wrap it is plainly causal:
+// slot cc is open to row t iff cc <= pos + t, torch.h:170-223): passes of one shape are then structurally identical and the backend reuses one plan
+T causal_mask_block(Builder & s, int C, int64_t pos, int n) {
+    std::vector<float> mv((size_t) C * (size_t) n);
+    for (int t = 0; t < n; t++) for (int cc = 0; cc < C; cc++) mv[(size_t) t * (size_t) C + (size_t) cc] = cc <= pos + t ? 0.0f : -INFINITY;
+    return s.constant(s.tensor(GGML_TYPE_F32, C, n), mv.data());
 }
 // moshi_lmgen_step (lm.h:778-979) of a B > 1 model: the host half runs per column over the column's own delay ring, the Temporal and the Depth graph
 // once for all columns (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - create_columns refuses those). An open
@@ -2183,7 +2180,7 @@ void set_token_inputs(T idx, T scale, const std::vector<int32_t> & ids) {
 // A held slot (moshi_hot_slot_hold) is stepped as a closed one. status[b]: -1 closed, -2 held, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
 void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     const moshi_hot_config & c = m->cfg;
-    const int B = m->n_streams, ncb = c.n_q + 1, CT = (int) m->cache.size(), dep_q = c.dep_q, dep_q_1 = dep_q + 1, needed = ncb - dep_q_1;
+    const int B = m->n_streams, ncb = c.n_q + 1, dep_q = c.dep_q, needed = m->proto.needed();
     int n_open = 0;
     for (int b = 0; b < B; b++) {
         const auto & col = m->cols[(size_t) b];
@@ -2193,18 +2190,17 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     if (!n_open) return;
     if (!m->g_temporal) build_temporal_graph(m);
     if (!m->g_depth) build_depth_graph_streams(m);
-    for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring (lm.h:819-824)
+    for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring
         auto & col = m->cols[(size_t) b];
-        if (!col.open || col.held) continue;
-        for (int i = 0; i < needed; i++) col.cache[(size_t) ((col.frames + c.delays[dep_q_1 + i]) % CT)][(size_t) (dep_q_1 + i)] = in_audio[(size_t) b * needed + i];
+        if (col.open && !col.held) col.ring.feed_user(in_audio + (size_t) b * needed, col.ring.frames);
     }
-    std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q);
+    std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q), audio((size_t) dep_q);
     {
     PhaseTimer pt(m, 1);
     for (int i = 0; i < ncb; i++) {
         for (int b = 0; b < B; b++) {
             const auto & col = m->cols[(size_t) b];
-            ids[(size_t) b] = !col.open || col.held || col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) (col.frames % CT)][(size_t) i];
+            ids[(size_t) b] = !col.open || col.held ? m->proto.initial[(size_t) i] : col.ring.input(i, col.ring.frames);
         }
         set_token_inputs(m->emb_idx[(size_t) i], m->emb_scale[(size_t) i], ids);
     }
@@ -2229,19 +2225,13 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     for (int b = 0; b < B; b++) {
         auto & col = m->cols[(size_t) b];
         if (!col.open || col.held) continue;
-        const int64_t off = ++col.frames;
         col.pos++;
-        auto & row = col.cache[(size_t) (off % CT)];
-        row[0] = text[(size_t) b];
-        for (int q = 0; q < dep_q; q++) row[(size_t) (q + 1)] = toks[(size_t) q * B + b];
-        if (off <= m->max_delay) continue;
-        status[b] = 1;
-        text_token_out[b] = col.cache[(size_t) ((off - m->max_delay + c.delays[0]) % CT)][0];
-        for (int i = 1; i < dep_q_1; i++) {
-            const int32_t v = col.cache[(size_t) ((off - m->max_delay + c.delays[i]) % CT)][(size_t) i];
-            out_audio[(size_t) b * dep_q + (i - 1)] = v;
-            if (v == -1) status[b] = 0;
-        }
+        for (int q = 0; q < dep_q; q++) audio[(size_t) q] = toks[(size_t) q * B + b];
+        col.ring.commit(text[(size_t) b], audio.data(), false);
+        const DelayRing::ReadOut r = col.ring.read_out(&text_token_out[b], audio.data());
+        if (r == DelayRing::ReadOut::filling) continue;
+        memcpy(out_audio + (size_t) b * dep_q, audio.data(), (size_t) dep_q * sizeof(int32_t));
+        status[b] = r == DelayRing::ReadOut::valid ? 1 : 0;
     }
 }
 }  // namespace
@@ -2298,7 +2288,7 @@ extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float *
     std::vector<int32_t> audio((size_t) c.dep_q, 0);
     if (c.dep_q > 0) depth_step(m, 3, audio);                         // text_token = 3 (lm.h:1035)
     m->last_text = sampled; m->last_audio = audio;
-    m->offset++;
+    m->ring.commit(sampled, audio.data(), true);   // nothing of a voice-prompt frame enters the ring: the count alone advances
 }
 
 extern "C" void moshi_hot_set_conditions(moshi_hot_model_t * m, const float * sum, const float * cross) { STREAMS_REFUSE();
@@ -2322,8 +2312,8 @@ extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens,
     unstage_temporal(m);
     m->tok_state_for = -1;
     const moshi_hot_config & c = m->cfg;
-    const int ncb = c.n_q + 1, CT = (int) m->cache.size();
-    GGML_ASSERT(ncb - (c.personaplex ? 8 : c.dep_q) - 1 > 0 && !c.demux_second_stream && !c.cross_attention);
+    const int ncb = c.n_q + 1;
+    GGML_ASSERT(m->proto.needed() > 0 && !c.demux_second_stream && !c.cross_attention);
     if (chunk < 1) chunk = 64;
     if (chunk > 64) chunk = 64;   // the device's batched kernels take up to 64 rows per pass
     ggml_backend_mi355x_set_capture(m->be, 0);   // same-shaped chunk graphs: reuse the plan, do not pay a hipGraph capture for a handful of replays
@@ -2336,39 +2326,12 @@ extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens,
             done++;
             continue;
         }
-        // host side of Tn provided frames (lm.h:812-817, 826-834, 933): ring writes, model inputs, offset
-        std::vector<std::vector<int32_t>> ids((size_t) ncb, std::vector<int32_t>((size_t) Tn));
-        std::vector<std::vector<float>> scales((size_t) ncb, std::vector<float>((size_t) Tn));
-        for (int t = 0; t < Tn; t++) {
-            const int32_t * tk = tokens + (size_t) (done + t) * ncb;
-            for (int i = 0; i < ncb; i++) m->cache[(size_t) ((m->offset + c.delays[i]) % CT)][(size_t) i] = tk[i];
-            const int pos = m->offset % CT;
-            for (int i = 0; i < ncb; i++) {
-                int32_t id = m->offset <= c.delays[i] ? m->initial[(size_t) i] : m->cache[(size_t) pos][(size_t) i];
-                scales[(size_t) i][(size_t) t] = id == -1 ? 0.f : 1.f;
-                ids[(size_t) i][(size_t) t] = id < 0 ? 0 : id;
-            }
-            m->offset++;
-        }
+        PassInputs in(ncb, Tn);
+        provided_frames(m->ring, tokens + (size_t) done * ncb, Tn, 0, in);
         PhaseTimer pt(m, 1);
         Builder & s = *m->scratch;
-        T input = nullptr;
-        for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed over Tn columns
-            T idx = s.i32s(ids[(size_t) i]);
-            T sc = s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), scales[(size_t) i].data());
-            T e = ggml_mul(s, ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[(size_t) (i - 1)], idx), sc);
-            input = input ? ggml_add(s, input, e) : e;
-        }
-        if (c.condition_sum) input = ggml_add(s, m->cond_sum, input);
-        // the [C, Tn] block of the bias table as an uploaded constant (before the wrap it is plainly causal: slot cc is open to row t iff
-        // cc <= offset + t, torch.h:170-223): the chunk graphs of one prefill are then structurally identical and the backend reuses one plan
-        T mask = s.tensor(GGML_TYPE_F32, m->temporal.capacity, Tn);
-        {
-            std::vector<float> mv((size_t) m->temporal.capacity * (size_t) Tn);
-            for (int t = 0; t < Tn; t++)
-                for (int cc = 0; cc < m->temporal.capacity; cc++) mv[(size_t) t * (size_t) m->temporal.capacity + (size_t) cc] = cc <= m->temporal.offset + t ? 0.0f : -INFINITY;
-            s.constant(mask, mv.data());
-        }
+        T input = embedding_sum_rows(m, s, in, Tn);
+        T mask = causal_mask_block(s, m->temporal.capacity, m->temporal.offset, Tn);
         T x = transformer_inline(s, m->temporal, input, mask);
         // transformer_out as the last of these frames would have left it (lm.h:434, 847-849)
         T last = ggml_view_2d(s, x, x->ne[0], 1, x->nb[1], (size_t) (Tn - 1) * x->nb[1]);
@@ -2429,45 +2392,18 @@ T transformer_layer_jobs(Builder & c, const Transformer & tr, Layer & L, T x, co
 
 // one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
 void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames) {
-    const moshi_hot_config & c = m->cfg;
-    const int ncb = c.n_q + 1, CT = (int) m->cache.size(), C = m->temporal.capacity;
+    const int C = m->temporal.capacity;
     int Tn = 0;
     for (const PassJob & j : jobs) Tn += j.n;
-    // host side of the provided frames (lm.h:812-817, 826-834, 933), per job: ring writes, model inputs, frame count
-    std::vector<std::vector<int32_t>> ids((size_t) ncb, std::vector<int32_t>((size_t) Tn));
-    std::vector<std::vector<float>> scales((size_t) ncb, std::vector<float>((size_t) Tn));
-    for (size_t ji = 0; ji < jobs.size(); ji++) {
-        PassJob & j = jobs[ji];
-        auto & col = m->cols[(size_t) j.b];
-        for (int t = 0; t < j.n; t++) {
-            const int32_t * tk = frames[ji] + (size_t) t * ncb;
-            for (int i = 0; i < ncb; i++) col.cache[(size_t) ((col.frames + c.delays[i]) % CT)][(size_t) i] = tk[i];
-            const int pos = (int) (col.frames % CT);
-            for (int i = 0; i < ncb; i++) {
-                const int32_t id = col.frames <= c.delays[i] ? m->initial[(size_t) i] : col.cache[(size_t) pos][(size_t) i];
-                scales[(size_t) i][(size_t) (j.row + t)] = id == -1 ? 0.f : 1.f;
-                ids[(size_t) i][(size_t) (j.row + t)] = id < 0 ? 0 : id;
-            }
-            col.frames++;
-        }
-    }
+    PassInputs in(m->cfg.n_q + 1, Tn);
+    for (size_t ji = 0; ji < jobs.size(); ji++) provided_frames(m->cols[(size_t) jobs[ji].b].ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
     PhaseTimer pt(m, 1);
     Builder & s = *m->scratch;
-    T input = nullptr;
-    for (int i = 0; i < ncb; i++) {   // moshi_lmmodel_text_token_embed over Tn columns
-        T idx = s.i32s(ids[(size_t) i]);
-        T sc = s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), scales[(size_t) i].data());
-        T e = ggml_mul(s, ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[(size_t) (i - 1)], idx), sc);
-        input = input ? ggml_add(s, input, e) : e;
-    }
+    T input = embedding_sum_rows(m, s, in, Tn);
     for (PassJob & j : jobs) {   // the job's mask block (causal from its position: no job passes the ring's end), ring slots and RoPE rows
-        std::vector<float> mv((size_t) C * (size_t) j.n);
         std::vector<int32_t> idx((size_t) j.n);
-        for (int t = 0; t < j.n; t++) {
-            for (int cc = 0; cc < C; cc++) mv[(size_t) t * (size_t) C + (size_t) cc] = cc <= j.pos + t ? 0.0f : -INFINITY;
-            idx[(size_t) t] = (int32_t) ((j.pos + t) % C);
-        }
-        j.mask = s.constant(s.tensor(GGML_TYPE_F32, C, j.n), mv.data());
+        for (int t = 0; t < j.n; t++) idx[(size_t) t] = (int32_t) ((j.pos + t) % C);
+        j.mask = causal_mask_block(s, C, j.pos, j.n);
         j.indices = s.i32s(idx);
         if (m->temporal.max_period) j.rot = timestep_embedding(s, j.n, m->temporal.dim / m->temporal.heads, s.f32((float) j.pos), m->temporal.max_period);
     }
@@ -2554,7 +2490,7 @@ uint64_t slot_fingerprint(const moshi_hot_model * m) {
     return h;
 }
 int64_t slot_host_bytes(const moshi_hot_model * m) {   // everything in front of the ring rows
-    const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->cache.size() * (m->cfg.n_q + 1) * 4 + (int64_t) m->cfg.dim * 4;
+    const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->proto.rows * m->proto.cols() * 4 + (int64_t) m->cfg.dim * 4;
     return (n + 15) / 16 * 16;
 }
 int64_t slot_ring_bytes(const moshi_hot_model * m, int64_t n_rows) {
@@ -2621,13 +2557,13 @@ extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf,
     SlotBlobHeader h;
     memset(&h, 0, sizeof(h));
     h.magic = SLOT_BLOB_MAGIC; h.version = SLOT_BLOB_VERSION; h.fingerprint = slot_fingerprint(m);
-    h.total_bytes = total; h.frames = col->frames; h.pos = col->pos; h.n_rows = n;
-    h.ring_rows = (int32_t) col->cache.size(); h.ring_cols = m->cfg.n_q + 1;
+    h.total_bytes = total; h.frames = col->ring.frames; h.pos = col->pos; h.n_rows = n;
+    h.ring_rows = m->proto.rows; h.ring_cols = m->proto.cols();
     h.seeded = m->sampling[(size_t) b].seeded ? 1 : 0; h.sampling = m->sampling[(size_t) b].s;
     memcpy(out, &h, sizeof(h));
     int32_t * ring = (int32_t *) (out + sizeof(h));
-    for (const auto & row : col->cache) for (int v : row) *ring++ = v;
-    slot_state_graph(m, b, -1, n, nullptr, nullptr, ring, out + host);
+    col->ring.export_rows(ring);
+    slot_state_graph(m, b, -1, n, nullptr, nullptr, ring + col->ring.rows.size(), out + host);
     return total;
 }
 
@@ -2640,14 +2576,14 @@ extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * bu
     const moshi_hot_config & c = m->cfg;
     const int64_t host = slot_host_bytes(m), C = m->temporal.capacity;
     if (h.magic != SLOT_BLOB_MAGIC || h.version != SLOT_BLOB_VERSION || h.fingerprint != slot_fingerprint(m)) return -1;
-    if (h.pos < 0 || h.frames < 0 || h.n_rows != (h.pos < C ? h.pos : C) || h.ring_rows != (int32_t) m->cache.size() || h.ring_cols != c.n_q + 1) return -1;
+    if (h.pos < 0 || h.frames < 0 || h.n_rows != (h.pos < C ? h.pos : C) || h.ring_rows != m->proto.rows || h.ring_cols != m->proto.cols()) return -1;
     if (h.total_bytes != host + slot_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
     const moshi_hot_sampling & sp = h.sampling;
     if (sampled_model(m) && (!(sp.temp > 0.f) || !(sp.temp_text > 0.f) || sp.top_k < 1 || sp.top_k > c.top_k || sp.top_k_text < 1 || sp.top_k_text > c.top_k_text)) return -1;
     const int32_t * ring = (const int32_t *) (in + sizeof(h));
     slot_state_graph(m, -1, b, h.n_rows, ring + (size_t) h.ring_rows * (size_t) h.ring_cols, in + host, nullptr, nullptr);
-    *col = { m->cache, h.frames, h.pos, true };
-    for (auto & row : col->cache) for (int & v : row) v = *ring++;
+    col->ring.import_rows(ring, h.frames);
+    col->pos = h.pos; col->open = true; col->held = false;
     m->sampling[(size_t) b] = { sp, h.seeded != 0 && sampled_model(m) };
     if (m->sampling[(size_t) b].seeded) m->any_seeded = true;
     m->sampling_dirty = true;
@@ -2724,14 +2660,13 @@ extern "C" int moshi_hot_sts_pipeline_frame(moshi_hot_model_t * m, const float *
         if (dec) mimi_decode_launch(m, m->pipe_tokens.data());          // frame k - 1
         if (pcm_next) mimi_encode_launch(m, pcm_next);                  // frame k + 1
     };
-    const int io = m->cfg.personaplex ? 8 : m->cfg.dep_q;
-    const int ok = moshi_hot_lm_step_n(m, m->pipe_codes.data(), m->cfg.n_q - io, text_token, audio_tokens,
+    const int ok = moshi_hot_lm_step_n(m, m->pipe_codes.data(), m->proto.needed(), text_token, audio_tokens,
                                        m->extra_heads.size() > 2 ? &m->pipe_vad : nullptr);   // frame k (blocks on the LM stream only)
     if (dec) mimi_decode_finish(m, pcm_prev);
     if (pcm_next) mimi_encode_finish(m, m->pipe_codes.data());
     m->pipe_have_codes = pcm_next != nullptr || !m->cfg.enable_mimi_encoder;
     m->pipe_have_tokens = ok != 0;
-    if (ok) memcpy(m->pipe_tokens.data(), audio_tokens, (size_t) (m->cfg.personaplex ? 8 : m->cfg.dep_q) * sizeof(int32_t));
+    if (ok) memcpy(m->pipe_tokens.data(), audio_tokens, (size_t) m->proto.io_dep_q * sizeof(int32_t));
     return (ok ? 1 : 0) | (dec ? 2 : 0);
 }
 extern "C" int moshi_hot_sts_pipeline_end(moshi_hot_model_t * m, int32_t * text_token, int32_t * audio_tokens, float * pcm_last) { STREAMS_REFUSE(-1);
@@ -2750,7 +2685,7 @@ extern "C" int moshi_hot_sts_pipeline_end(moshi_hot_model_t * m, int32_t * text_
 }
 
 extern "C" float moshi_hot_sts_pipeline_vad(moshi_hot_model_t * m) { return m->pipe_vad; }
-extern "C" int64_t moshi_hot_offset(moshi_hot_model_t * m) { return m->kind == ModelKind::lockstep ? m->cols[0].frames : m->offset; }   // (slots: 0)
+extern "C" int64_t moshi_hot_offset(moshi_hot_model_t * m) { return m->kind == ModelKind::lockstep ? m->cols[0].ring.frames : m->ring.frames; }   // (slots: the unbound ring's 0)
 extern "C" void moshi_hot_last_raw_tokens(moshi_hot_model_t * m, int32_t * text_token, int32_t * audio_tokens) {
     *text_token = m->last_text;
     for (size_t i = 0; i < m->last_audio.size(); i++) audio_tokens[i] = m->last_audio[i];
@@ -2780,9 +2715,7 @@ extern "C" struct ggml_tensor * moshi_hot_weight(moshi_hot_model_t * m, const ch
 extern "C" void moshi_hot_set_timing(moshi_hot_model_t * m, int on) { m->timing = on != 0; for (int i = 0; i < 4; i++) { m->phase_us[i] = 0; m->phase_n[i] = 0; } }
 extern "C" void moshi_hot_get_timing(moshi_hot_model_t * m, double * us_per_call) { for (int i = 0; i < 4; i++) us_per_call[i] = m->phase_n[i] ? m->phase_us[i] / (double) m->phase_n[i] : 0.0; }
 extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, const int32_t * audio_tokens) { STREAMS_REFUSE();
-    const int wpos = m->offset % (int) m->cache.size();
-    m->cache[(size_t) wpos][0] = text_token;
-    for (int q = 0; q < m->cfg.dep_q; q++) m->cache[(size_t) wpos][(size_t) (q + 1)] = audio_tokens[q];
+    m->ring.force_last(text_token, audio_tokens);
     m->tok_state_for = -1;   // the device-side token state still holds the model's own samples
 }
 extern "C" void moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset) {
