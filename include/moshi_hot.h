@@ -100,9 +100,15 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 // model and a slots model (below) are this one model and step alike; they differ only in where a column's position comes from. Here every column
 // is open from creation and all B share one stream position, so the mask row, the RoPE phase and the ring slot are common.
 // n_streams == 1 builds exactly moshi_hot_create's model.
-// n_streams > 1 takes the moshika-shaped LM only: enable_lm = 1 with both codec halves off, personaplex = 0, no demux / cross-attention / condition_sum /
-// extra heads / low-rank embeddings / weight schedule / delay_steps, tp_world == 0, dep_shard_world <= 1, depth_only == 0, chain_depth == 0,
-// codec_stream == 0, and 1 <= n_streams <= 16. Anything else returns NULL.
+// n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0, no demux / cross-attention / condition_sum /
+// low-rank embeddings / weight schedule / delay_steps, tp_world == 0, dep_shard_world <= 1, depth_only == 0, chain_depth == 0,
+// codec_stream == 0, and 1 <= n_streams <= 16, in one of two shapes:
+//  * the moshika shape: dep_q > 0, n_q > dep_q, extra_heads == 0;
+//  * the stt shape (moshi-stt): dep_q == 0 and n_q > 0 - no Depth transformer, every audio codebook is an input, the text token comes from the
+//    Temporal head - with extra_heads == 0, or extra_heads >= 1 heads of 1 <= extra_heads_dim <= 16 values on transformer_out (lm.h:966-976).
+//    A frame takes n_q codes per column, out_audio is not touched and may be NULL, the frame's only sampler site is 0 (the text head), and the
+//    heads' probabilities of every column are computed by the Temporal graph itself and read back with the tokens (moshi_hot_last_heads).
+// Anything else returns NULL.
 // On such a model moshi_hot_read_last("text_logits" | "transformer_out" | "dep_logits<k>") returns B consecutive rows (stream 0 first), and
 // moshi_hot_set_context_fill moves the shared stream position, not the delay rings. The single-stream frame calls (moshi_hot_lm_step*, moshi_hot_sts_*,
 // moshi_hot_ring_bytes, moshi_hot_host_ring, moshi_hot_layer_probe) return -1, and the calls without a result (moshi_hot_mimi_*, moshi_hot_prefill,
@@ -136,6 +142,12 @@ GGML_API void moshi_hot_slot_set_fill(moshi_hot_model_t * m, int b, int64_t offs
 // are valid, 0 while its own delay ring fills, -1 when it is closed; the outputs of a slot whose status is not 1 are written as -1. Returns the
 // number of slots with status 1, or -1 on a model that is not a slots model. With no slot open it does no device work and returns 0.
 GGML_API int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token, int32_t * out_audio, int32_t * status);
+// The extra heads of the last step of a B > 1 stt-shaped model (lockstep or slots): out[(b * extra_heads + k) * extra_heads_dim + i] = probability i of
+// soft_max(extra_heads[k] . transformer_out) of column b - B x extra_heads x extra_heads_dim floats, column-major by column. The VAD value the reference
+// reports (lm.h:966-976) is out[(b * extra_heads + 2) * extra_heads_dim]. The rows of a column whose status in that step was not 1 (closed, held, its
+// delay ring still filling) are -1. Returns the number of floats written, or -1 (nothing written) on a single-stream model, on a model without extra
+// heads, or when n is smaller than that count.
+GGML_API int moshi_hot_last_heads(moshi_hot_model_t * m, float * out, int64_t n);
 // Slot prefill: admit conversations that already have a history. Job j advances open slot slots[j] by n_frames[j] provided frames (tokens[j]:
 // n_frames[j] x (n_q + 1), text first - what moshi_hot_prefill takes), leaving the slot as a fresh single-stream model is after moshi_hot_prefill over
 // the same frames: delay ring, frame count (the frame the seeded noise source sees), stream position, the slot's KV ring rows and its row of
@@ -193,8 +205,8 @@ struct moshi_hot_sampling { uint64_t seed; float temp, temp_text; int32_t top_k,
 //    moshi_hot_slot_close / _open, and a newly opened slot restarts at frame 0 of its seed, so the same seed replays the same conversation.
 //  * single-stream (b = 0): only the seed is free - temp, temp_text, top_k and top_k_text must equal the configuration's (its graphs keep them baked in).
 //    Supported on the moshika-shaped LM (with or without the codec) stepped by moshi_hot_lm_step, moshi_hot_lm_step_n, moshi_hot_sts_frame and the
-//    moshi_hot_sts_pipeline_* calls with chain_depth = 0. Returns -1 with chain_depth > 0 (moshi_hot_lm_step_run_ahead included), personaplex, extra
-//    heads, demux, low-rank embeddings, delay_steps, cross-attention, condition_sum, a weight schedule, a Depth shard, a Depth hook or a tensor-parallel
+//    moshi_hot_sts_pipeline_* calls with chain_depth = 0, and on the stt-shaped LM (dep_q == 0: site 0 is its only sampler; extra heads allowed).
+//    Returns -1 with chain_depth > 0 (moshi_hot_lm_step_run_ahead included), personaplex, extra heads on a model with a Depth transformer, demux, low-rank embeddings, delay_steps, cross-attention, condition_sum, a weight schedule, a Depth shard, a Depth hook or a tensor-parallel
 //    stack. The text sample moshi_hot_lm_step_embedding computes and discards still draws from rand().
 // A column that was never set draws from rand() exactly as before: the sweep over the whole noise tensor is always drawn in full, in the same order, and
 // the rows of seeded columns are overwritten afterwards. A seeded column that is closed gets constant noise; its results are dropped.

@@ -1922,6 +1922,76 @@ static bool match_sampler_streams(const analysis & an, int pos, sample_streams_a
     return true;
 }
 
+// H3. the extra heads of a B-column stt step (moshi_hot.cpp build_temporal_graph): for every head k
+//    cpy(soft_max(mul_mat(W_k, x)), view k of heads_out)
+// with one contiguous F32 x = [K, .., B] (B >= 2 columns of K values) for all heads, W_k dense block-quantised [K, M] rows of one type, K % 256 == 0,
+// K <= 16384, M <= HEADS_MAX_M, a plain soft_max (no mask, scale 1), and destinations of M x B floats whose columns are one stride apart and whose rows
+// do not overlap. Matched at the first head's mul_mat; claims every such triple over the same x (at most HEADS_MAX) and is emitted where the last
+// copy stood. Neither the products nor the soft_max results may have another reader, and nothing else in the graph may touch the destination tensor.
+// Anything else (float weights, M > 16) is left to the plain nodes.
+static bool match_heads_streams(const analysis & an, int pos, heads_streams_args & a, std::vector<int> & members, int & emit_pos) {
+    const ggml_tensor * mm0 = an.g->nodes[pos];
+    if (mm0->op != GGML_OP_MUL_MAT) return false;
+    const ggml_tensor * x = mm0->src[1], * w0 = mm0->src[0];
+    if (!is_qblock(w0->type) || x->type != GGML_TYPE_F32 || !ggml_is_contiguous(x) || !x->data) return false;
+    const int64_t K = w0->ne[0], M = w0->ne[1];
+    if (K % 256 != 0 || K > 16384 || M < 1 || M > HEADS_MAX_M || x->ne[0] != K) return false;
+    const int64_t B = ggml_nelements(x) / K;
+    if (B < 2) return false;
+    memset(&a, 0, sizeof(a));
+    members.clear();
+    const ggml_tensor * root = nullptr;
+    int n = 0;
+    emit_pos = -1;
+    for (int i = pos; i < an.g->n_nodes && n < HEADS_MAX; i++) {
+        const ggml_tensor * mm = an.g->nodes[i];
+        if (an.skip[(size_t) i] || mm->op != GGML_OP_MUL_MAT || mm->src[1] != x) continue;
+        const ggml_tensor * w = mm->src[0];
+        if (w->type != w0->type || w->ne[0] != K || w->ne[1] != M || !dense_rows(w) || w->nb[1] != w0->nb[1] || !w->data || ((uintptr_t) w->data & 15) || (w->nb[1] & 15)) continue;
+        if (mm->type != GGML_TYPE_F32 || mm->view_src || mm->ne[0] != M || ggml_nelements(mm) != M * B || !ggml_is_contiguous(mm) || uses_of(an, mm) != 1) continue;
+        const ggml_tensor * sm = sole_consumer(an, mm);
+        if (!sm || sm->op != GGML_OP_SOFT_MAX || sm->src[0] != mm || sm->src[1] != NULL || sm->view_src || uses_of(an, sm) != 1) continue;
+        if (ggml_get_op_params_f32(sm, 0) != 1.0f || ggml_get_op_params_f32(sm, 1) != 0.0f) continue;
+        const ggml_tensor * cp = sole_consumer(an, sm);
+        if (!cp || cp->op != GGML_OP_CPY || cp->src[0] != sm || cp->type != GGML_TYPE_F32 || !cp->data || cp->ne[0] != M || ggml_nelements(cp) != M * B || cp->nb[0] != 4) continue;
+        const int psm = pos_of(an, sm), pcp = pos_of(an, cp);
+        if (psm < 0 || pcp < 0 || an.skip[(size_t) psm] || an.skip[(size_t) pcp]) continue;
+        // the one dimension of the destination that counts the columns
+        int bd = -1;
+        for (int d = 1; d < 4; d++) if (cp->ne[d] == B) bd = bd < 0 ? d : 4;
+        if (bd < 1 || bd > 3 || cp->nb[bd] % 4 != 0 || (int64_t) cp->nb[bd] < M * 4) continue;
+        const ggml_tensor * rt = cp->view_src ? cp->view_src : cp;
+        if (n == 0) { root = rt; a.out_bs = (int64_t) cp->nb[bd] / 4; }
+        else if (rt != root || (int64_t) cp->nb[bd] / 4 != a.out_bs) continue;
+        a.w[n] = (const char *) w->data; a.out[n] = (float *) cp->data;
+        n++;
+        members.insert(members.end(), { i, psm, pcp });
+        if (is_view_op(cp->src[1]->op) && pos_of(an, cp->src[1]) >= 0) members.push_back(pos_of(an, cp->src[1]));   // (the destination view: a layout node, no launch)
+        if (pcp > emit_pos) emit_pos = pcp;
+    }
+    if (n == 0 || (const ggml_tensor *) an.g->nodes[members[0]] != mm0) return false;
+    // every head's M values of a column lie inside one column period of the destination and no two heads' rows overlap: no two stores of the launch meet
+    float * lo = a.out[0];
+    for (int k = 1; k < n; k++) if (a.out[k] < lo) lo = a.out[k];
+    for (int k = 0; k < n; k++) {
+        if (a.out[k] - lo + M > a.out_bs) return false;
+        for (int j = 0; j < k; j++) if (a.out[k] - a.out[j] < M && a.out[j] - a.out[k] < M) return false;
+    }
+    // nothing but the claimed copies touches the destination tensor (a reader between two copies would see some heads only once they move to one launch)
+    for (int i = 0; i < an.g->n_nodes; i++) {
+        if (std::find(members.begin(), members.end(), i) != members.end()) continue;
+        const ggml_tensor * nd = an.g->nodes[i];
+        if (nd == root || nd->view_src == root) return false;
+        for (int s = 0; s < GGML_MAX_SRC; s++) if (nd->src[s] && (nd->src[s] == root || nd->src[s]->view_src == root)) return false;
+    }
+    // x must be complete before the first claimed product and is not rewritten before the launch: x is a node (or a leaf) read in place; a writer
+    // through an alias between the first product and the emit position would change what the later position reads
+    for (int i = pos + 1; i < emit_pos; i++) if (std::find(members.begin(), members.end(), i) == members.end() && writes_through_alias(an.g->nodes[i])) return false;
+    a.row_bytes = (int64_t) w0->nb[1]; a.wtype = (int) w0->type; a.K = (int) K; a.M = (int) M; a.n_heads = n; a.B = (int) B;
+    a.x = (const float *) x->data; a.x_cs = K;
+    return true;
+}
+
 // ---- plan construction --------------------------------------------------------------------------------------
 // Kernels whose workgroups wait for each other inside a launch (persistent chains, the fused attention + out_proj launch) need their WHOLE grid resident.
 // Two such launches from two streams of one device could interleave their dispatch and each keep the other's workgroups off the compute units, so only ONE
@@ -1954,6 +2024,18 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
     static const bool no_attn_prologue = getenv("MI355X_NO_ATTN_PROLOGUE") != nullptr;
     static const bool no_argmax_epilogue = getenv("MI355X_NO_ARGMAX_EPILOGUE") != nullptr;
     if (fuse) {
+        // the extra heads of a B-column stt step: every head's mul_mat -> soft_max -> cpy in one launch
+        static const bool no_heads = getenv("MI355X_NO_HEADS_FUSION") != nullptr;
+        for (int i = 0; i < g->n_nodes && !no_heads; i++) {
+            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_MUL_MAT) continue;
+            heads_streams_args ha;
+            std::vector<int> members;
+            int emit = -1;
+            if (!match_heads_streams(an, i, ha, members, emit)) continue;
+            for (int m : members) an.skip[(size_t) m] = 1;
+            at_pos[emit].push_back([=](hipStream_t s) { k_heads_streams(s, ha); });
+            p->n_fused += (int) members.size();
+        }
         // slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp slot_state_graph) - one launch for the whole run
         for (int i = 0; i < g->n_nodes; i++) {
             ring_copy_group rg;

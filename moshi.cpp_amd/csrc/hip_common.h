@@ -269,6 +269,13 @@ void k_sample_topk(hipStream_t s, const sample_args & a);
 #define SAMPLE_MAX_B 16
 struct sample_streams_args { const float * logits; int n; float scale; const float * inv_temp; int k; const float * noise; int32_t * out; int32_t * out2; int B; };
 void k_sample_topk_streams(hipStream_t s, const sample_streams_args & a);
+// The extra heads of a B-column stt step (moshi_hot.cpp build_temporal_graph): for every column b and head k, soft_max(W_k . x[:, b]) with W_k a block-
+// quantised [K, M] matrix (Q4_K / Q8_0 / Q4_0, K % 256 == 0, K <= 16384, M <= 16, at most 16 heads) - one launch, one workgroup per column, none waits
+// for another. out[k][b * out_bs + i] (floats) = probability i of head k of column b.
+#define HEADS_MAX 16
+#define HEADS_MAX_M 16
+struct heads_streams_args { const char * w[HEADS_MAX]; float * out[HEADS_MAX]; int64_t row_bytes; int wtype; int K, M, n_heads, B; const float * x; int64_t x_cs, out_bs; };
+void k_heads_streams(hipStream_t s, const heads_streams_args & a);
 #define VQ_LEVEL_WS_BYTES 4096
 void k_vq_level(hipStream_t s, const vq_level_args & a);
 // Consecutive levels of one RVQ stack (each level's residual is the previous level's output: core_vq.h:27-56 inside vq.h:97-114's loop) as ONE persistent

@@ -2643,3 +2643,63 @@ void k_gather_scalars(hipStream_t s, const gather_args & a) {
     GGML_ASSERT(a.n <= GATHER_MAX && (a.dst_type == GGML_TYPE_I32 || a.dst_type == GGML_TYPE_F32));
     gather_scalars_kernel<<<1, 64, 0, s>>>(a);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// extra heads of a B-column stt step: soft_max(W_k . x[:, b]) for every head k and column b, one launch
+// ---------------------------------------------------------------------------------------------------
+// One workgroup of four waves per column; no workgroup waits for another.
+//  1. the column is quantised to the activation records of the block mat-vec (Q8_K for Q4_K weights, Q8_0 for Q8_0 / Q4_0) in LDS, a wave per
+//     256-value block, exactly as matvec_q4k_kernel's prologue does;
+//  2. 16 lanes per weight row (n_heads x M <= 256 rows): lane j takes super-blocks j, j + 16, .. in ascending order, then the 4-step butterfly of the
+//     mat-vec's phase 4 - the same integers and the same float sums, in the same order, as the single-column mat-vec of that weight type. A lane
+//     reads its super-block straight from global memory (the weights of all heads are ~20 KB: nothing to stage or to pipeline);
+//  3. one wave per head: maximum, expf(v - max), the sum in double in index order, one reciprocal, a product (op_soft_max's operations and order).
+// LDS (all dynamic, 16-byte aligned carves): K / 256 records of 304 B, then 256 floats for the row sums.
+template <int FMT>
+__global__ void __launch_bounds__(256) heads_streams_kernel(heads_streams_args a) {
+    constexpr int SB = mvfmt<FMT>::SB;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int nb = a.K / 256, M = a.M, R = a.n_heads * a.M;
+    xblk * xs = (xblk *) smem;
+    float * logit = (float *) (smem + nb * XBLK_BYTES);
+    const float * x = a.x + (int64_t) b * a.x_cs;
+    for (int j = wave; j < nb; j += 4) {   // (wave-uniform: the quantisers reduce over the whole wave)
+        const float4 xv = *(const float4 *) (x + j * 256 + lane * 4);
+        const float v[4] = { xv.x, xv.y, xv.z, xv.w };
+        if (FMT == MVF_Q4K) quantize_block_q8k(xs + j, v, lane); else quantize_block_q80((xblk80 *) (xs + j), v, lane);
+    }
+    __syncthreads();
+    for (int rr = tid >> 4; rr < R; rr += 16) {
+        const int h = rr / M, i = rr - h * M;
+        const char * wrow = a.w[h] + (int64_t) i * a.row_bytes;
+        float sum = 0.f;
+        for (int j = tid & 15; j < nb; j += 16) {
+            const char * wb = wrow + (int64_t) j * SB;
+            const xblk * xb = xs + j;
+            if (FMT == MVF_Q4K) sum += q4k_q8k_block_dot((const block_q4_K *) wb, xb->q, xb->bsums, xb->d);
+            else if (FMT == MVF_Q80) sum += q80_q80_sb_dot(wb, (const xblk80 *) xb);
+            else sum += q40_q80_sb_dot(wb, (const xblk80 *) xb);
+        }
+        sum = row16_allsum_f32(sum);   // (a row's 16 lanes run the loop above together: every lane of the DPP row is active)
+        if ((tid & 15) == 0) logit[rr] = sum;
+    }
+    __syncthreads();
+    for (int h = wave; h < a.n_heads; h += 4) {   // (wave-uniform)
+        const float v = lane < M ? logit[h * M + lane] : -INFINITY;
+        const float mx = wave_allmax_f32(v);
+        const float e = lane < M ? expf(v - mx) : 0.f;
+        double sum = 0.0;
+        for (int i = 0; i < M; i++) sum += (double) __shfl(e, i, 64);
+        const float inv = (float) (1.0 / sum);
+        if (lane < M) a.out[h][(int64_t) b * a.out_bs + lane] = e * inv;
+    }
+}
+void k_heads_streams(hipStream_t s, const heads_streams_args & a) {
+    GGML_ASSERT(a.B >= 2 && a.n_heads >= 1 && a.n_heads <= HEADS_MAX && a.M >= 1 && a.M <= HEADS_MAX_M && a.K >= 256 && a.K % 256 == 0 && a.K <= 16384);
+    const size_t lds = (size_t) (a.K / 256) * XBLK_BYTES + 256 * sizeof(float);
+    if (a.wtype == GGML_TYPE_Q4_K) heads_streams_kernel<MVF_Q4K><<<a.B, 256, lds, s>>>(a);
+    else if (a.wtype == GGML_TYPE_Q8_0) heads_streams_kernel<MVF_Q80><<<a.B, 256, lds, s>>>(a);
+    else if (a.wtype == GGML_TYPE_Q4_0) heads_streams_kernel<MVF_Q40><<<a.B, 256, lds, s>>>(a);
+    else GGML_ABORT("k_heads_streams: weight type");
+}

@@ -813,6 +813,9 @@ struct moshi_hot_model {
     std::vector<T> emb, depformer_in, depformer_emb, linears;
     T depformer_text_emb = nullptr;
     std::vector<T> extra_heads;
+    // B > 1 with extra heads: state F32 [extra_heads_dim, extra_heads, B], the tail of the Temporal graph writes soft_max(extra_heads[k] . transformer_out) of every
+    // column into it each step; last_heads is the host copy moshi_hot_last_heads returns (rows of columns whose status was not 1: -1)
+    T heads_out = nullptr; std::vector<float> last_heads;
     // tts variants
     T text_out1 = nullptr, text_out2 = nullptr, dep_text_out1 = nullptr, dep_text_out2 = nullptr;   // demux (lm_utils.h:48-85)
     T dep_text_low_rank = nullptr; std::vector<T> depformer_emb_low_rank;                          // low-rank embeddings (lm_utils.h:157-217)
@@ -1037,6 +1040,13 @@ void build_temporal_graph(moshi_hot_model * m) {
     m->sampler_out = m->n_streams > 1 ? sample_tokens_streams(g, m->text_logits, c.temp_text, c.top_k_text, m->inv_temp_text, 0) : sample_token(g, m->text_logits, c.temp_text, c.top_k_text, 0);
     g.expand(m->sampler_out);
     if (m->tok_state) g.expand(ggml_cpy(g, ggml_reshape_1d(g, m->sampler_out, 1), ggml_view_1d(g, m->tok_state, 1, 0)));
+    // B > 1 with extra heads (stt): what the single-stream step computes for one head on the scratch context after the step (lm.h:966-976) sits here
+    // for every head and column, over the very value that goes into transformer_out: heads_out[:, k, b] = soft_max(extra_heads[k] . x[:, b])
+    if (m->heads_out) for (size_t k = 0; k < m->extra_heads.size(); k++) {
+        T sm = ggml_soft_max(g, linear(g, m->extra_heads[k], x));   // [extra_heads_dim, 1, B]
+        T row = ggml_view_3d(g, m->heads_out, m->heads_out->ne[0], 1, m->n_streams, m->heads_out->nb[1], m->heads_out->nb[2], k * m->heads_out->nb[1]);
+        g.expand(ggml_cpy(g, sm, row));
+    }
     g.alloc();
 }
 
@@ -1209,14 +1219,17 @@ extern "C" void moshi_hot_config_personaplex(struct moshi_hot_config * c) {
 static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams = 1,
                                         ModelKind kind = ModelKind::single);
 extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed) { return create_model(backend, cfg, seed, nullptr); }
-// a B > 1 model of either kind (moshi_hot.h): the moshika-shaped LM only
+// a B > 1 model of either kind (moshi_hot.h): the LM alone, in the moshika shape (a Depth transformer, no extra heads) or the stt shape (no Depth
+// transformer: every codebook is an input, the text token is the Temporal head's; extra heads of at most 16 values each on transformer_out)
 static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int B, ModelKind kind) {
     if (!cfg || B < 2 || B > 16) return nullptr;
     const moshi_hot_config & c = *cfg;
-    const bool ok = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && !c.extra_heads && !c.demux_second_stream &&
-                    !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len && c.tp_world == 0 &&
-                    c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream && c.dep_q > 0 && c.n_q > c.dep_q;
-    if (!ok) return nullptr;
+    const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && !c.demux_second_stream &&
+                        !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len && c.tp_world == 0 &&
+                        c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream;
+    const bool moshika_shape = c.dep_q > 0 && c.n_q > c.dep_q && !c.extra_heads;
+    const bool stt_shape = c.dep_q == 0 && c.n_q > 0 && (c.extra_heads == 0 || (c.extra_heads >= 1 && c.extra_heads_dim >= 1 && c.extra_heads_dim <= 16));
+    if (!common || !(moshika_shape || stt_shape)) return nullptr;
     return create_model(backend, cfg, seed, nullptr, B, kind);
 }
 extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams) {
@@ -1256,11 +1269,13 @@ extern "C" void moshi_hot_sampling_noise(uint64_t seed, int64_t frame, int site,
     for (int r = 0; r < n; r++) out[r] = sampling_noise(seed, frame, site, r, 1.f);
 }
 static bool sampled_model(const moshi_hot_model * m) { return m->cfg.temp > 0.f && m->cfg.temp_text > 0.f; }
-// a single-stream model whose two persistent graphs hold every sampler of a frame: the moshika-shaped LM stepped by moshi_hot_lm_step* (blocking steps)
+// a single-stream model whose persistent graphs hold every sampler of a frame: the moshika-shaped LM stepped by moshi_hot_lm_step* (blocking steps), or the
+// stt-shaped one (no Depth transformer: the text head's sampler is the frame's only one; its extra heads draw nothing)
 static bool single_sampling_supported(const moshi_hot_model * m) {
     const moshi_hot_config & c = m->cfg;
-    return c.enable_lm && !c.personaplex && !c.extra_heads && !c.demux_second_stream && !c.depformer_low_rank && !c.delay_steps && !c.cross_attention &&
-           !c.condition_sum && !c.dep_schedule_len && c.tp_world <= 1 && c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && c.dep_q > 0;
+    const bool stt_shape = c.dep_q == 0 && c.n_q > 0;
+    return c.enable_lm && !c.personaplex && (stt_shape || !c.extra_heads) && !c.demux_second_stream && !c.depformer_low_rank && !c.delay_steps && !c.cross_attention &&
+           !c.condition_sum && !c.dep_schedule_len && c.tp_world <= 1 && c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && (stt_shape || c.dep_q > 0);
 }
 extern "C" int moshi_hot_set_sampling(moshi_hot_model_t * m, int b, const struct moshi_hot_sampling * s) {
     const moshi_hot_config & c = m->cfg;
@@ -1414,6 +1429,10 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         if (c.cross_attention) m->cond_cross = state(m, GGML_TYPE_F32, c.dim, c.cross_len);
         for (int k = 0; k < c.extra_heads; k++)
             m->extra_heads.push_back(W.add("lm.extra_heads." + std::to_string(k) + ".weight", lt, c.dim, c.extra_heads_dim, 1, qgen(1.f / sqrtf((float) c.dim))));
+        if (m->n_streams > 1 && c.extra_heads > 0) {
+            m->heads_out = state(m, GGML_TYPE_F32, c.extra_heads_dim, c.extra_heads, m->n_streams);
+            m->last_heads.assign((size_t) c.extra_heads_dim * (size_t) c.extra_heads * (size_t) m->n_streams, -1.f);
+        }
         if (c.dep_q > 0) {
             // depformer_num_weights (lm_default.h:71-81): one set per step, or max(schedule) + 1
             int n_sets = c.dep_q;
@@ -2175,7 +2194,8 @@ T causal_mask_block(Builder & s, int C, int64_t pos, int n) {
     return s.constant(s.tensor(GGML_TYPE_F32, C, n), mv.data());
 }
 // moshi_lmgen_step (lm.h:778-979) of a B > 1 model: the host half runs per column over the column's own delay ring, the Temporal and the Depth graph
-// once for all columns (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - create_columns refuses those). An open
+// once for all columns (a greedy / sampled moshika-shaped frame: no provided tokens, no hooks, no delay_steps - create_columns refuses those; the stt
+// shape, dep_q == 0, has no Depth graph: all n_q codes of a column are inputs, its text token is the frame's only sample, out_audio is not touched). An open
 // column takes its codes from in_audio and advances one frame; a closed one is fed the initial tokens at its frozen position and is left as it is.
 // A held slot (moshi_hot_slot_hold) is stepped as a closed one. status[b]: -1 closed, -2 held, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
 void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
@@ -2187,14 +2207,17 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
         status[b] = !col.open ? -1 : col.held ? -2 : 0;
         n_open += col.open && !col.held;
     }
+    m->last_heads.assign(m->last_heads.size(), -1.f);
     if (!n_open) return;
     if (!m->g_temporal) build_temporal_graph(m);
-    if (!m->g_depth) build_depth_graph_streams(m);
+    if (dep_q > 0 && !m->g_depth) build_depth_graph_streams(m);   // (the stt shape has no Depth transformer: the text token is all a frame samples)
     for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring
         auto & col = m->cols[(size_t) b];
         if (col.open && !col.held) col.ring.feed_user(in_audio + (size_t) b * needed, col.ring.frames);
     }
     std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q), audio((size_t) dep_q);
+    std::vector<float> heads(m->last_heads.size());
+    const size_t heads_row = heads.size() / (size_t) B;   // extra_heads x extra_heads_dim values per column
     {
     PhaseTimer pt(m, 1);
     for (int i = 0; i < ncb; i++) {
@@ -2214,8 +2237,9 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     stage_sampling(m);
     m->g_temporal->compute();
     ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
+    if (m->heads_out) ggml_backend_tensor_get(m->heads_out, heads.data(), 0, heads.size() * 4);   // (read back with the tokens: no second compute)
     }
-    {
+    if (dep_q > 0) {
     PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
     set_token_inputs(m->dep_text_idx, m->dep_text_scale, text);
     m->g_depth->compute();
@@ -2230,8 +2254,9 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
         col.ring.commit(text[(size_t) b], audio.data(), false);
         const DelayRing::ReadOut r = col.ring.read_out(&text_token_out[b], audio.data());
         if (r == DelayRing::ReadOut::filling) continue;
-        memcpy(out_audio + (size_t) b * dep_q, audio.data(), (size_t) dep_q * sizeof(int32_t));
+        if (dep_q > 0) memcpy(out_audio + (size_t) b * dep_q, audio.data(), (size_t) dep_q * sizeof(int32_t));
         status[b] = r == DelayRing::ReadOut::valid ? 1 : 0;
+        if (status[b] == 1 && heads_row) memcpy(m->last_heads.data() + (size_t) b * heads_row, heads.data() + (size_t) b * heads_row, heads_row * sizeof(float));
     }
 }
 }  // namespace
@@ -2257,6 +2282,13 @@ extern "C" int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in
         for (int q = 0; q < m->cfg.dep_q; q++) out_audio[(size_t) b * m->cfg.dep_q + q] = -1;
     }
     return n_valid;
+}
+
+// the extra heads' probabilities of the last B-column step (moshi_hot.h)
+extern "C" int moshi_hot_last_heads(moshi_hot_model_t * m, float * out, int64_t n) {
+    if (m->n_streams < 2 || !m->heads_out || !out || n < (int64_t) m->last_heads.size()) return -1;
+    memcpy(out, m->last_heads.data(), m->last_heads.size() * sizeof(float));
+    return (int) m->last_heads.size();
 }
 
 extern "C" void moshi_hot_lm_step_embedding(moshi_hot_model_t * m, const float * embedding) { STREAMS_REFUSE();

@@ -69,6 +69,7 @@ SIGNATURES = {
     "moshi_hot_slot_position": (C.c_int64, [P, C.c_int]),
     "moshi_hot_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
     "moshi_hot_lm_step_slots": (C.c_int, [P, P, P, P, P]),
+    "moshi_hot_last_heads": (C.c_int, [P, P, C.c_int64]),
     "moshi_hot_slots_prefill": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "moshi_hot_slot_prefill": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
     "moshi_hot_slot_hold": (C.c_int, [P, C.c_int, C.c_int]),
@@ -168,6 +169,15 @@ def tiny(lib, linear_type=12, embed_type=2, layers=2, dep_q=3, n_q=6, context=24
     cfg.dep_dim, cfg.dep_heads, cfg.dep_layers, cfg.dep_ffn_hidden, cfg.dep_context = 256, 4, 2, 512, dep_q
     cfg.linear_type, cfg.embed_type = linear_type, embed_type
     cfg.mimi_n_q, cfg.mimi_codebook_size = n_q - dep_q, 64
+    return cfg
+
+
+def tiny_stt(lib, linear_type=12, embed_type=2, layers=2, context=24):
+    """moshi-stt's structure (BASELINE.json configs[2]) at test widths: no Depth transformer, 8 input codebooks, 3 extra heads of width 6 on
+    transformer_out (the third is the VAD head), both codec halves off."""
+    cfg = tiny(lib, linear_type=linear_type, embed_type=embed_type, layers=layers, dep_q=0, n_q=8, context=context)
+    cfg.extra_heads, cfg.extra_heads_dim = 3, 6
+    cfg.enable_mimi_encoder = cfg.enable_mimi_decoder = 0
     return cfg
 
 
