@@ -100,14 +100,15 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 // model and a slots model (below) are this one model and step alike; they differ only in where a column's position comes from. Here every column
 // is open from creation and all B share one stream position, so the mask row, the RoPE phase and the ring slot are common.
 // n_streams == 1 builds exactly moshi_hot_create's model.
-// n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0, no demux / cross-attention / condition_sum /
-// low-rank embeddings / weight schedule / delay_steps, tp_world == 0, dep_shard_world <= 1, depth_only == 0, chain_depth == 0,
-// codec_stream == 0, and 1 <= n_streams <= 16, in one of two shapes:
+// n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0, tp_world == 0, dep_shard_world <= 1, depth_only == 0,
+// chain_depth == 0, codec_stream == 0, and 1 <= n_streams <= 16, in one of three shapes (demux / cross-attention / condition_sum / low-rank embeddings /
+// weight schedule / delay_steps: on the tts shape only, see "tts streams and slots" below):
 //  * the moshika shape: dep_q > 0, n_q > dep_q, extra_heads == 0;
 //  * the stt shape (moshi-stt): dep_q == 0 and n_q > 0 - no Depth transformer, every audio codebook is an input, the text token comes from the
 //    Temporal head - with extra_heads == 0, or extra_heads >= 1 heads of 1 <= extra_heads_dim <= 16 values on transformer_out (lm.h:966-976).
 //    A frame takes n_q codes per column, out_audio is not touched and may be NULL, the frame's only sampler site is 0 (the text head), and the
 //    heads' probabilities of every column are computed by the Temporal graph itself and read back with the tokens (moshi_hot_last_heads).
+//  * the tts shape (moshi-tts): dep_q > 0, n_q == dep_q, extra_heads == 0.
 // Anything else returns NULL.
 // On such a model moshi_hot_read_last("text_logits" | "transformer_out" | "dep_logits<k>") returns B consecutive rows (stream 0 first), and
 // moshi_hot_set_context_fill moves the shared stream position, not the delay rings. The single-stream frame calls (moshi_hot_lm_step*, moshi_hot_sts_*,
@@ -183,6 +184,29 @@ GGML_API int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold);
 GGML_API int     moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst);
 GGML_API int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes);
 GGML_API int     moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes);
+
+// ---- tts streams and slots: B text-to-speech conversations ------------------------------------------------------------------------------------
+// The tts shape of a B > 1 model: dep_q > 0 and n_q == dep_q - no codebook is an input (in_audio may be NULL), every column brings a voice
+// (condition_cross, condition_sum) and a text stream. On this shape alone, in any combination: cross_attention (cross_len >= 1), condition_sum,
+// demux_second_stream, depformer_low_rank, dep_schedule_len > 0 (dep_context == 0: ring = schedule length) and delay_steps >= 0, applied per column by the
+// column's own frame count: while it is below delay_steps the column is REPLACED (src/moshi.cpp:905, lm.h:910-921: its Depth tokens are -1, nothing is read
+// out; the Depth graph is skipped when every stepping column is replaced), and audio[q] = -1 while it is below delays[q + 1] + delay_steps.
+// moshi_hot_slots_prefill / _slot_prefill and moshi_hot_slot_fork / _save / _load return -1 on this shape and change nothing.
+//
+// Column b's conditions (the B > 1 form of moshi_hot_set_conditions, which does nothing on such a model): sum F32[dim] and cross F32[dim * cross_len], either
+// may be NULL to leave that half as it is. cross also runs init() (transformer.h:343-396) for column b of every layer's K / V. The setting belongs to
+// the column as the sampling setting does: it may be set on an open or a closed slot, holds from the next step on and survives moshi_hot_slot_close /
+// _open; no other column's state is touched. A column never set has zero conditions (a single-stream model before moshi_hot_set_conditions).
+// Returns 0, or -1 on a single-stream model, for a bad column, or when the model has no condition of the kind given.
+GGML_API int moshi_hot_set_conditions_column(moshi_hot_model_t * m, int b, const float * sum, const float * cross);
+// moshi_hot_lm_step_streams / _slots with the text stream from above the boundary (the B-column form of moshi_hot_set_text_hook: the TTS state machine
+// hands this frame's token of every column in): text_in = B values or NULL. text_in[b] != MOSHI_HOT_TEXT_KEEP replaces column b's sampled text token where
+// on_text_hook does (lm.h:880-900): after the Temporal graph, before the Depth graph and the delay ring's write. Values of closed or held columns are
+// ignored; text_in == NULL is the plain call. They work on every B > 1 shape (moshika shape: a forced text token); in_audio may be NULL on the tts shape.
+// Returns as the plain calls; moshi_hot_lm_step_streams_text returns -1 on a single-stream model too.
+#define MOSHI_HOT_TEXT_KEEP INT32_MIN
+GGML_API int moshi_hot_lm_step_streams_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token, int32_t * out_audio);
+GGML_API int moshi_hot_lm_step_slots_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token, int32_t * out_audio, int32_t * status);
 
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute

@@ -1285,14 +1285,17 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
     if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1) return false;
     const ggml_tensor * kx = kq->src[0], * qp = kq->src[1];
     if (kx->type != GGML_TYPE_F32 || vx->type != GGML_TYPE_F32 || !kx->data || !vx->data || pos_of(an, kx) >= 0 || pos_of(an, vx) >= 0) return false;   // cached state, not graph values
-    const int64_t D = kx->ne[0], Tc = kx->ne[1], H = kx->ne[2];
-    if (vx->ne[0] != D || vx->ne[1] != Tc || vx->ne[2] != H || kx->ne[3] != 1 || kx->nb[0] != 4 || vx->nb[0] != 4) return false;
-    // q: [D, 1, H] permuted view of a dense [D * H] vector
-    if (qp->ne[0] != D || qp->ne[1] != 1 || qp->ne[2] != H || qp->ne[3] != 1 || qp->type != GGML_TYPE_F32 || qp->nb[0] != 4 || (int64_t) qp->nb[2] != D * 4) return false;
+    // B columns (B-column LM steps): K / V [D, Tc, H, B], q [D, 1, H, B] over a dense [D * H, B], x2 [D, H, 1, B] - one (head, column) workgroup each
+    const int64_t D = kx->ne[0], Tc = kx->ne[1], H = kx->ne[2], B = kx->ne[3];
+    if (D < 1 || D > 256 || Tc < 1 || H < 1 || B < 1 || B > 65535) return false;
+    if (vx->ne[0] != D || vx->ne[1] != Tc || vx->ne[2] != H || vx->ne[3] != B || kx->nb[0] != 4 || vx->nb[0] != 4) return false;
+    // q: [D, 1, H(, B)] permuted view of a dense [D * H(, B)] vector
+    if (qp->ne[0] != D || qp->ne[1] != 1 || qp->ne[2] != H || qp->ne[3] != B || qp->type != GGML_TYPE_F32 || qp->nb[0] != 4 || (int64_t) qp->nb[2] != D * 4) return false;
+    if (B > 1 && (int64_t) qp->nb[3] != D * H * 4) return false;
     const ggml_tensor * qsrc = qp;
     while (is_view_op(qsrc->op) && qsrc->op != GGML_OP_NONE && qsrc->src[0]) { if (uses_of(an, qsrc) != 1) return false; qsrc = qsrc->src[0]; }
-    if (!is_f32_vec(qsrc, D * H) || qsrc->data != qp->data) return false;
-    if (x2->ne[0] != D || x2->ne[1] != H || ggml_nelements(x2) != D * H || !ggml_is_contiguous(x2)) return false;
+    if (!is_f32_vec(qsrc, D * H * B) || qsrc->ne[0] != D * H || qsrc->data != qp->data) return false;
+    if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != 1 || x2->ne[3] != B || !ggml_is_contiguous(x2)) return false;
     xattn_args & a = grp.a;
     a.q = (const float *) qp->data;
     a.k = (const char *) kx->data; a.v = (const char *) vx->data;
@@ -1300,6 +1303,7 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
     a.H = (int) H; a.D = (int) D; a.Tc = (int) Tc;
     a.scale = ggml_get_op_params_f32(sm, 0);
     a.out = (float *) x2->data;
+    a.B = (int) B; a.q_cs = D * H; a.out_cs = D * H; a.k_nb3 = (int64_t) kx->nb[3]; a.v_nb3 = (int64_t) vx->nb[3];
     grp.members = { pos, pos_of(an, pv), pos_of(an, vt), pos_of(an, sm), pos_of(an, kq) };
     for (int m : grp.members) if (m < 0) return false;
     grp.emit_pos = pos;
@@ -2394,10 +2398,14 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
         // ggml_norm -> ggml_mul(., w) -> [ggml_add(., b)] as one launch with the three launches' float operations
         for (int i = 0; i < g->n_nodes; i++) {
             const ggml_tensor * nn = g->nodes[i];
-            if (an.skip[(size_t) i] || (nn->op != GGML_OP_NORM && nn->op != GGML_OP_RMS_NORM) || nn->type != GGML_TYPE_F32 || ggml_nelements(nn) != nn->ne[0] || uses_of(an, nn) != 1) continue;
+            if (an.skip[(size_t) i] || (nn->op != GGML_OP_NORM && nn->op != GGML_OP_RMS_NORM) || nn->type != GGML_TYPE_F32 || uses_of(an, nn) != 1) continue;
             if (nn->src[0]->type != GGML_TYPE_F32 || nn->src[0]->nb[0] != 4) continue;
+            // one row, or the B contiguous rows of a B-column LM activation [dim, 1, B] under the same [dim] weight and bias (norm_cross of B-column tts
+            // steps), one workgroup per row. Only that layout and LayerNorm: every other multi-row norm keeps the plan it had.
+            const int64_t n_rows = ggml_nelements(nn) / nn->ne[0];
+            if (n_rows != 1 && (nn->op != GGML_OP_NORM || nn->ne[1] != 1 || nn->ne[2] != n_rows || n_rows > 16 || !ggml_is_contiguous(nn) || !ggml_is_contiguous(nn->src[0]))) continue;
             const ggml_tensor * ml = sole_consumer(an, nn);
-            if (!ml || ml->op != GGML_OP_MUL || ml->view_src || pos_of(an, ml) < 0 || an.skip[(size_t) pos_of(an, ml)]) continue;
+            if (!ml || ml->op != GGML_OP_MUL || ml->view_src || pos_of(an, ml) < 0 || an.skip[(size_t) pos_of(an, ml)] || !ggml_are_same_shape(ml, nn)) continue;
             const ggml_tensor * wv = ml->src[0] == nn ? ml->src[1] : ml->src[0];
             if (wv == nn || wv->type != GGML_TYPE_F32 || !ggml_is_contiguous(wv) || ggml_nelements(wv) != nn->ne[0] || !wv->data || !ggml_is_contiguous(ml)) continue;
             std::vector<int> members = { i, pos_of(an, ml) };
@@ -2405,7 +2413,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             const ggml_tensor * ad = uses_of(an, ml) == 1 ? sole_consumer(an, ml) : nullptr;
             if (ad && ad->op == GGML_OP_ADD && !ad->view_src && pos_of(an, ad) >= 0 && !an.skip[(size_t) pos_of(an, ad)] && ggml_is_contiguous(ad)) {
                 const ggml_tensor * bv = ad->src[0] == ml ? ad->src[1] : ad->src[0];
-                if (bv != ml && bv->type == GGML_TYPE_F32 && ggml_is_contiguous(bv) && ggml_nelements(bv) == nn->ne[0] && bv->data && bv->op == GGML_OP_NONE && ad->src[0] == ml) {
+                if (bv != ml && bv->type == GGML_TYPE_F32 && ggml_is_contiguous(bv) && ggml_nelements(bv) == nn->ne[0] && bv->data && bv->op == GGML_OP_NONE && ad->src[0] == ml && ggml_are_same_shape(ad, nn)) {
                     bp = (const float *) bv->data; last = ad; members.push_back(pos_of(an, ad));
                 }
             }

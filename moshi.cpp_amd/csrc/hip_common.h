@@ -235,7 +235,9 @@ void   k_inproj_attn(hipStream_t s, const mv_args & a, const attn_args & at, voi
 
 // single-token cross-attention over cached F32 K / V [D, Tc, H] without a mask (moshi_streaming_multihead_cross_attention,
 // transformer.h:714-762): scores = K q (float products, double sums), soft_max(scale * s), out = sum_t p_t V_t; one workgroup per head
-struct xattn_args { const float * q; const char * k; const char * v; int64_t k_nb1, k_nb2, v_nb1, v_nb2; int H, D, Tc; float scale; float * out; };
+// B > 1 (cross_attn_streams_kernel): column strides q_cs / out_cs in floats (q rows of a dense [D * H, B], out [D, H, 1, B]), k_nb3 / v_nb3 in bytes
+struct xattn_args { const float * q; const char * k; const char * v; int64_t k_nb1, k_nb2, v_nb1, v_nb2; int H, D, Tc; float scale; float * out;
+                    int B = 1; int64_t q_cs = 0, out_cs = 0, k_nb3 = 0, v_nb3 = 0; };
 void k_cross_attn(hipStream_t s, const xattn_args & a);
 
 // sum of (scaled) embedding rows, left-to-right

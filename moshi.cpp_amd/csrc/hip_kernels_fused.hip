@@ -2159,16 +2159,15 @@ void k_inproj_attn(hipStream_t s, const mv_args & a, const attn_args & at, void 
 // mul_mat(cont(transpose(V)), p) -> cont(permute) with the per-op kernels' arithmetic (float products summed in double, expf of
 // scale * s - max, probabilities scaled by float(1 / sum)), without materialising the transposed V every frame
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) cross_attn_kernel(xattn_args a) {
-    extern __shared__ float xsm[];          // [D] q | [Tc] scores -> probabilities
-    __shared__ float sh_f[4];
-    __shared__ double sh_d[4];
-    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// one (head, column) pair: q = the head's D query values, kh / vh = its [D, Tc] condition rows, out = its D results. Shared by the single-column launch
+// and the B-column one, which is B x H of these in one grid - the same operations in the same order, so a column's result does not depend on B.
+__device__ __forceinline__ void cross_attn_body(const xattn_args & a, const float * __restrict__ q, const char * __restrict__ kh, const char * __restrict__ vh,
+                                                float * __restrict__ out, float * xsm, float * sh_f, double * sh_d) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = a.D, Tc = a.Tc;
     float * qs = xsm, * sc = xsm + D;
-    for (int d = tid; d < D; d += 256) qs[d] = a.q[(int64_t) h * D + d];
+    for (int d = tid; d < D; d += 256) qs[d] = q[d];
     __syncthreads();
-    const char * kh = a.k + (int64_t) h * a.k_nb2, * vh = a.v + (int64_t) h * a.v_nb2;
     // scores: a wave takes four condition rows at a time so that their loads travel together (one round trip per four rows, not per row)
     for (int t0 = wave * 4; t0 < Tc; t0 += 16) {
         double acc[4] = { 0, 0, 0, 0 };
@@ -2220,15 +2219,32 @@ __global__ void __launch_bounds__(256) cross_attn_kernel(xattn_args a) {
         if (tid < D) {
             double tot = 0;
             for (int gi = 0; gi < G; gi++) tot += part[gi * D + tid];
-            a.out[(int64_t) h * D + tid] = (float) tot;
+            out[tid] = (float) tot;
         }
     }
 }
+__global__ void __launch_bounds__(256) cross_attn_kernel(xattn_args a) {
+    extern __shared__ float xsm[];          // [D] q | [Tc] scores -> probabilities
+    __shared__ float sh_f[4];
+    __shared__ double sh_d[4];
+    const int h = blockIdx.x;
+    cross_attn_body(a, a.q + (int64_t) h * a.D, a.k + (int64_t) h * a.k_nb2, a.v + (int64_t) h * a.v_nb2, a.out + (int64_t) h * a.D, xsm, sh_f, sh_d);
+}
+// B columns: workgroup (h, b) is cross_attn_kernel's workgroup h over column b's query, K / V [D, Tc, H, B] and out [D, H, 1, B]
+__global__ void __launch_bounds__(256) cross_attn_streams_kernel(xattn_args a) {
+    extern __shared__ float xsm[];
+    __shared__ float sh_f[4];
+    __shared__ double sh_d[4];
+    const int h = blockIdx.x, b = blockIdx.y;
+    cross_attn_body(a, a.q + (int64_t) b * a.q_cs + (int64_t) h * a.D, a.k + (int64_t) b * a.k_nb3 + (int64_t) h * a.k_nb2,
+                    a.v + (int64_t) b * a.v_nb3 + (int64_t) h * a.v_nb2, a.out + (int64_t) b * a.out_cs + (int64_t) h * a.D, xsm, sh_f, sh_d);
+}
 void k_cross_attn(hipStream_t s, const xattn_args & a) {
-    GGML_ASSERT(a.D <= 256);
+    GGML_ASSERT(a.D >= 1 && a.D <= 256 && a.Tc >= 1 && a.H >= 1 && a.B >= 1);
     const size_t smem = (size_t) ((a.D + a.Tc + 1) & ~1) * 4 + (size_t) (256 / a.D > 0 ? 256 / a.D : 1) * a.D * 8;
     GGML_ASSERT(smem <= 64 * 1024);
-    cross_attn_kernel<<<a.H, 256, smem, s>>>(a);
+    if (a.B == 1) cross_attn_kernel<<<a.H, 256, smem, s>>>(a);
+    else cross_attn_streams_kernel<<<dim3((unsigned) a.H, (unsigned) a.B), 256, smem, s>>>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -446,7 +446,7 @@ __global__ void norm_kernel(tdesc dst, tdesc a, float eps, int rms, const float 
         float v = (x[i] - mean) * scale;
         v = v * w[i];
         if (b) v = v + b[i];
-        out[i] = v;
+        out[(int64_t) blockIdx.x * n + i] = v;   // (rows of the affine form are contiguous: k_norm_affine)
     }
 }
 void k_norm(hipStream_t s, tdesc dst, tdesc a, float eps, int rms) {
@@ -454,10 +454,11 @@ void k_norm(hipStream_t s, tdesc dst, tdesc a, float eps, int rms) {
     GGML_ASSERT(a.nb[0] == 4 && dst.nb[0] == 4);
     if (rows) norm_kernel<<<(int) rows, BLOCK, 0, s>>>(dst, a, eps, rms);
 }
-// one row: out = norm(a) * w (+ b)
+// every row (one workgroup each): out = norm(a) * w (+ b), w / b [ne0] shared by the rows, out contiguous
 void k_norm_affine(hipStream_t s, tdesc a, float eps, int rms, const float * w, const float * b, float * out) {
-    GGML_ASSERT(a.nb[0] == 4 && a.ne[1] * a.ne[2] * a.ne[3] == 1);
-    norm_kernel<<<1, BLOCK, 0, s>>>(a, a, eps, rms, w, b, out);
+    const int64_t rows = a.ne[1] * a.ne[2] * a.ne[3];
+    GGML_ASSERT(a.nb[0] == 4 && rows >= 1 && rows <= 65535);
+    norm_kernel<<<(int) rows, BLOCK, 0, s>>>(a, a, eps, rms, w, b, out);
 }
 
 __global__ void soft_max_kernel(tdesc dst, tdesc a, tdesc mask, int has_mask, float scale) {

@@ -521,7 +521,13 @@ T cross_attention(Builder & c, const Transformer & tr, Layer & L, T query) {
 }
 
 // init() of the cross-attention state (transformer.h:343-396): K/V = last two thirds of in_proj applied to condition_cross
+void init_cross_expand(Builder & s, const Transformer & tr, Layer & L, T condition_cross, T k_dst, T v_dst);
 void init_cross(Builder & s, const Transformer & tr, Layer & L, T condition_cross) {
+    init_cross_expand(s, tr, L, condition_cross, L.k_cross, L.v_cross);
+    s.compute_scratch();
+}
+// the graph of init() for one layer, into k_dst / v_dst [D, Tc, H] (the layer's states, or one column of them on a B > 1 model)
+void init_cross_expand(Builder & s, const Transformer & tr, Layer & L, T condition_cross, T k_dst, T v_dst) {
     const int H = tr.heads, dim = (int) L.cross_in->ne[1] / 3;
     T kv = linear_view(s, L.cross_in, dim, 2 * dim, condition_cross);
     auto half = [&](size_t off) {
@@ -530,9 +536,8 @@ void init_cross(Builder & s, const Transformer & tr, Layer & L, T condition_cros
         t = ggml_reshape_4d(s, t, t->ne[0] / H, H, t->ne[1], t->ne[2]);
         return ggml_permute(s, t, 0, 2, 1, 3);
     };
-    s.expand(ggml_cpy(s, half(0), L.k_cross));
-    s.expand(ggml_cpy(s, half(kv->nb[1] / 2), L.v_cross));
-    s.compute_scratch();
+    s.expand(ggml_cpy(s, half(0), k_dst));
+    s.expand(ggml_cpy(s, half(kv->nb[1] / 2), v_dst));
 }
 
 // moshi_streaming_transformer_layer (transformer.h:910-1039)
@@ -957,8 +962,13 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
                              W.add(p + "norm_cross.bias", GGML_TYPE_F32, dim, 1, 1, [](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, 0.02f); }) };
             L.cross_in = W.add(p + "cross_attention.in_projs.0.weight", wtype, dim, 3 * dim, 1, qgen(s_in));
             L.cross_out = W.add(p + "cross_attention.out_projs.0.weight", wtype, dim, dim, 1, qgen(s_in * upd));   // a residual update like out_proj / linear_out
-            L.k_cross = state(m, GGML_TYPE_F32, dim / heads, cross_len, heads);
-            L.v_cross = state(m, GGML_TYPE_F32, dim / heads, cross_len, heads);
+            if (m->n_streams > 1) {   // one condition per column
+                L.k_cross = state4(m, GGML_TYPE_F32, dim / heads, cross_len, heads, m->n_streams);
+                L.v_cross = state4(m, GGML_TYPE_F32, dim / heads, cross_len, heads, m->n_streams);
+            } else {
+                L.k_cross = state(m, GGML_TYPE_F32, dim / heads, cross_len, heads);
+                L.v_cross = state(m, GGML_TYPE_F32, dim / heads, cross_len, heads);
+            }
         }
     }
 }
@@ -1011,10 +1021,10 @@ T build_input_embedding(moshi_hot_model * m, Builder & g) {
         return ggml_mul(g, ggml_get_rows(g, table, idx), scale);
     };
     T input;
-    if (c.demux_second_stream) {   // moshi_scaled_embedding_demux_build (lm_utils.h:48-66)
-        T left = g.tensor(GGML_TYPE_I32, 1);
+    if (c.demux_second_stream) {   // moshi_scaled_embedding_demux_build (lm_utils.h:48-66); B > 1: B left and right indices, one right scale per column
+        T left = g.tensor(GGML_TYPE_I32, B);
         m->emb_idx.push_back(left); m->emb_scale.push_back(nullptr);
-        m->emb_right_idx = g.tensor(GGML_TYPE_I32, 1); m->emb_right_scale = g.tensor(GGML_TYPE_F32, 1);
+        m->emb_right_idx = g.tensor(GGML_TYPE_I32, B); m->emb_right_scale = B > 1 ? g.tensor(GGML_TYPE_F32, 1, B) : g.tensor(GGML_TYPE_F32, 1);
         T l = ggml_get_rows(g, m->text_emb, left), r = ggml_get_rows(g, m->text_emb, m->emb_right_idx);
         T ry = linear(g, m->text_out2, r), ly = linear(g, m->text_out1, l);
         input = ggml_add(g, ly, ggml_mul(g, ry, m->emb_right_scale));
@@ -1104,15 +1114,28 @@ void build_depth_graph_streams(moshi_hot_model * m) {
     m->g_depth = new Builder(m->be, 256);
     Builder & g = *m->g_depth;
     m->dep_text_idx = g.tensor(GGML_TYPE_I32, B);
-    m->dep_text_scale = g.tensor(GGML_TYPE_F32, 1, B);
-    T last = ggml_mul(g, ggml_get_rows(g, m->depformer_text_emb, m->dep_text_idx), m->dep_text_scale);   // [E, B]
+    T last;
+    if (c.demux_second_stream) {   // tts: the demuxed text embedding (lm_utils.h:48-66), B left and right indices, one right scale per column
+        m->dep_right_idx = g.tensor(GGML_TYPE_I32, B); m->dep_right_scale = g.tensor(GGML_TYPE_F32, 1, B);
+        T l = ggml_get_rows(g, m->depformer_text_emb, m->dep_text_idx), r = ggml_get_rows(g, m->depformer_text_emb, m->dep_right_idx);   // [E, B]
+        T ry = linear(g, m->dep_text_out2, r), ly = linear(g, m->dep_text_out1, l);                                                      // [dep_dim, B]
+        last = ggml_add(g, ly, ggml_mul(g, ry, m->dep_right_scale));
+    } else {
+        m->dep_text_scale = g.tensor(GGML_TYPE_F32, 1, B);
+        last = ggml_mul(g, ggml_get_rows(g, m->depformer_text_emb, m->dep_text_idx), m->dep_text_scale);   // [E, B]
+        if (m->dep_text_low_rank) last = linear(g, m->dep_text_low_rank, last);                            // tts: low-rank embeddings (lm_utils.h:157-217)
+    }
     T tokens = g.tensor(GGML_TYPE_I32, (int64_t) B * c.dep_q);
     if (c.temp > 0.f) { m->inv_temp = g.tensor(GGML_TYPE_F32, 1, B); m->sampling_dirty = true; }
     T view = nullptr, next = nullptr;
     for (int k = 0; k < c.dep_q; k++) {
-        if (k > 0) last = ggml_get_rows(g, m->depformer_emb[(size_t) (k - 1)], next);   // moshi_scaled_embedding_chained (lm_utils.h:208-217)
+        if (k > 0) {   // moshi_scaled_embedding_chained (lm_utils.h:208-217)
+            last = ggml_get_rows(g, m->depformer_emb[(size_t) (k - 1)], next);
+            if (!m->depformer_emb_low_rank.empty()) last = linear(g, m->depformer_emb_low_rank[(size_t) (k - 1)], last);
+        }
         // moshi_lmmodel_forward_depformer_transform (lm.h:446-475)
-        T din = linear(g, m->depformer_in[(size_t) k], m->transformer_out);           // [dep_dim, 1, B]
+        const int in_index = c.dep_schedule_len ? c.dep_schedule[k] : k;
+        T din = linear(g, m->depformer_in[(size_t) in_index], m->transformer_out);    // [dep_dim, 1, B]
         last = ggml_cast(g, last, GGML_TYPE_F32);
         din = ggml_add(g, din, ggml_reshape_3d(g, last, last->ne[0], 1, B));
         T dout = transformer_inline(g, m->depth, din);
@@ -1224,12 +1247,17 @@ extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const st
 static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int B, ModelKind kind) {
     if (!cfg || B < 2 || B > 16) return nullptr;
     const moshi_hot_config & c = *cfg;
-    const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && !c.demux_second_stream &&
-                        !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len && c.tp_world == 0 &&
+    const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && c.tp_world == 0 &&
                         c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream;
-    const bool moshika_shape = c.dep_q > 0 && c.n_q > c.dep_q && !c.extra_heads;
-    const bool stt_shape = c.dep_q == 0 && c.n_q > 0 && (c.extra_heads == 0 || (c.extra_heads >= 1 && c.extra_heads_dim >= 1 && c.extra_heads_dim <= 16));
-    if (!common || !(moshika_shape || stt_shape)) return nullptr;
+    // the tts branches: on the tts shape alone, in any combination
+    const bool no_tts = !c.demux_second_stream && !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len;
+    const bool moshika_shape = c.dep_q > 0 && c.n_q > c.dep_q && !c.extra_heads && no_tts;
+    const bool stt_shape = c.dep_q == 0 && c.n_q > 0 && (c.extra_heads == 0 || (c.extra_heads >= 1 && c.extra_heads_dim >= 1 && c.extra_heads_dim <= 16)) && no_tts;
+    // the tts shape (moshi-tts): no codebook is an input; a voice (condition_cross, condition_sum) and a text stream per column
+    const bool tts_shape = c.dep_q > 0 && c.n_q == c.dep_q && !c.extra_heads && c.delay_steps >= 0 && c.depformer_low_rank >= 0 &&
+                           (!c.cross_attention || c.cross_len >= 1) && c.dep_schedule_len >= 0 && c.dep_schedule_len <= MOSHI_HOT_MAX_CODEBOOKS &&
+                           (c.dep_schedule_len == 0 || c.dep_schedule_len >= c.dep_q);
+    if (!common || !(moshika_shape || stt_shape || tts_shape)) return nullptr;
     return create_model(backend, cfg, seed, nullptr, B, kind);
 }
 extern "C" moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams) {
@@ -1240,6 +1268,8 @@ extern "C" int moshi_hot_n_streams(moshi_hot_model_t * m) { return m->n_streams;
 extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
     return create_columns(backend, cfg, seed, n_slots, ModelKind::slots);
 }
+// the tts shape of a B > 1 model (no codebook is an input): a conversation's conditions would have to travel with its prefill or snapshot, which refuse it
+static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m->cfg.n_q == m->cfg.dep_q; }
 // slot b of a slots model, or NULL (a bad index or a model of another kind)
 static moshi_hot_model::Column * slot(moshi_hot_model_t * m, int b) {
     return m->kind == ModelKind::slots && b >= 0 && b < m->n_streams ? &m->cols[(size_t) b] : nullptr;
@@ -1425,8 +1455,8 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         }
         m->transformer_out = m->n_streams > 1 ? state(m, GGML_TYPE_F32, c.dim, 1, m->n_streams) : state(m, GGML_TYPE_F32, c.dim);
         if (c.chain_depth) m->tok_state = state(m, GGML_TYPE_I32, 1 + c.dep_q);
-        if (c.condition_sum) m->cond_sum = state(m, GGML_TYPE_F32, c.dim);
-        if (c.cross_attention) m->cond_cross = state(m, GGML_TYPE_F32, c.dim, c.cross_len);
+        if (c.condition_sum) m->cond_sum = state(m, GGML_TYPE_F32, c.dim, m->n_streams);                    // B > 1: one column per conversation
+        if (c.cross_attention) m->cond_cross = state(m, GGML_TYPE_F32, c.dim, c.cross_len, m->n_streams);
         for (int k = 0; k < c.extra_heads; k++)
             m->extra_heads.push_back(W.add("lm.extra_heads." + std::to_string(k) + ".weight", lt, c.dim, c.extra_heads_dim, 1, qgen(1.f / sqrtf((float) c.dim))));
         if (m->n_streams > 1 && c.extra_heads > 0) {
@@ -1596,6 +1626,20 @@ void demux_set(const moshi_hot_config & c, int32_t input, T left, T right, T rig
     ggml_backend_tensor_set(left, &l, 0, 4);
     ggml_backend_tensor_set(right, &r, 0, 4);
     ggml_backend_tensor_set(right_scale, &sc, 0, 4);
+}
+// the same for the B columns of a B > 1 model: left / right I32 [B], right_scale F32 [1, B]
+void demux_set_columns(const moshi_hot_config & c, const std::vector<int32_t> & inputs, T left, T right, T right_scale) {
+    const int32_t n = c.text_card + 1;
+    std::vector<int32_t> l(inputs.size()), r(inputs.size()); std::vector<float> sc(inputs.size());
+    for (size_t b = 0; b < inputs.size(); b++) {
+        const int32_t input = inputs[b] < 0 ? 0 : inputs[b];
+        l[b] = input % n; r[b] = input / n - 1;
+        sc[b] = r[b] < 0 ? 0.f : 1.f;
+        if (r[b] < 0) r[b] = 0;
+    }
+    ggml_backend_tensor_set(left, l.data(), 0, l.size() * 4);
+    ggml_backend_tensor_set(right, r.data(), 0, r.size() * 4);
+    ggml_backend_tensor_set(right_scale, sc.data(), 0, sc.size() * 4);
 }
 void depth_step(moshi_hot_model * m, int32_t text_token, std::vector<int32_t> & audio) {   // moshi_lmmodel_depformer_step (lm.h:532-552)
     PhaseTimer pt(m, 2);
@@ -2198,7 +2242,11 @@ T causal_mask_block(Builder & s, int C, int64_t pos, int n) {
 // shape, dep_q == 0, has no Depth graph: all n_q codes of a column are inputs, its text token is the frame's only sample, out_audio is not touched). An open
 // column takes its codes from in_audio and advances one frame; a closed one is fed the initial tokens at its frozen position and is left as it is.
 // A held slot (moshi_hot_slot_hold) is stepped as a closed one. status[b]: -1 closed, -2 held, 1 valid, else 0. text_token_out / out_audio are written for every open column whose delay ring is full. No column open: no work.
-void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
+// text_in (B values or NULL): where text_in[b] != MOSHI_HOT_TEXT_KEEP it replaces stepping column b's sampled text token where on_text_hook would
+// (lm.h:880-900): after the Temporal graph, before the Depth graph and the ring write. tts shape: a column inside its first delay_steps frames is
+// REPLACED (src/moshi.cpp:905, lm.h:910-921) - its Depth tokens are -1; the Depth graph is skipped when every stepping column is, else it runs for all
+// columns and the replaced ones' results are dropped (the Depth rings start afresh every frame).
+void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     const moshi_hot_config & c = m->cfg;
     const int B = m->n_streams, ncb = c.n_q + 1, dep_q = c.dep_q, needed = m->proto.needed();
     int n_open = 0;
@@ -2213,7 +2261,7 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     if (dep_q > 0 && !m->g_depth) build_depth_graph_streams(m);   // (the stt shape has no Depth transformer: the text token is all a frame samples)
     for (int b = 0; b < B; b++) {   // other speaker's codes enter each open column's delay ring
         auto & col = m->cols[(size_t) b];
-        if (col.open && !col.held) col.ring.feed_user(in_audio + (size_t) b * needed, col.ring.frames);
+        if (needed > 0 && col.open && !col.held) col.ring.feed_user(in_audio + (size_t) b * needed, col.ring.frames);
     }
     std::vector<int32_t> ids((size_t) B), text((size_t) B), toks((size_t) B * dep_q), audio((size_t) dep_q);
     std::vector<float> heads(m->last_heads.size());
@@ -2225,7 +2273,8 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
             const auto & col = m->cols[(size_t) b];
             ids[(size_t) b] = !col.open || col.held ? m->proto.initial[(size_t) i] : col.ring.input(i, col.ring.frames);
         }
-        set_token_inputs(m->emb_idx[(size_t) i], m->emb_scale[(size_t) i], ids);
+        if (i == 0 && c.demux_second_stream) demux_set_columns(c, ids, m->emb_idx[0], m->emb_right_idx, m->emb_right_scale);
+        else set_token_inputs(m->emb_idx[(size_t) i], m->emb_scale[(size_t) i], ids);
     }
     if (m->kind == ModelKind::lockstep) transformer_graph_step_at(*m->scratch, m->temporal, 1, (int) m->cols[0].pos);   // one shared position
     else {
@@ -2239,9 +2288,19 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
     ggml_backend_tensor_get(m->sampler_out, text.data(), 0, (size_t) B * 4);
     if (m->heads_out) ggml_backend_tensor_get(m->heads_out, heads.data(), 0, heads.size() * 4);   // (read back with the tokens: no second compute)
     }
-    if (dep_q > 0) {
+    std::vector<char> replace((size_t) B, 0);   // depformer_replace_tokens (src/moshi.cpp:905), by the column's own clock
+    int n_depth = 0;
+    for (int b = 0; b < B; b++) {
+        const auto & col = m->cols[(size_t) b];
+        if (!col.open || col.held) continue;
+        if (text_in && text_in[b] != MOSHI_HOT_TEXT_KEEP) text[(size_t) b] = text_in[b];
+        replace[(size_t) b] = col.ring.frames < c.delay_steps;
+        n_depth += !replace[(size_t) b];
+    }
+    if (dep_q > 0 && n_depth > 0) {
     PhaseTimer pt(m, 2);   // moshi_lmmodel_depformer_step (lm.h:532-552)
-    set_token_inputs(m->dep_text_idx, m->dep_text_scale, text);
+    if (c.demux_second_stream) demux_set_columns(c, text, m->dep_text_idx, m->dep_right_idx, m->dep_right_scale);
+    else set_token_inputs(m->dep_text_idx, m->dep_text_scale, text);
     m->g_depth->compute();
     ggml_backend_tensor_get(m->dep_tokens, toks.data(), 0, toks.size() * 4);   // [dep_q][B]
     }
@@ -2250,9 +2309,12 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
         auto & col = m->cols[(size_t) b];
         if (!col.open || col.held) continue;
         col.pos++;
-        for (int q = 0; q < dep_q; q++) audio[(size_t) q] = toks[(size_t) q * B + b];
+        const int64_t offset = col.ring.frames;
+        for (int q = 0; q < dep_q; q++) audio[(size_t) q] = replace[(size_t) b] ? -1 : toks[(size_t) q * B + b];   // lm.h:910-913
+        if (c.delay_steps)                                                                                       // on_audio_hook (lm.h:915-921)
+            for (int q = 0; q < dep_q; q++) if (offset < c.delays[q + 1] + c.delay_steps) audio[(size_t) q] = -1;
         col.ring.commit(text[(size_t) b], audio.data(), false);
-        const DelayRing::ReadOut r = col.ring.read_out(&text_token_out[b], audio.data());
+        const DelayRing::ReadOut r = replace[(size_t) b] ? DelayRing::ReadOut::filling : col.ring.read_out(&text_token_out[b], audio.data());
         if (r == DelayRing::ReadOut::filling) continue;
         if (dep_q > 0) memcpy(out_audio + (size_t) b * dep_q, audio.data(), (size_t) dep_q * sizeof(int32_t));
         status[b] = r == DelayRing::ReadOut::valid ? 1 : 0;
@@ -2262,19 +2324,26 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, int32_t * te
 }  // namespace
 
 // B lockstep streams: 1 when every stream's outputs are valid, else 0 (the outputs are written once the delay rings are full, -1 tokens included)
+extern "C" int moshi_hot_lm_step_streams_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token_out, int32_t * out_audio) {
+    if (m->kind != ModelKind::lockstep) return -1;   // (slots: moshi_hot_lm_step_slots_text; one stream: moshi_hot_set_text_hook)
+    std::vector<int32_t> status((size_t) m->n_streams);
+    lm_step_columns(m, in_audio, text_in, text_token_out, out_audio, status.data());
+    for (int32_t s : status) if (s != 1) return 0;
+    return 1;
+}
 extern "C" int moshi_hot_lm_step_streams(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio) {
     if (m->kind == ModelKind::slots) return -1;   // (moshi_hot_lm_step_slots)
     if (m->kind == ModelKind::single) return moshi_hot_lm_step(m, in_audio, text_token_out, out_audio);
-    std::vector<int32_t> status((size_t) m->n_streams);
-    lm_step_columns(m, in_audio, text_token_out, out_audio, status.data());
-    for (int32_t s : status) if (s != 1) return 0;
-    return 1;
+    return moshi_hot_lm_step_streams_text(m, in_audio, nullptr, text_token_out, out_audio);
 }
 
 // B stream slots: the number of slots with status 1; the outputs of every other slot are -1
 extern "C" int moshi_hot_lm_step_slots(moshi_hot_model_t * m, const int32_t * in_audio, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
+    return moshi_hot_lm_step_slots_text(m, in_audio, nullptr, text_token_out, out_audio, status);
+}
+extern "C" int moshi_hot_lm_step_slots_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     if (m->kind != ModelKind::slots) return -1;
-    lm_step_columns(m, in_audio, text_token_out, out_audio, status);
+    lm_step_columns(m, in_audio, text_in, text_token_out, out_audio, status);
     int n_valid = 0;
     for (int b = 0; b < m->n_streams; b++) {
         if (status[b] == 1) { n_valid++; continue; }
@@ -2331,6 +2400,26 @@ extern "C" void moshi_hot_set_conditions(moshi_hot_model_t * m, const float * su
         ggml_backend_tensor_set(m->cond_cross, cross, 0, (size_t) c.dim * (size_t) c.cross_len * 4);
         for (auto & L : m->temporal.layers) init_cross(*m->scratch, m->temporal, L, m->cond_cross);
     }
+}
+// one column's conditions on a B > 1 model (moshi_hot.h): column b of cond_sum / cond_cross, then init() of the cross-attention state (transformer.h:343-396)
+// for that column alone, every layer in one scratch compute
+extern "C" int moshi_hot_set_conditions_column(moshi_hot_model_t * m, int b, const float * sum, const float * cross) {
+    const moshi_hot_config & c = m->cfg;
+    if (m->n_streams < 2 || b < 0 || b >= m->n_streams || (!m->cond_sum && !m->cond_cross) || (sum && !m->cond_sum) || (cross && !m->cond_cross)) return -1;
+    if (sum) ggml_backend_tensor_set(m->cond_sum, sum, (size_t) b * m->cond_sum->nb[1], (size_t) c.dim * 4);
+    if (cross) {
+        T cc = m->cond_cross;
+        ggml_backend_tensor_set(cc, cross, (size_t) b * cc->nb[2], (size_t) c.dim * (size_t) c.cross_len * 4);
+        Builder & s = *m->scratch;
+        T col = ggml_view_3d(s, cc, cc->ne[0], cc->ne[1], 1, cc->nb[1], cc->nb[2], (size_t) b * cc->nb[2]);
+        for (auto & L : m->temporal.layers) {
+            T k = L.k_cross, v = L.v_cross;
+            init_cross_expand(s, m->temporal, L, col, ggml_view_3d(s, k, k->ne[0], k->ne[1], k->ne[2], k->nb[1], k->nb[2], (size_t) b * k->nb[3]),
+                              ggml_view_3d(s, v, v->ne[0], v->ne[1], v->ne[2], v->nb[1], v->nb[2], (size_t) b * v->nb[3]));
+        }
+        s.compute_scratch();
+    }
+    return 0;
 }
 extern "C" void moshi_hot_set_text_hook(moshi_hot_model_t * m, moshi_hot_text_hook_t hook, void * user) { STREAMS_REFUSE(); m->text_hook = hook; m->text_hook_user = user; }
 
@@ -2452,7 +2541,7 @@ void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
 }  // namespace
 
 extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
-    if (m->kind != ModelKind::slots || n_jobs < 0 || n_jobs > m->n_streams) return -1;
+    if (m->kind != ModelKind::slots || tts_shape(m) || n_jobs < 0 || n_jobs > m->n_streams) return -1;
     const int ncb = m->cfg.n_q + 1;
     int total = 0;
     for (int j = 0; j < n_jobs; j++) {
@@ -2569,7 +2658,7 @@ void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const vo
 
 extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) {
     moshi_hot_model::Column * a = slot(m, src), * b = slot(m, dst);
-    if (!a || !b || src == dst || !a->open || b->open) return -1;
+    if (!a || !b || src == dst || !a->open || b->open || tts_shape(m)) return -1;
     slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr);
     *b = *a;
     b->held = false;
@@ -2580,7 +2669,7 @@ extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) {
 
 extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) {
     const moshi_hot_model::Column * col = slot(m, b);
-    if (!col || !col->open || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || !col->open || tts_shape(m) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m), total = host + slot_ring_bytes(m, n);
     if (!buf) return total;
     if (nbytes < total) return -1;
@@ -2601,7 +2690,7 @@ extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf,
 
 extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) {
     moshi_hot_model::Column * col = slot(m, b);
-    if (!col || col->open || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || col->open || tts_shape(m) || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     const uint8_t * in = (const uint8_t *) buf;
     SlotBlobHeader h;
     memcpy(&h, in, sizeof(h));

@@ -45,6 +45,17 @@ def get_sampling(lib, model, b):
     return (s.seed, s.temp, s.temp_text, s.top_k, s.top_k_text, bool(seeded.value))
 
 
+TEXT_KEEP = -2 ** 31   # MOSHI_HOT_TEXT_KEEP
+
+
+def set_conditions_column(lib, model, b, sum=None, cross=None):
+    """moshi_hot_set_conditions_column: sum float32 [dim], cross float32 [cross_len, dim] (numpy arrays; None leaves that half) -> 0 or -1"""
+    import numpy as np
+    s = None if sum is None else np.ascontiguousarray(sum, np.float32)
+    x = None if cross is None else np.ascontiguousarray(cross, np.float32)
+    return lib.moshi_hot_set_conditions_column(model, b, None if s is None else s.ctypes.data, None if x is None else x.ctypes.data)
+
+
 P = C.c_void_p
 SIGNATURES = {
     "moshi_hot_config_moshika": (None, [C.POINTER(Config)]),
@@ -70,6 +81,9 @@ SIGNATURES = {
     "moshi_hot_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
     "moshi_hot_lm_step_slots": (C.c_int, [P, P, P, P, P]),
     "moshi_hot_last_heads": (C.c_int, [P, P, C.c_int64]),
+    "moshi_hot_set_conditions_column": (C.c_int, [P, C.c_int, P, P]),
+    "moshi_hot_lm_step_streams_text": (C.c_int, [P, P, P, P, P]),
+    "moshi_hot_lm_step_slots_text": (C.c_int, [P, P, P, P, P, P]),
     "moshi_hot_slots_prefill": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "moshi_hot_slot_prefill": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
     "moshi_hot_slot_hold": (C.c_int, [P, C.c_int, C.c_int]),
