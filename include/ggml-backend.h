@@ -154,6 +154,10 @@ GGML_API void ggml_backend_mi355x_set_flags(ggml_backend_t backend, int flags);
 // hipGraph capture of repeated graphs on / off without touching cached plans (off: a repeated graph still reuses its plan, launched eagerly -
 // for sequences of same-shaped one-off graphs such as prompt-prefill chunks, where a capture costs more than it saves). No-op on other backends.
 GGML_API void ggml_backend_mi355x_set_capture(ggml_backend_t backend, int enabled);
+// The widest B-column sampler graph (moshi_sample_token over a batch dimension) that this handle plans as ONE launch: 16 on a fresh handle, as before
+// graphs of more columns existed (those run their node chain, with the same tokens); a model of 17 .. 64 columns raises it to its width for the
+// handle it was created on. Values are clamped to 16 .. 64; plans made so far are kept. No-op on other backends.
+GGML_API void ggml_backend_mi355x_set_max_columns(ggml_backend_t backend, int n_columns);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 // Makes the backend's HIP device current on the calling thread. A caller that talks to another HIP-based library itself on this backend's stream (RCCL:

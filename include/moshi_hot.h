@@ -78,6 +78,10 @@ struct moshi_hot_config {
     // moshi_hot_sts_pipeline_frame runs AHEAD: step k is queued before step k - 1's tokens have been read (moshika-shaped models only; anything else
     // falls back to blocking steps behind the same calls).
     int32_t chain_depth;
+    // moshi_hot_create_streams / moshi_hot_create_slots: 0 = at most MOSHI_HOT_DEFAULT_MAX_STREAMS (16) columns, the limit every configuration written
+    // before wide batches existed keeps; 1 = up to MOSHI_HOT_MAX_STREAMS (64). A caller opts in because a column is not free: its K / V rings are
+    // 2 x num_layers x dim x context BF16 values of device memory (1.57 GB at moshika's widths and context 3000). Nothing else depends on it.
+    int32_t wide_streams;
 };
 
 typedef struct moshi_hot_model moshi_hot_model_t;
@@ -101,7 +105,7 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 // is open from creation and all B share one stream position, so the mask row, the RoPE phase and the ring slot are common.
 // n_streams == 1 builds exactly moshi_hot_create's model.
 // n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0, tp_world == 0, dep_shard_world <= 1, depth_only == 0,
-// chain_depth == 0, codec_stream == 0, and 1 <= n_streams <= 16, in one of three shapes (demux / cross-attention / condition_sum / low-rank embeddings /
+// chain_depth == 0, codec_stream == 0, and 1 <= n_streams <= 16 (wide_streams = 1: <= MOSHI_HOT_MAX_STREAMS), in one of three shapes (demux / cross-attention / condition_sum / low-rank embeddings /
 // weight schedule / delay_steps: on the tts shape only, see "tts streams and slots" below):
 //  * the moshika shape: dep_q > 0, n_q > dep_q, extra_heads == 0;
 //  * the stt shape (moshi-stt): dep_q == 0 and n_q > 0 - no Depth transformer, every audio codebook is an input, the text token comes from the
@@ -109,12 +113,15 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 //    A frame takes n_q codes per column, out_audio is not touched and may be NULL, the frame's only sampler site is 0 (the text head), and the
 //    heads' probabilities of every column are computed by the Temporal graph itself and read back with the tokens (moshi_hot_last_heads).
 //  * the tts shape (moshi-tts): dep_q > 0, n_q == dep_q, extra_heads == 0.
-// Anything else returns NULL.
+// Anything else returns NULL, and so does a B > 1 model whose state (chiefly the K / V rings: 2 x layers x dim x context BF16 values per column, 1.57 GB
+// at moshika's widths and context 3000) cannot be allocated on the device: nothing is left behind, the caller may ask for fewer columns.
 // On such a model moshi_hot_read_last("text_logits" | "transformer_out" | "dep_logits<k>") returns B consecutive rows (stream 0 first), and
 // moshi_hot_set_context_fill moves the shared stream position, not the delay rings. The single-stream frame calls (moshi_hot_lm_step*, moshi_hot_sts_*,
 // moshi_hot_ring_bytes, moshi_hot_host_ring, moshi_hot_layer_probe) return -1, and the calls without a result (moshi_hot_mimi_*, moshi_hot_prefill,
 // moshi_hot_personaplex_system_prompts*, moshi_hot_lm_step_embedding, moshi_hot_fill_ring, moshi_hot_force_last, moshi_hot_set_conditions, the hooks,
 // moshi_hot_depth_shard_* and moshi_hot_tp_*) do nothing; moshi_hot_depth_shard_msg / _tout and moshi_hot_tp_msg return NULL.
+#define MOSHI_HOT_MAX_STREAMS 64           // columns of one streams or slots model with wide_streams = 1: what one pass of the batched mat-muls takes
+#define MOSHI_HOT_DEFAULT_MAX_STREAMS 16   // ... and with wide_streams = 0
 GGML_API moshi_hot_model_t * moshi_hot_create_streams(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_streams);
 // one frame of every stream (moshi_lmgen_step, lm.h:778-979, B times in lockstep): in_audio = B x (n_q - dep_q) codes (stream-major), text_token = B,
 // out_audio = B x dep_q (stream-major). Returns 1 when every stream's outputs are valid, else 0: while the delay rings fill (the same for every
@@ -124,7 +131,7 @@ GGML_API int moshi_hot_n_streams(moshi_hot_model_t * m);
 
 // ---- stream slots: B independent conversations over one set of weights, admitted and retired mid-batch ----------------------------------------
 // The B-column model of moshi_hot_create_streams with a stream position per column: slot b's mask row, RoPE phase and ring slot follow its own
-// position, so a conversation can start in any frame while the others run on. Same configurations as moshi_hot_create_streams, 2 <= n_slots <= 16;
+// position, so a conversation can start in any frame while the others run on. Same configurations as moshi_hot_create_streams, 2 <= n_slots <= 16 (wide_streams = 1: <= MOSHI_HOT_MAX_STREAMS);
 // anything else returns NULL (one conversation: moshi_hot_create). All slots start closed.
 // A closed slot still occupies its column: it is stepped frozen at its position, fed the initial tokens, writes only its own KV ring rows, and its
 // results are discarded. moshi_hot_read_last returns B rows and moshi_hot_n_streams returns B, as on a streams model. The single-stream calls and

@@ -54,6 +54,7 @@ struct hip_ctx {
     std::string name, description;
     hipStream_t stream = nullptr;
     int flags = 0;
+    int max_columns = 16;        // ggml_backend_mi355x_set_max_columns: the widest B-column sampler graph planned as one launch
     bool no_capture = false;     // ggml_backend_mi355x_set_capture(.., 0): plans of repeated graphs are reused but not captured into hipGraphs
     ggml_mi355x_stats stats = {};
     // pooled allocations: size class -> free pointers
@@ -2119,7 +2120,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_GET_ROWS || g->nodes[i]->type != GGML_TYPE_I32) continue;
             sample_streams_args sa;
             std::vector<int> members;
-            if (!match_sampler_streams(an, i, sa, members)) continue;
+            if (!match_sampler_streams(an, i, sa, members) || sa.B > c->max_columns) continue;
             bool clash = false;
             for (int m : members) if (an.skip[(size_t) m]) clash = true;
             if (clash) continue;
@@ -2785,8 +2786,10 @@ static enum ggml_backend_dev_type hip_dev_type(ggml_backend_dev_t) { return GGML
 static ggml_backend_t hip_dev_init(ggml_backend_dev_t d, const char *) {
     hip_ctx * c = (hip_ctx *) d->context;
     ctx_init_lazy(c);
-    // a fresh backend handle starts from default flags and zeroed counters (the device context is shared)
-    if (c->flags != 0) { HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; }
+    // a fresh backend handle starts from default flags, the default sampler width and zeroed counters (the device context is shared)
+    if (c->flags != 0 || c->max_columns != 16) {
+        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16;
+    }
     c->stats = {};
     auto * b = new ggml_backend;
     b->iface = { hip_backend_name, hip_backend_free, hip_backend_sync, hip_alloc_buffer, hip_graph_compute, hip_supports_op, hip_get_tensor_async, hip_event_record, hip_event_wait };
@@ -2831,6 +2834,9 @@ extern "C" void ggml_backend_mi355x_get_stats(ggml_backend_t b, struct ggml_mi35
 extern "C" void ggml_backend_mi355x_set_capture(ggml_backend_t b, int enabled) {
     if (b && b->iface.get_name == hip_backend_name) ((hip_ctx *) b->context)->no_capture = !enabled;   // any other backend: nothing to do
 }
+extern "C" void ggml_backend_mi355x_set_max_columns(ggml_backend_t b, int n) {
+    if (b && b->iface.get_name == hip_backend_name) { hip_ctx * c = (hip_ctx *) b->context; n = n < 16 ? 16 : n > SAMPLE_MAX_B ? SAMPLE_MAX_B : n; if (n > c->max_columns) c->max_columns = n; }
+}
 extern "C" void ggml_backend_mi355x_set_flags(ggml_backend_t b, int flags) {
     hip_ctx * c = ctx_of(b);
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
@@ -2868,5 +2874,6 @@ extern "C" ggml_backend_t ggml_backend_mi355x_init_stream(ggml_backend_t base) {
     ggml_backend_t b = c->dev_obj.iface.init_backend(&c->dev_obj, NULL);
     c->flags = b0->flags;             // the debug flags in force on `base` (no fusion / no hipGraph / ...) apply to its sibling stream too
     c->no_capture = b0->no_capture;
+    c->max_columns = b0->max_columns;
     return b;
 }

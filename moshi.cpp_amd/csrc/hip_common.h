@@ -154,7 +154,8 @@ void k_matvec(hipStream_t s, const mv_args & a);
 void k_gate_quant_q8k(hipStream_t s, const float * h, int64_t K, void * out_blocks, int wtype);   // activation format follows the weight type
 // alpha * rms_norm(x) quantised once to the same padded blocks (K <= 4096); n_out (optional) receives the normed floats
 void k_norm_quant_q8k(hipStream_t s, const float * x, const float * alpha, float eps, int64_t K, void * out_blocks, int wtype, float * n_out);
-// batched Q4_K / Q8_0 / Q4_0 mat-mul for prompt prefill (T = 2..64 activation rows): rows quantised to Q8_K (Q4_K weights) or Q8_0 into `ws`, then 16x16x32 int8 MFMA tiles
+// batched Q4_K / Q8_0 / Q4_0 mat-mul for prompt prefill and the B-column LM step (T = 2..64 activation rows): rows quantised to Q8_K (Q4_K weights) or Q8_0 into `ws`, then
+// 16x16x32 int8 MFMA tiles. Q4_K weights take all T <= 64 columns in one pass, Q8_0 / Q4_0 passes of 32 (MI355X_MMQ_WIDE, hip_kernels_fused.hip); bit-identical per column either way
 size_t k_mm_q4k_batched_ws_size(int64_t K, int64_t T);
 bool k_mm_q4k_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
 // prologue: MV_PLAIN (x[K, T] as is), MV_RMSNORM (alpha * rms_norm(x), eps) or MV_GATE_SILU (x = h[2K, T]: silu(h[:K]) * h[K:]); residual optional
@@ -213,7 +214,7 @@ struct attn_blocks_args { attn_args a; int n_jobs, write_only; attn_block_job jo
 void k_attn_blocks(hipStream_t s, const attn_blocks_args & a, unsigned * err = nullptr);
 // rows consecutive rows of n floats, row r copied from its own source src[r] (stream slots: the B mask rows, each a window of the bias table at the
 // slot's own column, transformer.h:1259-1289) - one launch instead of one per row
-#define COPY_ROWS_MAX 16
+#define COPY_ROWS_MAX 64   // (64 pointers by value: 512 bytes of kernel arguments)
 struct copy_rows_args { const float * src[COPY_ROWS_MAX]; float * dst; int64_t n; int rows; };
 void k_copy_rows(hipStream_t s, const copy_rows_args & a);
 // Slot snapshots (moshi_hot_slot_fork / _save / _load): a run of same-type copies between [D, n, H] row-range views - ring rows [0, n) of every head
@@ -268,7 +269,7 @@ struct sample_args { const float * logits; int n; float scale; int k; const floa
 void k_sample_topk(hipStream_t s, const sample_args & a);
 // the same for the B columns of a B-column LM step, one workgroup per column: logits [n, B], noise [k, B], out / out2 = B tokens. inv_temp (may be NULL):
 // one scale per column (the graph's mul by a [1, B] input) instead of `scale`
-#define SAMPLE_MAX_B 16
+#define SAMPLE_MAX_B 64
 struct sample_streams_args { const float * logits; int n; float scale; const float * inv_temp; int k; const float * noise; int32_t * out; int32_t * out2; int B; };
 void k_sample_topk_streams(hipStream_t s, const sample_streams_args & a);
 // The extra heads of a B-column stt step (moshi_hot.cpp build_temporal_graph): for every column b and head k, soft_max(W_k . x[:, b]) with W_k a block-

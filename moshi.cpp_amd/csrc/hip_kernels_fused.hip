@@ -1041,8 +1041,10 @@ __global__ void __launch_bounds__(64) gate_quant_rows_q8k_kernel(const float * h
 // lane. Its 6-bit sub-block scale s = 8 sh + sl is folded into the 4-bit weights before the MFMA (q * sh and q * sl stay below 128, a
 // packed dword times a small integer never carries between bytes), so the eight sub-blocks of a super-block ACCUMULATE in the matrix
 // core: isum = 8 * sum(x . q sh) + sum(x . q sl), no per-tile scaling on the VALU. The mins meet the split block sums the same way.
+// NT = 3 and 4 column tiles (33..64 columns) are the wide form of a B-column step: the weight tile is staged and its scaled nibbles are built
+// once, then meet every column tile. Four tiles are held to two waves per SIMD (238 VGPRs, no scratch) as the narrower forms are.
 template <int NT>
-__global__ void __launch_bounds__(64 * MMQ_NW) mm_q4k_mfma_kernel(const char * w, int64_t row_bytes, int nb, int M, int T, const xblkb * xq,
+__global__ void __attribute__((amdgpu_waves_per_eu(NT == 4 ? 2 : 1))) __launch_bounds__(64 * MMQ_NW) mm_q4k_mfma_kernel(const char * w, int64_t row_bytes, int nb, int M, int T, const xblkb * xq,
                                                                    float * y, int64_t y_cs, const float * residual, int64_t r_cs) {
     __shared__ __attribute__((aligned(16))) char stage_all[MMQ_NW][16 * MMQ_ROW];
     __shared__ float red[MMQ_NW - 1][NT * 4][64];
@@ -1464,6 +1466,7 @@ __global__ void __launch_bounds__(64 * MMQ_NW) mm_q80_mfma_kernel(const char * w
 }
 
 static int env_int(const char * name, int def);
+#define MMQ_WIDE_DEFAULT 3   // the Q4_K kernels take 33..64 columns in one pass; the Q8_0 / Q4_0 kernel was 3-5 % slower that way and keeps passes of 32
 size_t k_mm_q4k_batched_ws_size(int64_t K, int64_t T) { return (size_t) (K / 256) * (size_t) T * sizeof(xblkb); }
 bool k_mm_q4k_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) {
     return (wtype == GGML_TYPE_Q4_K || wtype == GGML_TYPE_Q8_0 || wtype == GGML_TYPE_Q4_0) && K % 256 == 0 && T >= 2 && T <= 64 && M >= 16;
@@ -1471,24 +1474,33 @@ bool k_mm_q4k_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) {
 void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
                       void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
     const int nb = (int) (K / 256);
+    // Columns per pass. Up to 64 (four MFMA column tiles) go in ONE launch, so a B-column step of 33..64 conversations streams and unpacks every
+    // weight tile once; a column's arithmetic does not depend on the tile count (integer block dots, the per-wave float sums and the cross-wave
+    // order are per column), so its result is bit-identical to the 32-column pass. MI355X_MMQ_WIDE=0 restores passes of 32 everywhere (the A/B of DESIGN.md 20).
+    // The switch is a mask, one bit per kernel family, so that each can be timed against its own two-pass form: 1 the Q4_K split-K kernel (M < 8192),
+    // 2 the Q4_K rows kernel, 4 the Q8_0 / Q4_0 kernel.
+    static const int wide = env_int("MI355X_MMQ_WIDE", MMQ_WIDE_DEFAULT);
+    static const int rows_min = env_int("MI355X_MMQ_ROWS_MIN_M", 8192);   // >= 128 workgroups of 64 rows
+    const int family = wtype != GGML_TYPE_Q4_K ? 4 : M >= rows_min ? 2 : 1;
+    const int pass = (wide & family) ? 64 : 32;
     if (wtype != GGML_TYPE_Q4_K) {   // Q8_0 / Q4_0 weights: Q8_0 activation rows
         xblk80b * xq0 = (xblk80b *) ws;
         if (prologue == MV_RMSNORM) rms_quant_rows_q80_kernel<<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, nb, xq0);
         else if (prologue == MV_GATE_SILU) gate_quant_rows_q80_kernel<<<(int) (T * nb), 64, 0, s>>>(x, x_cs, (int) K, nb, xq0);
         else quant_rows_q80_kernel<<<(int) (T * nb), 64, 0, s>>>(x, x_cs, nb, xq0);
         const int grid = (int) ((M + 15) / 16), thr = 64 * MMQ_NW;
-        for (int64_t c0 = 0; c0 < T; c0 += 32) {
-            const int Tc = (int) (T - c0 < 32 ? T - c0 : 32);
+        for (int64_t c0 = 0; c0 < T; c0 += pass) {
+            const int Tc = (int) (T - c0 < pass ? T - c0 : pass);
             const xblk80b * xq = xq0 + c0 * nb;
             float * yc = y + c0 * y_cs;
             const float * rc = residual ? residual + c0 * r_cs : nullptr;
+#define MMQ80_LAUNCH(NT, FMT) mm_q80_mfma_kernel<NT, FMT><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
             if (wtype == GGML_TYPE_Q8_0) {
-                if (Tc <= 16) mm_q80_mfma_kernel<1, MVF_Q80><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
-                else mm_q80_mfma_kernel<2, MVF_Q80><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+                if (Tc <= 16) MMQ80_LAUNCH(1, MVF_Q80); else if (Tc <= 32) MMQ80_LAUNCH(2, MVF_Q80); else if (Tc <= 48) MMQ80_LAUNCH(3, MVF_Q80); else MMQ80_LAUNCH(4, MVF_Q80);
             } else {
-                if (Tc <= 16) mm_q80_mfma_kernel<1, MVF_Q40><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
-                else mm_q80_mfma_kernel<2, MVF_Q40><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+                if (Tc <= 16) MMQ80_LAUNCH(1, MVF_Q40); else if (Tc <= 32) MMQ80_LAUNCH(2, MVF_Q40); else if (Tc <= 48) MMQ80_LAUNCH(3, MVF_Q40); else MMQ80_LAUNCH(4, MVF_Q40);
             }
+#undef MMQ80_LAUNCH
         }
         return;
     }
@@ -1497,18 +1509,19 @@ void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_byte
     else quant_rows_q8k_kernel<<<(int) (T * nb), 64, 0, s>>>(x, x_cs, nb, (xblkb *) ws);
     const int grid = (int) ((M + 15) / 16);
     const int thr = 64 * MMQ_NW;
-    for (int64_t c0 = 0; c0 < T; c0 += 32) {   // 32 columns per pass (two MFMA column tiles; four would leave one wave per SIMD)
-        const int Tc = (int) (T - c0 < 32 ? T - c0 : 32);
+    for (int64_t c0 = 0; c0 < T; c0 += pass) {
+        const int Tc = (int) (T - c0 < pass ? T - c0 : pass);
         const xblkb * xq = (const xblkb *) ws + c0 * nb;
         float * yc = y + c0 * y_cs;
         const float * rc = residual ? residual + c0 * r_cs : nullptr;
-        static const int rows_min = env_int("MI355X_MMQ_ROWS_MIN_M", 8192);   // >= 128 workgroups of 64 rows
+#define MMQ4K_ROWS(NT) mm_q4k_mfma_rows_kernel<NT><<<grid64, 256, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
+#define MMQ4K_LAUNCH(NT) mm_q4k_mfma_kernel<NT><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
         if (M >= rows_min) {
             const int grid64 = (int) ((M + 63) / 64);
-            if (Tc <= 16) mm_q4k_mfma_rows_kernel<1><<<grid64, 256, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
-            else mm_q4k_mfma_rows_kernel<2><<<grid64, 256, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
-        } else if (Tc <= 16) mm_q4k_mfma_kernel<1><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
-        else mm_q4k_mfma_kernel<2><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+            if (Tc <= 16) MMQ4K_ROWS(1); else if (Tc <= 32) MMQ4K_ROWS(2); else if (Tc <= 48) MMQ4K_ROWS(3); else MMQ4K_ROWS(4);
+        } else if (Tc <= 16) MMQ4K_LAUNCH(1); else if (Tc <= 32) MMQ4K_LAUNCH(2); else if (Tc <= 48) MMQ4K_LAUNCH(3); else MMQ4K_LAUNCH(4);
+#undef MMQ4K_ROWS
+#undef MMQ4K_LAUNCH
     }
 }
 

@@ -808,7 +808,6 @@ struct moshi_hot_model {
     Weights * W = nullptr;
     // persistent state (StateContext, src/context.h:656-780)
     struct ggml_context * st_ctx = nullptr; ggml_backend_buffer_t st_buf = nullptr;
-    std::vector<std::pair<T, std::vector<uint8_t>>> st_init;
     Builder * scratch = nullptr, * scratch_codec = nullptr;
 
     // LM
@@ -899,12 +898,11 @@ namespace {
 
 T state(moshi_hot_model * m, enum ggml_type type, int64_t n0, int64_t n1 = 1, int64_t n2 = 1) {
     T t = ggml_new_tensor_3d(m->st_ctx, type, n0, n1, n2);
-    m->st_init.push_back({ t, std::vector<uint8_t>(ggml_nbytes(t), 0) });   // zero-filled (transformer.h:164-166, conv.h:112)
+    // zero-filled (transformer.h:164-166, conv.h:112): create_model clears the whole state buffer on the device, no host copy of the zeros
     return t;
 }
 T state4(moshi_hot_model * m, enum ggml_type type, int64_t n0, int64_t n1, int64_t n2, int64_t n3) {   // a state with a batch dimension (lockstep streams)
     T t = ggml_new_tensor_4d(m->st_ctx, type, n0, n1, n2, n3);
-    m->st_init.push_back({ t, std::vector<uint8_t>(ggml_nbytes(t), 0) });
     return t;
 }
 
@@ -1245,7 +1243,7 @@ extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const st
 // a B > 1 model of either kind (moshi_hot.h): the LM alone, in the moshika shape (a Depth transformer, no extra heads) or the stt shape (no Depth
 // transformer: every codebook is an input, the text token is the Temporal head's; extra heads of at most 16 values each on transformer_out)
 static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int B, ModelKind kind) {
-    if (!cfg || B < 2 || B > 16) return nullptr;
+    if (!cfg || B < 2 || B > (cfg->wide_streams ? MOSHI_HOT_MAX_STREAMS : MOSHI_HOT_DEFAULT_MAX_STREAMS)) return nullptr;
     const moshi_hot_config & c = *cfg;
     const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && c.tp_world == 0 &&
                         c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream;
@@ -1381,6 +1379,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     m->be = backend;
     m->n_streams = n_streams;
     m->kind = kind;   // (build_temporal_graph reads it)
+    if (n_streams > MOSHI_HOT_DEFAULT_MAX_STREAMS) ggml_backend_mi355x_set_max_columns(backend, n_streams);   // its samplers stay one launch per site
     m->sampling.assign((size_t) n_streams, { { 0, cfg->temp, cfg->temp_text, cfg->top_k, cfg->top_k_text }, false });
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
@@ -1542,9 +1541,12 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     }
     W.load();
     m->st_buf = ggml_backend_alloc_ctx_tensors(m->st_ctx, backend);
+    if (!m->st_buf && m->n_streams > 1) {   // the B columns' rings did not fit the device: answered as a bad configuration is (moshi_hot.h)
+        moshi_hot_free(m);
+        return nullptr;
+    }
     GGML_ASSERT(m->st_buf);
-    for (auto & s : m->st_init) ggml_backend_tensor_set(s.first, s.second.data(), 0, s.second.size());
-    m->st_init.clear();
+    ggml_backend_buffer_clear(m->st_buf, 0);   // every state starts as zeros (64 columns of moshika rings are 100 GB: cleared in place)
     m->tokens_tmp.resize((size_t) (c.n_q + 1 + 32));
     m->pipe_codes.resize((size_t) (c.n_q + 1 + 32)); m->pipe_tokens.resize((size_t) (c.n_q + 1 + 32));
     ggml_backend_synchronize(backend);   // weights and zeroed states are in place before any other stream touches them

@@ -3,6 +3,7 @@ libggml-mi355x.so through the public ggml C API only)."""
 import ctypes as C
 
 MAX_CB = 33
+MAX_STREAMS = 64   # MOSHI_HOT_MAX_STREAMS: columns of one streams or slots model whose configuration sets wide_streams = 1 (otherwise 16)
 
 
 class Config(C.Structure):
@@ -18,7 +19,8 @@ class Config(C.Structure):
                                          "condition_sum", "dep_schedule_len")] + \
                [("dep_schedule", C.c_int32 * MAX_CB), ("update_scale", C.c_float),
                 ("dep_shard_rank", C.c_int32), ("dep_shard_world", C.c_int32), ("depth_only", C.c_int32),
-                ("tp_rank", C.c_int32), ("tp_world", C.c_int32), ("codec_stream", C.c_int32), ("chain_depth", C.c_int32)]
+                ("tp_rank", C.c_int32), ("tp_world", C.c_int32), ("codec_stream", C.c_int32), ("chain_depth", C.c_int32),
+                ("wide_streams", C.c_int32)]
 
     @property
     def io_dep_q(self):
