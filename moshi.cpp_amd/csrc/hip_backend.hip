@@ -6,7 +6,10 @@
 //   * ggml_backend_graph_compute() turns a cgraph into a *plan*: an ordered list of kernel launches in
 //     which the hot node sequences (norm -> mat-vec, gated FFN, residual add, the whole single-token
 //     attention block, the 17-stream embedding sum) are matched and replaced by the fused kernels of
-//     hip_kernels_fused.hip; everything else falls back to one generic kernel per node.
+//     hip_kernels_fused.hip; everything else falls back to one generic kernel per node. The planner is
+//     build_plan: one match_* function per node pattern, one pass_* function per fusion that claims the
+//     matched nodes under one rule (claim), the passes in the order of the fusion_passes list, then the
+//     post-passes that emit the attention groups, lay the steps out and merge runs into persistent chains.
 //   * plans of cached graphs (Temporal / Depth / Mimi graphs are built once by the caller and replayed
 //     every frame, src/context.h:538-544) are captured into a hipGraph and replayed with one
 //     hipGraphLaunch; throw-away scratch graphs (src/context.h:628-653) are launched directly.
@@ -441,7 +444,8 @@ static const ggml_tensor * sole_consumer(const analysis & an, const ggml_tensor 
     return an.g->nodes[an.last_consumer.at(t)];
 }
 
-static bool is_view_op(enum ggml_op op) { return op == GGML_OP_VIEW || op == GGML_OP_RESHAPE || op == GGML_OP_PERMUTE || op == GGML_OP_TRANSPOSE || op == GGML_OP_NONE; }
+static bool is_layout_op(enum ggml_op op) { return op == GGML_OP_VIEW || op == GGML_OP_RESHAPE || op == GGML_OP_PERMUTE || op == GGML_OP_TRANSPOSE; }
+static bool is_view_op(enum ggml_op op) { return is_layout_op(op) || op == GGML_OP_NONE; }
 static bool is_f32_vec(const ggml_tensor * t, int64_t n) {
     return t->type == GGML_TYPE_F32 && ggml_nelements(t) == n && ggml_is_contiguous(t);
 }
@@ -455,7 +459,7 @@ static const char * resolve_dense(const ggml_tensor * t) {
     if (!t->data || !ggml_is_contiguous(t)) return nullptr;
     const ggml_tensor * cur = t;
     int64_t delta = 0;
-    while (cur->op == GGML_OP_VIEW || cur->op == GGML_OP_RESHAPE || cur->op == GGML_OP_PERMUTE || cur->op == GGML_OP_TRANSPOSE) {
+    while (is_layout_op(cur->op)) {
         const ggml_tensor * s = cur->src[0];
         if (!s->data) return nullptr;
         delta += (const char *) cur->data - (const char *) s->data;
@@ -482,7 +486,7 @@ static bool strided_resolve(const ggml_tensor * t, sview & sv) {
     const int64_t es = (int64_t) ggml_type_size(t->type);
     const ggml_tensor * cur = t;
     for (int guard = 0; guard < 8; guard++) {
-        while (cur->op == GGML_OP_VIEW || cur->op == GGML_OP_RESHAPE || cur->op == GGML_OP_PERMUTE || cur->op == GGML_OP_TRANSPOSE) cur = cur->src[0];
+        while (is_layout_op(cur->op)) cur = cur->src[0];
         if (!(cur->op == GGML_OP_CONT || cur->op == GGML_OP_DUP) || cur->src[0]->type != cur->type || !ggml_is_contiguous(cur) || !cur->data || !cur->src[0]->data) break;
         const ggml_tensor * src = cur->src[0];
         // position of our base inside the dense copy -> logical coordinates of the copy
@@ -657,10 +661,12 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
 }
 
 // ---- fusion matchers --------------------------------------------------------------------------------------
+// what every matcher returns: the nodes one launch replaces and the position at which that launch is emitted (embedding sums: where they matched)
+struct group { int emit_pos = -1; std::vector<int> members; };
 
 // A. mat-vec with fused activation prologue and residual epilogue. Returns the position at which the
 //    fused kernel must be emitted (the last node of the group), or -1.
-struct mv_group { mv_args a; int emit_pos; std::vector<int> members; };
+struct mv_group : group { mv_args a; };
 static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members, int64_t B = 1);
 
 static bool writes_through_alias(const ggml_tensor * n) {
@@ -820,12 +826,44 @@ static bool match_matvec(const analysis & an, int pos, mv_group & grp) {
     return true;
 }
 
+// A''. LayerNorm with weight (and bias) over one row that no mat-vec prologue took (tts: norm_cross in front of the cross-attention's row-view projection):
+//      ggml_norm -> ggml_mul(., w) -> [ggml_add(., b)] as one launch with the three launches' float operations, matched at the norm
+struct norm_affine_group : group { tdesc x; float eps; int rms; const float * w, * b; float * out; };
+static bool match_norm_affine(const analysis & an, int pos, norm_affine_group & grp) {
+    const ggml_tensor * nn = an.g->nodes[pos];
+    if ((nn->op != GGML_OP_NORM && nn->op != GGML_OP_RMS_NORM) || nn->type != GGML_TYPE_F32 || uses_of(an, nn) != 1) return false;
+    if (nn->src[0]->type != GGML_TYPE_F32 || nn->src[0]->nb[0] != 4) return false;
+    // one row, or the B contiguous rows of a B-column LM activation [dim, 1, B] under the same [dim] weight and bias (norm_cross of B-column tts
+    // steps), one workgroup per row. Only that layout and LayerNorm: every other multi-row norm keeps the plan it had.
+    const int64_t n_rows = ggml_nelements(nn) / nn->ne[0];
+    if (n_rows != 1 && (nn->op != GGML_OP_NORM || nn->ne[1] != 1 || nn->ne[2] != n_rows || n_rows > 16 || !ggml_is_contiguous(nn) || !ggml_is_contiguous(nn->src[0]))) return false;
+    const ggml_tensor * ml = sole_consumer(an, nn);
+    if (!ml || ml->op != GGML_OP_MUL || ml->view_src || pos_of(an, ml) < 0 || an.skip[(size_t) pos_of(an, ml)] || !ggml_are_same_shape(ml, nn)) return false;
+    const ggml_tensor * wv = ml->src[0] == nn ? ml->src[1] : ml->src[0];
+    if (wv == nn || wv->type != GGML_TYPE_F32 || !ggml_is_contiguous(wv) || ggml_nelements(wv) != nn->ne[0] || !wv->data || !ggml_is_contiguous(ml)) return false;
+    grp.members = { pos, pos_of(an, ml) };
+    const ggml_tensor * last = ml;
+    grp.b = nullptr;
+    const ggml_tensor * ad = uses_of(an, ml) == 1 ? sole_consumer(an, ml) : nullptr;
+    if (ad && ad->op == GGML_OP_ADD && !ad->view_src && pos_of(an, ad) >= 0 && !an.skip[(size_t) pos_of(an, ad)] && ggml_is_contiguous(ad)) {
+        const ggml_tensor * bv = ad->src[0] == ml ? ad->src[1] : ad->src[0];
+        if (bv != ml && bv->type == GGML_TYPE_F32 && ggml_is_contiguous(bv) && ggml_nelements(bv) == nn->ne[0] && bv->data && bv->op == GGML_OP_NONE && ad->src[0] == ml && ggml_are_same_shape(ad, nn)) {
+            grp.b = (const float *) bv->data; last = ad; grp.members.push_back(pos_of(an, ad));
+        }
+    }
+    // (the weight must be the second factor or the first: the product is the same float either way; the bias must be the second summand: v + b)
+    grp.x = make_tdesc(nn->src[0]); grp.eps = ggml_get_op_params_f32(nn, 0); grp.rms = nn->op == GGML_OP_RMS_NORM;
+    grp.w = (const float *) wv->data; grp.out = (float *) last->data;
+    grp.emit_pos = pos_of(an, last);
+    return true;
+}
+
 // B. single-token attention block
-struct attn_group { attn_args a; int emit_pos; std::vector<int> members; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
-                    bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
+struct attn_group : group { attn_args a; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
+                          bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
 
 static const ggml_tensor * strip_views(const ggml_tensor * t) {
-    while (t && (t->op == GGML_OP_RESHAPE || t->op == GGML_OP_VIEW || t->op == GGML_OP_PERMUTE || t->op == GGML_OP_TRANSPOSE)) t = t->src[0];
+    while (t && is_layout_op(t->op)) t = t->src[0];
     return t;
 }
 
@@ -1106,7 +1144,7 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
 // B'''. stream slots' mask rows (moshi_hot.cpp transformer_graph_step_slots): for r = 0 .. n-1, in graph order, cont_r = cont(view of a dense row of the
 //      bias table, n_el floats at the slot's own column) and cpy(cont_r, view of dst at row r) - n >= 2 rows of one destination, consecutive and in order.
 //      Every source is read at the last cpy instead of at its cont: only layout nodes may sit between the members.
-struct row_copy_group { copy_rows_args a; int emit_pos; std::vector<int> members; };
+struct row_copy_group : group { copy_rows_args a; };
 static bool match_row_copies(const analysis & an, int pos, row_copy_group & grp) {
     const ggml_cgraph * g = an.g;
     memset(&grp.a, 0, sizeof(grp.a));
@@ -1149,11 +1187,53 @@ static bool match_row_copies(const analysis & an, int pos, row_copy_group & grp)
     return true;
 }
 
+// B'''a. cpy(cont(x), dst): copy the strided source straight into dst (the per-step mask row: cont(view of the bias table) -> cpy into the graph input,
+//      transformer.h:1259-1289 - two launches on the LM stream in front of every Temporal graph), matched at the cpy
+struct cpy_fold_group : group { tdesc d, x; };
+static bool match_cpy_of_cont(const analysis & an, int pos, cpy_fold_group & grp) {
+    const ggml_tensor * n = an.g->nodes[pos];
+    if (n->op != GGML_OP_CPY) return false;
+    const ggml_tensor * ct = n->src[0];
+    const int pc = pos_of(an, ct);
+    if (ct->op != GGML_OP_CONT || pc < 0 || an.skip[(size_t) pc] || uses_of(an, ct) != 1 || ct->view_src) return false;
+    if (ct->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ct->src[0]->type != GGML_TYPE_F32 || !ggml_are_same_shape(ct, ct->src[0]) ||
+        !ggml_are_same_shape(n, ct) || !ggml_is_contiguous(n)) return false;
+    // the strided source is read at the cpy's position instead of the cont's: nothing in between may write through an alias (set_rows, a cpy into
+    // a view of the same table), or the fold would copy newer data than the cont saw
+    for (int j = pc + 1; j < pos; j++) if (writes_through_alias(an.g->nodes[j])) return false;
+    grp.members = { pos, pc };
+    grp.emit_pos = pos;
+    grp.d = make_tdesc(n); grp.x = make_tdesc(ct->src[0]);
+    return true;
+}
+
+// B'''b. timestep table of add(a, b): one launch (the Temporal graph's RoPE phase: add(arange, offset) -> timestep_embedding), matched at the
+//      timestep_embedding. hoist_dst is set when both operands are uploaded leaves (pstep::hoist_dst)
+struct timestep_group : group { tdesc d, x; const float * y; int yn, dim, max_period; const char * hoist_dst; size_t hoist_bytes; };
+static bool match_timestep_of_add(const analysis & an, int pos, timestep_group & grp) {
+    const ggml_tensor * n = an.g->nodes[pos];
+    if (n->op != GGML_OP_TIMESTEP_EMBEDDING) return false;
+    const ggml_tensor * ad = n->src[0];
+    const int pa = pos_of(an, ad);
+    if (ad->op != GGML_OP_ADD || pa < 0 || an.skip[(size_t) pa] || uses_of(an, ad) != 1 || ad->view_src || ad->type != GGML_TYPE_F32) return false;
+    const ggml_tensor * x = ad->src[0], * y = ad->src[1];
+    if (x->type != GGML_TYPE_F32 || y->type != GGML_TYPE_F32 || !ggml_is_contiguous(x) || !ggml_is_contiguous(y) || !ggml_are_same_shape(x, ad) ||
+        ggml_nelements(ad) != ad->ne[0] || !(ggml_nelements(y) == ggml_nelements(ad) || ggml_nelements(y) == 1)) return false;
+    grp.members = { pos, pa };
+    grp.emit_pos = pos;
+    grp.d = make_tdesc(n); grp.x = make_tdesc(x);
+    grp.y = (const float *) y->data; grp.yn = (int) ggml_nelements(y);
+    grp.dim = n->op_params[0]; grp.max_period = n->op_params[1];
+    const bool leaves = x->op == GGML_OP_NONE && y->op == GGML_OP_NONE && !x->view_src && !y->view_src;   // (both operands are uploaded leaves)
+    grp.hoist_dst = leaves ? (const char *) n->data : nullptr; grp.hoist_bytes = leaves ? ggml_nbytes(n) : 0;
+    return true;
+}
+
 // B''''. slot snapshots (moshi_hot.cpp slot_state_graph): a run of cpy(a, b) of one type between [D, n, H] row-range views - each head one contiguous run
 //      of n x D elements on both sides - at least one side inside ONE column of a [D, C, H, B] ring (B > 1), with nothing but layout nodes between the
 //      copies: one k_ring_copy launch for up to RING_COPY_MAX of them. A copy whose bases, head strides or run length are no multiples of 16 bytes, whose
 //      ranges overlap, or that touches what an earlier job of the run writes (or writes what one reads) is declined and stays a generic copy.
-struct ring_copy_group { ring_copy_args a; int emit_pos; std::vector<int> members; };
+struct ring_copy_group : group { ring_copy_args a; };
 struct byte_range { const char * lo, * hi; bool overlaps(const byte_range & o) const { return lo < o.hi && o.lo < hi; } };
 // t as H runs of contiguous bytes inside its root tensor: base, head stride, run length and the range they span
 static bool ring_copy_side(const ggml_tensor * t, const char ** base, int64_t * hs, int64_t * run, byte_range * span, bool * ring_column) {
@@ -1204,7 +1284,7 @@ static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & gr
 
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
 //     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue
-struct bmm_group { int emit_pos; std::vector<int> members; std::function<void(hipStream_t)> run; };
+struct bmm_group : group { std::function<void(hipStream_t)> run; };
 static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_group & grp) {
     const ggml_tensor * mm = an.g->nodes[pos];
     if (mm->op != GGML_OP_MUL_MAT) return false;
@@ -1272,7 +1352,7 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
 }
 
 // B'. cross-attention over a cached condition, ending at x2 = cont(permute(mul_mat(cont(transpose(V)), soft_max(mul_mat(K, q)))))
-struct xattn_group { xattn_args a; int emit_pos; std::vector<int> members; };
+struct xattn_group : group { xattn_args a; };
 static bool match_cross_attention(const analysis & an, int pos, xattn_group & grp) {
     const ggml_tensor * x2 = an.g->nodes[pos];
     if (x2->op != GGML_OP_CONT || x2->type != GGML_TYPE_F32 || x2->src[0]->op != GGML_OP_PERMUTE || uses_of(an, x2->src[0]) != 1) return false;
@@ -1312,7 +1392,7 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
 }
 
 // C. left-deep sum of (scaled) embedding rows ending at node `pos`
-struct embed_group { embed_sum_args a; std::vector<int> members; };
+struct embed_group : group { embed_sum_args a; };
 
 // B > 1: B columns - rows gathered by B indices [dim, B], times one scale per column [1, B]
 static bool match_embed_term(const analysis & an, const ggml_tensor * e, embed_src & out, std::vector<int> & members, int64_t B) {
@@ -1395,12 +1475,40 @@ static bool match_embed_sum(const analysis & an, int pos, embed_group & grp) {
         members.push_back(pos_of(an, adds[f - 1 - i]));
     }
     grp.members = members;
+    grp.emit_pos = pos;
+    return true;
+}
+
+// C'. one embedding row through a small Q8_0 projection (tts: low-rank Depth embeddings): get_rows -> mul_mat [-> cast] as one launch, matched at the mul_mat
+struct lowrank_group : group { lowrank_embed_args a; };
+static bool match_lowrank_embed(const analysis & an, int pos, lowrank_group & grp) {
+    const ggml_tensor * mm = an.g->nodes[pos];
+    if (mm->op != GGML_OP_MUL_MAT || mm->type != GGML_TYPE_F32) return false;
+    const ggml_tensor * W = mm->src[0], * gr = mm->src[1];
+    if (W->type != GGML_TYPE_Q8_0 || !dense_rows(W) || W->ne[2] * W->ne[3] != 1 || gr->op != GGML_OP_GET_ROWS || gr->type != GGML_TYPE_F32) return false;
+    const int pg = pos_of(an, gr);
+    if (pg < 0 || an.skip[(size_t) pg] || uses_of(an, gr) != 1 || ggml_nelements(gr) != gr->ne[0] || gr->ne[0] != W->ne[0]) return false;
+    const ggml_tensor * tab = gr->src[0], * idx = gr->src[1];
+    if (ggml_nelements(idx) != 1 || idx->type != GGML_TYPE_I32 || !dense_rows(tab) || !idx->data) return false;
+    switch (tab->type) { case GGML_TYPE_F32: case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: break; default: return false; }
+    const int64_t K = W->ne[0], M = W->ne[1];
+    if (K % 32 != 0 || K > 2048 || ggml_nelements(mm) != M || !ggml_is_contiguous(mm)) return false;
+    grp.members = { pg, pos };
+    grp.emit_pos = pos;
+    float * out = (float *) mm->data;
+    const ggml_tensor * cp = sole_consumer(an, mm);   // ggml_cast(.., F32) of an F32 tensor: a copy - write its storage directly
+    if (cp && cp->op == GGML_OP_CPY && uses_of(an, mm) == 1 && cp->type == GGML_TYPE_F32 && cp->src[0] == mm && ggml_is_contiguous(cp) && cp->view_src == NULL &&
+        ggml_are_same_shape(cp, mm) && pos_of(an, cp) >= 0 && !an.skip[(size_t) pos_of(an, cp)]) {
+        grp.members.push_back(pos_of(an, cp)); out = (float *) cp->data; grp.emit_pos = pos_of(an, cp);
+    }
+    grp.a = { (const char *) tab->data, (int64_t) tab->nb[1], tab->ne[1], (int) tab->type, (const int32_t *) idx->data,
+              (const char *) W->data, (int64_t) W->nb[1], (int) K, (int) M, out };
     return true;
 }
 
 // D. streaming / stateless conv1d (conv.h:50-96, 137-161): [elu] -> concat(prev, x) -> {tail cpy, im2col} -> mul_mat -> reshape
 //    [-> + bias] [-> residual + y]  becomes  stream_im2col + conv_tail + one product with the bias/residual epilogue.
-struct step_group { std::vector<step_fn> steps; int emit_pos; std::vector<int> members; sample_args smp; vq_level_args vq; bool has_vq = false; };   // smp / vq: match_sampler's / match_vq_level's arguments
+struct step_group : group { std::vector<step_fn> steps; sample_args smp; vq_level_args vq; bool has_vq = false; };   // smp / vq: match_sampler's / match_vq_level's arguments
 
 static bool is_elu(const ggml_tensor * t) { return t->op == GGML_OP_UNARY && t->op_params[0] == GGML_UNARY_OP_ELU && t->view_src == NULL; }
 
@@ -1854,7 +1962,10 @@ static bool match_sampler(const analysis & an, int pos, step_group & grp) {
 //    with idx = cont(view(argsort_desc(p), k)) [k, B], p = soft_max(sc) [n, B], sc = scale(logits, 1 / temp) or mul(logits, inv_temp [1, B])
 // inv_temp must be a contiguous F32 graph INPUT (no node of the graph is it, views it or copies into it). A trailing cpy of the B tokens into an I32
 // vector (the chained Depth graph's token rows) becomes out2. One workgroup per column and none waits for another: no residency planning.
-static bool match_sampler_streams(const analysis & an, int pos, sample_streams_args & a, std::vector<int> & members) {
+struct sampler_streams_group : group { sample_streams_args a; };
+static bool match_sampler_streams(const analysis & an, int pos, sampler_streams_group & grp) {
+    sample_streams_args & a = grp.a; std::vector<int> & members = grp.members;
+    grp.emit_pos = pos;
     const ggml_tensor * out = an.g->nodes[pos];
     if (out->op != GGML_OP_GET_ROWS || out->type != GGML_TYPE_I32 || out->ne[0] != 1 || out->ne[1] != 1 || out->ne[3] != 1 || !out->data) return false;
     const int64_t B = out->ne[2];
@@ -1934,7 +2045,9 @@ static bool match_sampler_streams(const analysis & an, int pos, sample_streams_a
 // do not overlap. Matched at the first head's mul_mat; claims every such triple over the same x (at most HEADS_MAX) and is emitted where the last
 // copy stood. Neither the products nor the soft_max results may have another reader, and nothing else in the graph may touch the destination tensor.
 // Anything else (float weights, M > 16) is left to the plain nodes.
-static bool match_heads_streams(const analysis & an, int pos, heads_streams_args & a, std::vector<int> & members, int & emit_pos) {
+struct heads_group : group { heads_streams_args a; };
+static bool match_heads_streams(const analysis & an, int pos, heads_group & grp) {
+    heads_streams_args & a = grp.a; std::vector<int> & members = grp.members; int & emit_pos = grp.emit_pos;
     const ggml_tensor * mm0 = an.g->nodes[pos];
     if (mm0->op != GGML_OP_MUL_MAT) return false;
     const ggml_tensor * x = mm0->src[1], * w0 = mm0->src[0];
@@ -2014,420 +2127,387 @@ static bool spin_kernels_allowed(hip_ctx * c) {
 }
 static bool spin_kernels_possible(const hip_ctx * c) { return c->device >= 0 && c->device < 64 && !is_stream_context(c) && (!g_spin_owner[c->device] || g_spin_owner[c->device] == c); }
 
-static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
-    plan_t * p = new plan_t;
-    p->n_nodes = g->n_nodes;
-    emitter em = { c, p };
+// What the passes of build_plan share.
+struct planner {
+    hip_ctx * c; plan_t * p; ggml_cgraph * g;
+    bool keep, fuse;   // keep: the plan is cached or profiled, not launched once and freed; fuse: backend flag 1 is not set
+    emitter em;
     analysis an;
-    analyse(an, g);
-    collect_plan_buffers(p, g);
-    const bool fuse = !(c->flags & 1);
+    std::map<int, std::vector<pstep>> at_pos;   // fused groups, keyed by the position at which they are emitted
+    std::vector<attn_group> attn_groups;        // pass_attention's groups: emitted after pass_matvecs, which absorbs some (emit_pos = -1)
+    std::unordered_map<const void *, float *> paired_gate;   // storage of a linear_in output h (never materialised) -> g = silu(h_l) * h_r
+};
 
-    // fused groups, keyed by the position at which they are emitted
-    std::map<int, std::vector<pstep>> at_pos;
-    std::vector<attn_group> attn_groups;
-    static const bool no_attn_prologue = getenv("MI355X_NO_ATTN_PROLOGUE") != nullptr;
+// THE CLAIM RULE. A group takes its nodes only if every member is a node of the graph (no negative position) and none is claimed already - `self`, the
+// node a pass stands on, excepted. Then every member is marked: no later pass matches it, no generic launch is emitted for it.
+static bool claimable(const planner & pl, const std::vector<int> & members, int self = -1) {
+    for (int m : members) if (m < 0 || (m != self && pl.an.skip[(size_t) m])) return false;
+    return true;
+}
+static bool claim(planner & pl, const std::vector<int> & members, int self = -1) {
+    if (!claimable(pl, members, self)) return false;
+    for (int m : members) pl.an.skip[(size_t) m] = 1;
+    return true;
+}
+// ... and counted as fused nodes, which every pass but the mat-vec pass does with all its members. Where a pass had no check of its own before this
+// rule, the line at its claim says why the rule never refuses there; where its check only lacked `m < 0` (attention, codec convolutions, scalar gathers,
+// both samplers, cross-attention, batched mat-muls) it read an.skip[m], so a negative member was an out-of-bounds read already: no matcher returns one.
+static bool claim_group(planner & pl, const group & grp, int self = -1) {
+    if (!claim(pl, grp.members, self)) return false;
+    pl.p->n_fused += (int) grp.members.size();
+    return true;
+}
+
+// the extra heads of a B-column stt step: every head's mul_mat -> soft_max -> cpy in one launch
+static void pass_heads_streams(planner & pl) {
+    static const bool no_heads = getenv("MI355X_NO_HEADS_FUSION") != nullptr;
+    for (int i = 0; i < pl.g->n_nodes && !no_heads; i++) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_MUL_MAT) continue;
+        heads_group grp;
+        // (claim: the first pass; the matcher tests an.skip for the triples and declines a destination that a non-member touches, so the one member it
+        // does not test, the destination view, is in no earlier group of this pass either)
+        if (!match_heads_streams(pl.an, i, grp) || !claim_group(pl, grp)) continue;
+        const heads_streams_args ha = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_heads_streams(s, ha); });
+    }
+}
+
+// slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp slot_state_graph) - one launch for the whole run
+static void pass_ring_copies(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        ring_copy_group grp;
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CPY || !match_ring_copies(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: every member is a position the matcher's own loop stood on and tested an.skip for)
+        const ring_copy_args ra = grp.a; const int cus = pl.c->usable_cus;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_ring_copy(s, ra, cus); });
+        pl.p->n_ring_copy_launches++; pl.p->n_ring_copy_jobs += ra.n_jobs;
+    }
+}
+
+// attention blocks (they swallow set_rows / soft_max / two mul_mats): collected here, emitted after the mat-vec pass, which may absorb a short-ring
+// attention into the projection that consumes it
+static void pass_attention(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
+        attn_group grp;
+        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp)) continue;
+        if (claim_group(pl, grp)) pl.attn_groups.push_back(grp);
+    }
+    // mask copies that every consumer now bypasses (NOT the claim rule: the copy is no matcher's member, and it is marked and counted as it always was,
+    // whatever claimed it before)
+    std::map<const ggml_tensor *, int> bypass;
+    for (auto & ag : pl.attn_groups) if (ag.mask_node) bypass[ag.mask_node]++;
+    for (auto & kv : bypass) if (uses_of(pl.an, kv.first) == kv.second) { pl.an.skip[(size_t) pos_of(pl.an, kv.first)] = 1; pl.p->n_fused++; }
+}
+
+// codec convolutions
+static void pass_codec_convs(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        if (pl.an.skip[(size_t) i]) continue;
+        step_group grp;
+        const enum ggml_op op = pl.g->nodes[i]->op;
+        if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em)) continue; }
+        else if (op == GGML_OP_CONV_TRANSPOSE_1D) { if (!match_convtr(pl.an, i, grp, pl.em)) continue; }
+        else if (op == GGML_OP_ARGMAX) { if (!match_vq_level(pl.an, i, grp, pl.em)) continue; }
+        else if (op == GGML_OP_CONCAT) { if (!match_dw_convtr(pl.an, i, grp)) continue; }
+        else continue;
+        if (!claim_group(pl, grp)) continue;
+        for (auto & f : grp.steps) {
+            pl.at_pos[grp.emit_pos].push_back(f);
+            if (grp.has_vq) { pl.p->vq_copies.emplace_back(new vq_level_args(grp.vq)); pl.at_pos[grp.emit_pos].back().vq = pl.p->vq_copies.back().get(); }
+        }
+    }
+}
+
+// scalar gathers (top-most node first, so it claims the whole tree)
+static void pass_scalar_gathers(planner & pl) {
+    for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
+        if (pl.an.skip[(size_t) i] || !(pl.g->nodes[i]->op == GGML_OP_CPY || pl.g->nodes[i]->op == GGML_OP_CONCAT)) continue;
+        step_group grp;
+        if (!match_scalar_gather(pl.an, i, grp) || !claim_group(pl, grp)) continue;
+        for (auto & f : grp.steps) pl.at_pos[grp.emit_pos].push_back(f);
+    }
+}
+
+static bool no_sampler_fusion() { static const bool off = getenv("MI355X_NO_SAMPLER_FUSION") != nullptr; return off; }
+static bool is_sampler_top(const ggml_tensor * n) { return n->op == GGML_OP_GET_ROWS && n->type == GGML_TYPE_I32; }
+
+// top-k samplers (temp > 0)
+static void pass_samplers(planner & pl) {
+    for (int i = pl.g->n_nodes - 1; i >= 0 && !no_sampler_fusion(); i--) {
+        if (pl.an.skip[(size_t) i] || !is_sampler_top(pl.g->nodes[i])) continue;
+        step_group grp;
+        if (!match_sampler(pl.an, i, grp) || !claim_group(pl, grp)) continue;
+        // (a step of its own that a step program may take in: the Depth transformer's samplers sit between its steps' mat-vecs, mv_args::special = 3)
+        pl.p->sampler_copies.emplace_back(new sample_args(grp.smp));
+        for (auto & f : grp.steps) pl.at_pos[grp.emit_pos].push_back(pstep::special_step(f, 3, nullptr, nullptr, pl.p->sampler_copies.back().get()));
+    }
+}
+
+// the B-column form of the same samplers (B-column LM steps)
+static void pass_sampler_streams(planner & pl) {
+    for (int i = pl.g->n_nodes - 1; i >= 0 && !no_sampler_fusion(); i--) {
+        if (pl.an.skip[(size_t) i] || !is_sampler_top(pl.g->nodes[i])) continue;
+        sampler_streams_group grp;
+        if (!match_sampler_streams(pl.an, i, grp) || grp.a.B > pl.c->max_columns || !claim_group(pl, grp)) continue;
+        const sample_streams_args sa = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_sample_topk_streams(s, sa); });
+    }
+}
+
+// cross-attention over cached conditions (tts)
+static void pass_cross_attention(planner & pl) {
+    static const bool no_xattn = getenv("MI355X_NO_CROSS_ATTN_FUSION") != nullptr;
+    for (int i = 0; i < pl.g->n_nodes && !no_xattn; i++) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CONT) continue;
+        xattn_group grp;
+        if (!match_cross_attention(pl.an, i, grp) || !claim_group(pl, grp)) continue;
+        const xattn_args xa = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_cross_attn(s, xa); });
+    }
+}
+
+// one embedding row through a small Q8_0 projection (tts: low-rank Depth embeddings)
+static void pass_lowrank_embed(planner & pl) {
+    static const bool no_lowrank = getenv("MI355X_NO_LOWRANK_FUSION") != nullptr;
+    for (int i = 0; i < pl.g->n_nodes && !no_lowrank; i++) {
+        lowrank_group grp;
+        if (pl.an.skip[(size_t) i] || !match_lowrank_embed(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: the matcher tests position and an.skip of the get_rows and of the cast; the mul_mat is node i)
+        const lowrank_embed_args la = grp.a;
+        pl.p->lowrank_copies.emplace_back(new lowrank_embed_args(la));
+        pl.at_pos[grp.emit_pos].push_back(pstep::special_step([=](hipStream_t s) { k_lowrank_embed(s, la); }, 2, nullptr, pl.p->lowrank_copies.back().get()));
+    }
+}
+
+// embedding sums (top-most add first)
+static void pass_embed_sums(planner & pl) {
+    for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_ADD) continue;
+        embed_group grp;
+        if (!match_embed_sum(pl.an, i, grp) || !claim_group(pl, grp)) continue;   // (a term that is no node of the graph: a negative member, refused)
+        const embed_sum_args a = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_embed_sum(s, a); });
+    }
+}
+
+// a run of cpy(cont(window of a table), row r of dst) for r = 0, 1, .. (stream slots: the B mask rows, moshi_hot.cpp transformer_graph_step_slots):
+// one launch for all rows instead of one per row
+static void pass_row_copies(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        row_copy_group grp;
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CONT || !match_row_copies(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: every member is a position the matcher's own loop stood on and tested an.skip for)
+        const copy_rows_args ra = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_copy_rows(s, ra); });
+    }
+}
+
+// cpy(cont(x), dst) that the row-copy pass left: the strided source goes straight into dst
+static void pass_cpy_of_cont(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        cpy_fold_group grp;
+        if (pl.an.skip[(size_t) i] || !match_cpy_of_cont(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: the matcher tests position and an.skip of the cont; the cpy is node i)
+        const tdesc d = grp.d, x = grp.x;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_cpy(s, d, x); });
+    }
+}
+
+// timestep table of add(a, b): one launch
+static void pass_timestep_of_add(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        timestep_group grp;
+        if (pl.an.skip[(size_t) i] || !match_timestep_of_add(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: the matcher tests position and an.skip of the add; the timestep_embedding is node i)
+        const tdesc d = grp.d, tx = grp.x;
+        const float * yp = grp.y; const int yn = grp.yn, dim = grp.dim, mp = grp.max_period;
+        pstep st([=](hipStream_t s) { k_timestep_embedding(s, d, tx, dim, mp, yp, yn); });
+        st.hoist_dst = grp.hoist_dst; st.hoist_bytes = grp.hoist_bytes;
+        pl.at_pos[grp.emit_pos].push_back(std::move(st));
+    }
+}
+
+// ---- the mat-vec pass: four rewrites of one claimed projection `a`, applied in this order ----
+// greedy sampling (sampling.h:57-63) as the projection's epilogue: argmax of the logits, optionally copied into the token buffer
+static void fold_argmax_epilogue(planner & pl, const mv_group & grp, mv_args & a) {
     static const bool no_argmax_epilogue = getenv("MI355X_NO_ARGMAX_EPILOGUE") != nullptr;
-    if (fuse) {
-        // the extra heads of a B-column stt step: every head's mul_mat -> soft_max -> cpy in one launch
-        static const bool no_heads = getenv("MI355X_NO_HEADS_FUSION") != nullptr;
-        for (int i = 0; i < g->n_nodes && !no_heads; i++) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_MUL_MAT) continue;
-            heads_streams_args ha;
-            std::vector<int> members;
-            int emit = -1;
-            if (!match_heads_streams(an, i, ha, members, emit)) continue;
-            for (int m : members) an.skip[(size_t) m] = 1;
-            at_pos[emit].push_back([=](hipStream_t s) { k_heads_streams(s, ha); });
-            p->n_fused += (int) members.size();
-        }
-        // slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp slot_state_graph) - one launch for the whole run
-        for (int i = 0; i < g->n_nodes; i++) {
-            ring_copy_group rg;
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_CPY || !match_ring_copies(an, i, rg)) continue;
-            for (int m : rg.members) an.skip[(size_t) m] = 1;
-            const ring_copy_args ra = rg.a; const int cus = c->usable_cus;
-            at_pos[rg.emit_pos].push_back([=](hipStream_t s) { k_ring_copy(s, ra, cus); });
-            p->n_fused += (int) rg.members.size();
-            p->n_ring_copy_launches++; p->n_ring_copy_jobs += ra.n_jobs;
-        }
-        // attention blocks first (they swallow set_rows / soft_max / two mul_mats); emitted after the mat-vec pass, which may
-        // absorb a short-ring attention into the projection that consumes it
-        for (int i = 0; i < g->n_nodes; i++) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
-            attn_group grp;
-            if (!match_attention(an, i, grp) && !match_attention_streams(an, i, grp)) continue;
-            bool clash = false;
-            for (int m : grp.members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            attn_groups.push_back(grp);
-            p->n_fused += (int) grp.members.size();
-        }
-        {   // mask copies that every consumer now bypasses
-            std::map<const ggml_tensor *, int> bypass;
-            for (auto & ag : attn_groups) if (ag.mask_node) bypass[ag.mask_node]++;
-            for (auto & kv : bypass) if (uses_of(an, kv.first) == kv.second) { an.skip[(size_t) pos_of(an, kv.first)] = 1; p->n_fused++; }
-        }
-        // codec convolutions
-        for (int i = 0; i < g->n_nodes; i++) {
-            if (an.skip[(size_t) i]) continue;
-            step_group grp;
-            if (g->nodes[i]->op == GGML_OP_MUL_MAT) { if (!match_conv(an, i, grp, em)) continue; }
-            else if (g->nodes[i]->op == GGML_OP_CONV_TRANSPOSE_1D) { if (!match_convtr(an, i, grp, em)) continue; }
-            else if (g->nodes[i]->op == GGML_OP_ARGMAX) { if (!match_vq_level(an, i, grp, em)) continue; }
-            else if (g->nodes[i]->op == GGML_OP_CONCAT) { if (!match_dw_convtr(an, i, grp)) continue; }
-            else continue;
-            bool clash = false;
-            for (int m : grp.members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            for (auto & f : grp.steps) {
-                at_pos[grp.emit_pos].push_back(f);
-                if (grp.has_vq) { p->vq_copies.emplace_back(new vq_level_args(grp.vq)); at_pos[grp.emit_pos].back().vq = p->vq_copies.back().get(); }
-            }
-            p->n_fused += (int) grp.members.size();
-        }
-        // scalar gathers (top-most node first, so it claims the whole tree)
-        for (int i = g->n_nodes - 1; i >= 0; i--) {
-            if (an.skip[(size_t) i] || !(g->nodes[i]->op == GGML_OP_CPY || g->nodes[i]->op == GGML_OP_CONCAT)) continue;
-            step_group grp;
-            if (!match_scalar_gather(an, i, grp)) continue;
-            bool clash = false;
-            for (int m : grp.members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            for (auto & f : grp.steps) at_pos[grp.emit_pos].push_back(f);
-            p->n_fused += (int) grp.members.size();
-        }
-        // top-k samplers (temp > 0)
-        static const bool no_sampler = getenv("MI355X_NO_SAMPLER_FUSION") != nullptr;
-        for (int i = g->n_nodes - 1; i >= 0 && !no_sampler; i--) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_GET_ROWS || g->nodes[i]->type != GGML_TYPE_I32) continue;
-            step_group grp;
-            if (!match_sampler(an, i, grp)) continue;
-            bool clash = false;
-            for (int m : grp.members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            // (a step of its own that a step program may take in: the Depth transformer's samplers sit between its steps' mat-vecs, mv_args::special = 3)
-            p->sampler_copies.emplace_back(new sample_args(grp.smp));
-            for (auto & f : grp.steps) at_pos[grp.emit_pos].push_back(pstep::special_step(f, 3, nullptr, nullptr, p->sampler_copies.back().get()));
-            p->n_fused += (int) grp.members.size();
-        }
-        // the B-column form of the same samplers (B-column LM steps)
-        for (int i = g->n_nodes - 1; i >= 0 && !no_sampler; i--) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_GET_ROWS || g->nodes[i]->type != GGML_TYPE_I32) continue;
-            sample_streams_args sa;
-            std::vector<int> members;
-            if (!match_sampler_streams(an, i, sa, members) || sa.B > c->max_columns) continue;
-            bool clash = false;
-            for (int m : members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : members) an.skip[(size_t) m] = 1;
-            at_pos[i].push_back([=](hipStream_t s) { k_sample_topk_streams(s, sa); });
-            p->n_fused += (int) members.size();
-        }
-        // cross-attention over cached conditions (tts)
-        static const bool no_xattn = getenv("MI355X_NO_CROSS_ATTN_FUSION") != nullptr;
-        for (int i = 0; i < g->n_nodes && !no_xattn; i++) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_CONT) continue;
-            xattn_group xg;
-            if (!match_cross_attention(an, i, xg)) continue;
-            bool clash = false;
-            for (int m : xg.members) if (an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : xg.members) an.skip[(size_t) m] = 1;
-            const xattn_args xa = xg.a;
-            at_pos[xg.emit_pos].push_back([=](hipStream_t s) { k_cross_attn(s, xa); });
-            p->n_fused += (int) xg.members.size();
-        }
-        // one embedding row through a small Q8_0 projection (tts: low-rank Depth embeddings): get_rows -> mul_mat [-> cast] as one launch
-        static const bool no_lowrank = getenv("MI355X_NO_LOWRANK_FUSION") != nullptr;
-        for (int i = 0; i < g->n_nodes && !no_lowrank; i++) {
-            const ggml_tensor * mm = g->nodes[i];
-            if (an.skip[(size_t) i] || mm->op != GGML_OP_MUL_MAT || mm->type != GGML_TYPE_F32) continue;
-            const ggml_tensor * W = mm->src[0], * gr = mm->src[1];
-            if (W->type != GGML_TYPE_Q8_0 || !dense_rows(W) || W->ne[2] * W->ne[3] != 1 || gr->op != GGML_OP_GET_ROWS || gr->type != GGML_TYPE_F32) continue;
-            const int pg = pos_of(an, gr);
-            if (pg < 0 || an.skip[(size_t) pg] || uses_of(an, gr) != 1 || ggml_nelements(gr) != gr->ne[0] || gr->ne[0] != W->ne[0]) continue;
-            const ggml_tensor * tab = gr->src[0], * idx = gr->src[1];
-            if (ggml_nelements(idx) != 1 || idx->type != GGML_TYPE_I32 || !dense_rows(tab) || !idx->data) continue;
-            switch (tab->type) { case GGML_TYPE_F32: case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: break; default: continue; }
-            const int64_t K = W->ne[0], M = W->ne[1];
-            if (K % 32 != 0 || K > 2048 || ggml_nelements(mm) != M || !ggml_is_contiguous(mm)) continue;
-            std::vector<int> members = { pg, i };
-            float * out = (float *) mm->data;
-            int emit = i;
-            const ggml_tensor * cp = sole_consumer(an, mm);   // ggml_cast(.., F32) of an F32 tensor: a copy - write its storage directly
-            if (cp && cp->op == GGML_OP_CPY && uses_of(an, mm) == 1 && cp->type == GGML_TYPE_F32 && cp->src[0] == mm && ggml_is_contiguous(cp) && cp->view_src == NULL &&
-                ggml_are_same_shape(cp, mm) && pos_of(an, cp) >= 0 && !an.skip[(size_t) pos_of(an, cp)]) {
-                members.push_back(pos_of(an, cp)); out = (float *) cp->data; emit = pos_of(an, cp);
-            }
-            for (int m2 : members) an.skip[(size_t) m2] = 1;
-            const lowrank_embed_args la = { (const char *) tab->data, (int64_t) tab->nb[1], tab->ne[1], (int) tab->type, (const int32_t *) idx->data,
-                                            (const char *) W->data, (int64_t) W->nb[1], (int) K, (int) M, out };
-            p->lowrank_copies.emplace_back(new lowrank_embed_args(la));
-            at_pos[emit].push_back(pstep::special_step([=](hipStream_t s) { k_lowrank_embed(s, la); }, 2, nullptr, p->lowrank_copies.back().get()));
-            p->n_fused += (int) members.size();
-        }
-        // embedding sums
-        for (int i = g->n_nodes - 1; i >= 0; i--) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_ADD) continue;
-            embed_group grp;
-            if (!match_embed_sum(an, i, grp)) continue;
-            bool clash = false;
-            for (int m : grp.members) if (m < 0 || an.skip[(size_t) m]) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            const embed_sum_args a = grp.a;
-            at_pos[i].push_back([=](hipStream_t s) { k_embed_sum(s, a); });
-            p->n_fused += (int) grp.members.size();
-        }
-        // a run of cpy(cont(window of a table), row r of dst) for r = 0, 1, .. (stream slots: the B mask rows, moshi_hot.cpp transformer_graph_step_slots):
-        // one launch for all rows instead of one per row
-        for (int i = 0; i < g->n_nodes; i++) {
-            row_copy_group rg;
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_CONT || !match_row_copies(an, i, rg)) continue;
-            for (int m : rg.members) an.skip[(size_t) m] = 1;
-            const copy_rows_args ra = rg.a;
-            at_pos[rg.emit_pos].push_back([=](hipStream_t s) { k_copy_rows(s, ra); });
-            p->n_fused += (int) rg.members.size();
-        }
-        // cpy(cont(x), dst): copy the strided source straight into dst (the per-step mask row: cont(view of the bias table) -> cpy into the graph input,
-        // transformer.h:1259-1289 - two launches on the LM stream in front of every Temporal graph)
-        for (int i = 0; i < g->n_nodes; i++) {
-            const ggml_tensor * n = g->nodes[i];
-            if (an.skip[(size_t) i] || n->op != GGML_OP_CPY) continue;
-            const ggml_tensor * ct = n->src[0];
-            const int pc = pos_of(an, ct);
-            if (ct->op != GGML_OP_CONT || pc < 0 || an.skip[(size_t) pc] || uses_of(an, ct) != 1 || ct->view_src) continue;
-            if (ct->type != GGML_TYPE_F32 || n->type != GGML_TYPE_F32 || ct->src[0]->type != GGML_TYPE_F32 || !ggml_are_same_shape(ct, ct->src[0]) ||
-                !ggml_are_same_shape(n, ct) || !ggml_is_contiguous(n)) continue;
-            // the strided source is read at the cpy's position instead of the cont's: nothing in between may write through an alias (set_rows, a cpy into
-            // a view of the same table), or the fold would copy newer data than the cont saw
-            bool writer_between = false;
-            for (int j = pc + 1; j < i; j++) if (writes_through_alias(g->nodes[j])) writer_between = true;
-            if (writer_between) continue;
-            an.skip[(size_t) i] = an.skip[(size_t) pc] = 1;
-            const tdesc d = make_tdesc(n), x = make_tdesc(ct->src[0]);
-            at_pos[i].push_back([=](hipStream_t s) { k_cpy(s, d, x); });
-            p->n_fused += 2;
-        }
-        // timestep table of add(a, b): one launch (the Temporal graph's RoPE phase: add(arange, offset) -> timestep_embedding)
-        for (int i = 0; i < g->n_nodes; i++) {
-            const ggml_tensor * n = g->nodes[i];
-            if (an.skip[(size_t) i] || n->op != GGML_OP_TIMESTEP_EMBEDDING) continue;
-            const ggml_tensor * ad = n->src[0];
-            const int pa = pos_of(an, ad);
-            if (ad->op != GGML_OP_ADD || pa < 0 || an.skip[(size_t) pa] || uses_of(an, ad) != 1 || ad->view_src || ad->type != GGML_TYPE_F32) continue;
-            const ggml_tensor * x = ad->src[0], * y = ad->src[1];
-            if (x->type != GGML_TYPE_F32 || y->type != GGML_TYPE_F32 || !ggml_is_contiguous(x) || !ggml_is_contiguous(y) || !ggml_are_same_shape(x, ad) ||
-                ggml_nelements(ad) != ad->ne[0] || !(ggml_nelements(y) == ggml_nelements(ad) || ggml_nelements(y) == 1)) continue;
-            an.skip[(size_t) i] = an.skip[(size_t) pa] = 1;
-            const tdesc d = make_tdesc(n), tx = make_tdesc(x);
-            const float * yp = (const float *) y->data; const int yn = (int) ggml_nelements(y);
-            const int dim = n->op_params[0], mp = n->op_params[1];
-            {
-                pstep st([=](hipStream_t s) { k_timestep_embedding(s, d, tx, dim, mp, yp, yn); });
-                if (x->op == GGML_OP_NONE && y->op == GGML_OP_NONE && !x->view_src && !y->view_src) { st.hoist_dst = (const char *) n->data; st.hoist_bytes = ggml_nbytes(n); }   // (both operands are uploaded leaves)
-                at_pos[i].push_back(std::move(st));
-            }
-            p->n_fused += 2;
-        }
-        // mat-vecs with prologue / epilogue
-        std::unordered_map<const void *, float *> paired_gate;   // storage of a linear_in output h (never materialised) -> g = silu(h_l) * h_r
-        size_t paired_consumed = 0;
-        // on by default (MI355X_PAIRED_GATE=0 turns it off): the gate kernel it removes (-2.3 us per layer) is mostly paid back by linear_out quantising its 44
-        // activation blocks in every workgroup (+1.8 us, profiles/r02_frame_stamps_paired_gate.txt) - neutral while the frame waited for the host between graphs,
-        // +1.1 % once the LM graphs run back to back (354.7 -> 358.7 frames/s, profiles/r02_ab_paired_gate_run_ahead.txt)
-        static const bool no_pair = getenv("MI355X_PAIRED_GATE") != nullptr && atoi(getenv("MI355X_PAIRED_GATE")) == 0;
-        static const bool no_batched_fusion = getenv("MI355X_NO_BATCHED_MM") != nullptr || getenv("MI355X_NO_BATCHED_FUSION") != nullptr;
-        for (int i = 0; i < g->n_nodes; i++) {
-            if (an.skip[(size_t) i] || g->nodes[i]->op != GGML_OP_MUL_MAT) continue;
-            mv_group grp;
-            if (!match_matvec(an, i, grp)) {
-                bmm_group bg;
-                if (!no_batched_fusion && match_batched_mm(an, i, em, bg)) {
-                    bool bclash = false;
-                    for (int m : bg.members) if (m != i && an.skip[(size_t) m]) bclash = true;
-                    if (!bclash) {
-                        for (int m : bg.members) an.skip[(size_t) m] = 1;
-                        at_pos[bg.emit_pos].push_back(bg.run);
-                        p->n_fused += (int) bg.members.size();
-                    }
-                }
-                continue;
-            }
-            bool clash = false;
-            for (int m : grp.members) if (m < 0 || (m != i && an.skip[(size_t) m])) clash = true;
-            if (clash) continue;
-            for (int m : grp.members) an.skip[(size_t) m] = 1;
-            mv_args a = grp.a;
-            if (is_qblock((enum ggml_type) a.wtype) && a.ncols == 1 && !no_argmax_epilogue) {
-                // greedy sampling (sampling.h:57-63): argmax of the logits, optionally copied into the token buffer
-                const ggml_tensor * ynode = g->nodes[grp.emit_pos];
-                const ggml_tensor * am = nullptr;
-                int n_am = 0;
-                for (int j = grp.emit_pos + 1; j < g->n_nodes; j++) if (g->nodes[j]->op == GGML_OP_ARGMAX && g->nodes[j]->src[0] == ynode) { am = g->nodes[j]; n_am++; }
-                if (am && n_am == 1 && !an.skip[(size_t) pos_of(an, am)] && (float *) ynode->data == a.y && ggml_nelements(ynode) == a.M && am->data) {
-                    a.argmax_out[0] = (int32_t *) am->data;
-                    an.skip[(size_t) pos_of(an, am)] = 1;
-                    // a copy of the token into an I32 slot
-                    const ggml_tensor * cp = nullptr;
-                    for (int j = pos_of(an, am) + 1; j < g->n_nodes; j++)
-                        if (g->nodes[j]->op == GGML_OP_CPY && g->nodes[j]->src[0] == am && g->nodes[j]->type == GGML_TYPE_I32 && ggml_nelements(g->nodes[j]) == 1) { cp = g->nodes[j]; break; }
-                    if (cp && !an.skip[(size_t) pos_of(an, cp)]) { a.argmax_out[1] = (int32_t *) cp->data; an.skip[(size_t) pos_of(an, cp)] = 1; }
-                    unsigned * tk = (unsigned *) em.ws(256 + 2 * 4 * 8192);   // arrival counter | per-workgroup argmax candidates (value, index)
-                    HIP_CHECK(hipMemsetAsync(tk, 0, 256, em.c->stream));
-                    a.ticket = tk;
-                    p->n_fused += 1 + (cp ? 1 : 0);
-                }
-            }
-            if (a.prologue == MV_PLAIN && is_qblock((enum ggml_type) a.wtype) && a.ncols == 1 && !no_attn_prologue) {
-                // x is the output of a single-token attention over a short ring (Depth transformer): recompute it in every
-                // workgroup of this projection instead of launching it on its own (16 heads x 8 slots is ~nothing)
-                for (auto & ag : attn_groups) {
-                    const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || ag.B > 1 || ag.column || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
-                    if (a.K != 1024 || at.H != 16 || ag.emit_pos > grp.emit_pos || uses_of(an, g->nodes[ag.emit_pos]) != 1) continue;
-                    p->attn_copies.emplace_back(new attn_args(at));   // owned by the plan, passed by value at launch
-                    a.prologue = MV_ATTN;
-                    a.attn = p->attn_copies.back().get();
-                    ag.emit_pos = -1;
-                    break;
-                }
-            }
-            if (a.prologue == MV_RMSNORM && a.wtype == GGML_TYPE_Q4_K && a.ncols == 1 && keep && !(c->flags & 512) && grp.emit_pos == i) {
-                // the Temporal layer's in_proj, read by nothing but the layer's single-token attention over a LONG ring: the attention runs as the TAIL of
-                // the projection's own launch (inproj_attn_kernel) - emitted where the attention stood; no launch is emitted for the projection itself
-                bool merged = false;
-                for (auto & ag : attn_groups) {
-                    const attn_args & at = ag.a;
-                    if (ag.emit_pos < 0 || ag.B > 1 || ag.column || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
-                    if (!k_inproj_attn_supported(a, at, c->usable_cus)) continue;
-                    // every reader of the projection's output must be inside the attention block
-                    // (followed through layout-only nodes - a view / reshape / permute / transpose of the output is the output: a reader of such an alias that is
-                    // not part of the attention block would run before the deferred projection has written anything)
-                    bool private_y = true;
-                    std::vector<const ggml_tensor *> aliases { g->nodes[i] };
-                    for (int j = i + 1; j < g->n_nodes && private_y; j++) {
-                        const ggml_tensor * nj = g->nodes[j];
-                        bool reads = false;
-                        for (int sidx = 0; sidx < GGML_MAX_SRC; sidx++)
-                            if (nj->src[sidx] && std::find(aliases.begin(), aliases.end(), nj->src[sidx]) != aliases.end()) reads = true;
-                        if (!reads) continue;
-                        const bool layout = nj->op == GGML_OP_VIEW || nj->op == GGML_OP_RESHAPE || nj->op == GGML_OP_PERMUTE || nj->op == GGML_OP_TRANSPOSE;
-                        if (layout) { aliases.push_back(nj); continue; }
-                        if (std::find(ag.members.begin(), ag.members.end(), j) == ag.members.end()) private_y = false;
-                    }
-                    if (!private_y || !spin_kernels_allowed(c)) continue;
-                    const mv_args am = a; const attn_args aa = at;
-                    unsigned * err = c->err_dev;
-                    const size_t wn = k_inproj_attn_ws_size(a, at);
-                    void * ws = em.ws(wn);
-                    HIP_CHECK(hipMemsetAsync(ws, 0, wn, c->stream));
-                    at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), [=](hipStream_t s) { k_inproj_attn(s, am, aa, ws, err); });
-                    ag.emit_pos = -1;
-                    p->n_fused += 1; p->n_attn_folded++; c->stats.attention_folds_planned++;
-                    merged = true;
-                    break;
-                }
-                if (merged) { if (grp.members.size() > 1) p->n_fused += (int) grp.members.size(); continue; }
-            }
-            if (!no_pair && a.prologue != MV_GATE_SILU && a.ncols == 1 && a.residual == nullptr && a.res_embed.table == nullptr && a.ticket == nullptr &&
-                a.M % 2 == 0 && k_matvec_pair_ok(a.wtype, a.K, a.M / 2) && grp.emit_pos == i) {
-                // linear_in of a gated FFN whose only readers are the silu(left) * right pair feeding a long linear_out: let every workgroup take
-                // matching rows of both halves and write g itself (the [2 F] intermediate and the gate kernel disappear)
-                const ggml_tensor * h = g->nodes[i];
-                const int64_t F = a.M / 2;
-                const ggml_tensor * l = nullptr, * r = nullptr;
-                int nv = 0;
-                for (int j = i + 1; j < g->n_nodes && j < i + 12; j++) {
-                    const ggml_tensor * v = g->nodes[j];
-                    if (v->op == GGML_OP_VIEW && v->src[0] == h) { nv++; if (v->data == h->data) l = v; else if ((const char *) v->data == (const char *) h->data + F * 4) r = v; }
-                }
-                if (uses_of(an, h) == 2 && nv == 2 && l && r && ggml_nelements(l) == F && ggml_nelements(r) == F && ggml_is_contiguous(l) && ggml_is_contiguous(r) &&
-                    uses_of(an, l) == 1 && uses_of(an, r) == 1) {
-                    const ggml_tensor * sl = sole_consumer(an, l), * ml = sole_consumer(an, r);
-                    if (sl && sl->op == GGML_OP_UNARY && sl->op_params[0] == GGML_UNARY_OP_SILU && uses_of(an, sl) == 1 && ml && ml->op == GGML_OP_MUL &&
-                        ml->src[0] == sl && ml->src[1] == r && uses_of(an, ml) == 1) {
-                        const ggml_tensor * mo = sole_consumer(an, ml);
-                        // the pairing is decided HERE, for both sides: the consumer's own match is run now and must come out as the gated prologue over this
-                        // very h with none of its members claimed by another group - otherwise h has to be written and nothing is redirected
-                        bool consumer_ok = false;
-                        if (mo && mo->op == GGML_OP_MUL_MAT && mo->src[1] == ml && is_qblock(mo->src[0]->type) && mo->src[0]->ne[0] == F && F > 4096 &&
-                            !an.skip[(size_t) pos_of(an, mo)]) {
-                            mv_group cg;
-                            const int mpos = pos_of(an, mo);
-                            consumer_ok = match_matvec(an, mpos, cg) && cg.a.prologue == MV_GATE_SILU && (const void *) cg.a.x == h->data && cg.a.K == F && cg.a.ncols == 1;
-                            for (int m2 : cg.members) if (m2 < 0 || (m2 != mpos && an.skip[(size_t) m2])) consumer_ok = false;
-                        }
-                        if (consumer_ok) {
-                            float * gbuf = (float *) em.ws((size_t) F * 4);
-                            a.pair_F = F;
-                            a.y = gbuf;
-                            paired_gate[h->data] = gbuf;
-                        }
-                    }
-                }
-            }
-            if (a.prologue == MV_GATE_SILU && is_qblock((enum ggml_type) a.wtype) && a.K > 4096 && paired_gate.count((const void *) a.x)) {
-                // the producer already wrote g = silu(left) * right: plain activation, quantised in this kernel's prologue
-                const float * gbuf = paired_gate[(const void *) a.x];
-                paired_consumed++;
-                a.prologue = MV_PLAIN;
-                a.x = gbuf;
-                a.x_cs = a.K;
-            }
-            if (a.prologue == MV_GATE_SILU && is_qblock((enum ggml_type) a.wtype) && a.K > 4096) {
-                // long gated rows: quantise the activation once, not once per workgroup
-                void * blocks = em.ws((size_t) (a.K / 256) * MV_XBLK_BYTES);
-                const float * h = a.x; const int64_t K = a.K;
-                const int wt = a.wtype;
-                at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_gate_quant_q8k(s, h, K, blocks, wt); });
-                a.prologue = MV_PREQ8K;
-                a.x = (const float *) blocks;
-            }
-            at_pos[grp.emit_pos].push_back(pstep(a));
-            if (grp.members.size() > 1) p->n_fused += (int) grp.members.size();
-        }
-        GGML_ASSERT(paired_consumed == paired_gate.size() && "a linear_in was redirected to the paired gate form but its linear_out did not pick the gate vector up");
+    if (!is_qblock((enum ggml_type) a.wtype) || a.ncols != 1 || no_argmax_epilogue) return;
+    const analysis & an = pl.an; const ggml_cgraph * g = pl.g;
+    const ggml_tensor * ynode = g->nodes[grp.emit_pos];
+    const ggml_tensor * am = nullptr;
+    int n_am = 0;
+    for (int j = grp.emit_pos + 1; j < g->n_nodes; j++) if (g->nodes[j]->op == GGML_OP_ARGMAX && g->nodes[j]->src[0] == ynode) { am = g->nodes[j]; n_am++; }
+    if (!am || n_am != 1 || (float *) ynode->data != a.y || ggml_nelements(ynode) != a.M || !am->data || !claim(pl, { pos_of(an, am) })) return;
+    a.argmax_out[0] = (int32_t *) am->data;
+    // a copy of the token into an I32 slot
+    const ggml_tensor * cp = nullptr;
+    for (int j = pos_of(an, am) + 1; j < g->n_nodes; j++)
+        if (g->nodes[j]->op == GGML_OP_CPY && g->nodes[j]->src[0] == am && g->nodes[j]->type == GGML_TYPE_I32 && ggml_nelements(g->nodes[j]) == 1) { cp = g->nodes[j]; break; }
+    if (cp && claim(pl, { pos_of(an, cp) })) a.argmax_out[1] = (int32_t *) cp->data;
+    unsigned * tk = (unsigned *) pl.em.ws(256 + 2 * 4 * 8192);   // arrival counter | per-workgroup argmax candidates (value, index)
+    HIP_CHECK(hipMemsetAsync(tk, 0, 256, pl.c->stream));
+    a.ticket = tk;
+    pl.p->n_fused += 1 + (cp ? 1 : 0);
+}
+
+// x is the output of a single-token attention over a short ring (Depth transformer): recompute it in every workgroup of this projection
+// instead of launching it on its own (16 heads x 8 slots is ~nothing)
+static void fold_short_ring_attention(planner & pl, const mv_group & grp, mv_args & a) {
+    static const bool no_attn_prologue = getenv("MI355X_NO_ATTN_PROLOGUE") != nullptr;
+    if (a.prologue != MV_PLAIN || !is_qblock((enum ggml_type) a.wtype) || a.ncols != 1 || no_attn_prologue) return;
+    for (auto & ag : pl.attn_groups) {
+        const attn_args & at = ag.a;
+        if (ag.emit_pos < 0 || ag.B > 1 || ag.column || (const float *) at.out != a.x || at.T != 1 || at.D != 64 || at.C > 8 || (int64_t) at.H * at.D != a.K) continue;
+        if (a.K != 1024 || at.H != 16 || ag.emit_pos > grp.emit_pos || uses_of(pl.an, pl.g->nodes[ag.emit_pos]) != 1) continue;
+        pl.p->attn_copies.emplace_back(new attn_args(at));   // owned by the plan, passed by value at launch
+        a.prologue = MV_ATTN;
+        a.attn = pl.p->attn_copies.back().get();
+        ag.emit_pos = -1;
+        return;
     }
-    if (fuse) {
-        // LayerNorm with weight (and bias) over one row that no mat-vec prologue took (tts: norm_cross in front of the cross-attention's row-view projection):
-        // ggml_norm -> ggml_mul(., w) -> [ggml_add(., b)] as one launch with the three launches' float operations
-        for (int i = 0; i < g->n_nodes; i++) {
-            const ggml_tensor * nn = g->nodes[i];
-            if (an.skip[(size_t) i] || (nn->op != GGML_OP_NORM && nn->op != GGML_OP_RMS_NORM) || nn->type != GGML_TYPE_F32 || uses_of(an, nn) != 1) continue;
-            if (nn->src[0]->type != GGML_TYPE_F32 || nn->src[0]->nb[0] != 4) continue;
-            // one row, or the B contiguous rows of a B-column LM activation [dim, 1, B] under the same [dim] weight and bias (norm_cross of B-column tts
-            // steps), one workgroup per row. Only that layout and LayerNorm: every other multi-row norm keeps the plan it had.
-            const int64_t n_rows = ggml_nelements(nn) / nn->ne[0];
-            if (n_rows != 1 && (nn->op != GGML_OP_NORM || nn->ne[1] != 1 || nn->ne[2] != n_rows || n_rows > 16 || !ggml_is_contiguous(nn) || !ggml_is_contiguous(nn->src[0]))) continue;
-            const ggml_tensor * ml = sole_consumer(an, nn);
-            if (!ml || ml->op != GGML_OP_MUL || ml->view_src || pos_of(an, ml) < 0 || an.skip[(size_t) pos_of(an, ml)] || !ggml_are_same_shape(ml, nn)) continue;
-            const ggml_tensor * wv = ml->src[0] == nn ? ml->src[1] : ml->src[0];
-            if (wv == nn || wv->type != GGML_TYPE_F32 || !ggml_is_contiguous(wv) || ggml_nelements(wv) != nn->ne[0] || !wv->data || !ggml_is_contiguous(ml)) continue;
-            std::vector<int> members = { i, pos_of(an, ml) };
-            const ggml_tensor * last = ml; const float * bp = nullptr;
-            const ggml_tensor * ad = uses_of(an, ml) == 1 ? sole_consumer(an, ml) : nullptr;
-            if (ad && ad->op == GGML_OP_ADD && !ad->view_src && pos_of(an, ad) >= 0 && !an.skip[(size_t) pos_of(an, ad)] && ggml_is_contiguous(ad)) {
-                const ggml_tensor * bv = ad->src[0] == ml ? ad->src[1] : ad->src[0];
-                if (bv != ml && bv->type == GGML_TYPE_F32 && ggml_is_contiguous(bv) && ggml_nelements(bv) == nn->ne[0] && bv->data && bv->op == GGML_OP_NONE && ad->src[0] == ml && ggml_are_same_shape(ad, nn)) {
-                    bp = (const float *) bv->data; last = ad; members.push_back(pos_of(an, ad));
-                }
-            }
-            // (the weight must be the second factor or the first: the product is the same float either way; the bias must be the second summand: v + b)
-            for (int m2 : members) an.skip[(size_t) m2] = 1;
-            const tdesc a = make_tdesc(nn->src[0]); const float eps = ggml_get_op_params_f32(nn, 0); const int rms = nn->op == GGML_OP_RMS_NORM;
-            const float * wp = (const float *) wv->data; float * out = (float *) last->data;
-            at_pos[pos_of(an, last)].push_back([=](hipStream_t s) { k_norm_affine(s, a, eps, rms, wp, bp, out); });
-            p->n_fused += (int) members.size();
+}
+
+// the Temporal layer's in_proj at node i, read by nothing but the layer's single-token attention over a LONG ring: the attention runs as the TAIL of
+// the projection's own launch (inproj_attn_kernel) - emitted where the attention stood. True: no launch is to be emitted for the projection itself
+static bool merge_inproj_attention(planner & pl, int i, const mv_group & grp, const mv_args & a) {
+    hip_ctx * c = pl.c; const ggml_cgraph * g = pl.g;
+    if (a.prologue != MV_RMSNORM || a.wtype != GGML_TYPE_Q4_K || a.ncols != 1 || !pl.keep || (c->flags & 512) || grp.emit_pos != i) return false;
+    for (auto & ag : pl.attn_groups) {
+        const attn_args & at = ag.a;
+        if (ag.emit_pos < 0 || ag.B > 1 || ag.column || at.q != a.y || ag.emit_pos < grp.emit_pos) continue;
+        if (!k_inproj_attn_supported(a, at, c->usable_cus)) continue;
+        // every reader of the projection's output must be inside the attention block
+        // (followed through layout-only nodes - a view / reshape / permute / transpose of the output is the output: a reader of such an alias that is
+        // not part of the attention block would run before the deferred projection has written anything)
+        bool private_y = true;
+        std::vector<const ggml_tensor *> aliases { g->nodes[i] };
+        for (int j = i + 1; j < g->n_nodes && private_y; j++) {
+            const ggml_tensor * nj = g->nodes[j];
+            bool reads = false;
+            for (int sidx = 0; sidx < GGML_MAX_SRC; sidx++)
+                if (nj->src[sidx] && std::find(aliases.begin(), aliases.end(), nj->src[sidx]) != aliases.end()) reads = true;
+            if (!reads) continue;
+            if (is_layout_op(nj->op)) { aliases.push_back(nj); continue; }
+            if (std::find(ag.members.begin(), ag.members.end(), j) == ag.members.end()) private_y = false;
         }
+        if (!private_y || !spin_kernels_allowed(c)) continue;
+        const mv_args am = a; const attn_args aa = at;
+        unsigned * err = c->err_dev;
+        const size_t wn = k_inproj_attn_ws_size(a, at);
+        void * ws = pl.em.ws(wn);
+        HIP_CHECK(hipMemsetAsync(ws, 0, wn, c->stream));
+        pl.at_pos[ag.emit_pos].insert(pl.at_pos[ag.emit_pos].begin(), [=](hipStream_t s) { k_inproj_attn(s, am, aa, ws, err); });
+        ag.emit_pos = -1;
+        pl.p->n_fused += 1; pl.p->n_attn_folded++; c->stats.attention_folds_planned++;
+        return true;
     }
-    // slot prefill: the column groups of one layer of one pass (consecutive groups of one shape with nothing but layout nodes and their own members
-    // between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase
+    return false;
+}
+
+// linear_in of a gated FFN at node i whose only readers are the silu(left) * right pair feeding a long linear_out: let every workgroup take
+// matching rows of both halves and write g itself (the [2 F] intermediate and the gate kernel disappear)
+static void pair_gate_producer(planner & pl, int i, const mv_group & grp, mv_args & a) {
+    // on by default (MI355X_PAIRED_GATE=0 turns it off): the gate kernel it removes (-2.3 us per layer) is mostly paid back by linear_out quantising its 44
+    // activation blocks in every workgroup (+1.8 us, profiles/r02_frame_stamps_paired_gate.txt) - neutral while the frame waited for the host between graphs,
+    // +1.1 % once the LM graphs run back to back (354.7 -> 358.7 frames/s, profiles/r02_ab_paired_gate_run_ahead.txt)
+    static const bool no_pair = getenv("MI355X_PAIRED_GATE") != nullptr && atoi(getenv("MI355X_PAIRED_GATE")) == 0;
+    if (no_pair || a.prologue == MV_GATE_SILU || a.ncols != 1 || a.residual != nullptr || a.res_embed.table != nullptr || a.ticket != nullptr ||
+        a.M % 2 != 0 || !k_matvec_pair_ok(a.wtype, a.K, a.M / 2) || grp.emit_pos != i) return;
+    const analysis & an = pl.an; const ggml_cgraph * g = pl.g;
+    const ggml_tensor * h = g->nodes[i];
+    const int64_t F = a.M / 2;
+    const ggml_tensor * l = nullptr, * r = nullptr;
+    int nv = 0;
+    for (int j = i + 1; j < g->n_nodes && j < i + 12; j++) {
+        const ggml_tensor * v = g->nodes[j];
+        if (v->op == GGML_OP_VIEW && v->src[0] == h) { nv++; if (v->data == h->data) l = v; else if ((const char *) v->data == (const char *) h->data + F * 4) r = v; }
+    }
+    if (!(uses_of(an, h) == 2 && nv == 2 && l && r && ggml_nelements(l) == F && ggml_nelements(r) == F && ggml_is_contiguous(l) && ggml_is_contiguous(r) &&
+          uses_of(an, l) == 1 && uses_of(an, r) == 1)) return;
+    const ggml_tensor * sl = sole_consumer(an, l), * ml = sole_consumer(an, r);
+    if (!(sl && sl->op == GGML_OP_UNARY && sl->op_params[0] == GGML_UNARY_OP_SILU && uses_of(an, sl) == 1 && ml && ml->op == GGML_OP_MUL &&
+          ml->src[0] == sl && ml->src[1] == r && uses_of(an, ml) == 1)) return;
+    const ggml_tensor * mo = sole_consumer(an, ml);
+    // the pairing is decided HERE, for both sides: the consumer's own match is run now and must come out as the gated prologue over this
+    // very h with none of its members claimed by another group - otherwise h has to be written and nothing is redirected
+    if (!(mo && mo->op == GGML_OP_MUL_MAT && mo->src[1] == ml && is_qblock(mo->src[0]->type) && mo->src[0]->ne[0] == F && F > 4096 &&
+          !an.skip[(size_t) pos_of(an, mo)])) return;
+    mv_group cg;
+    const int mpos = pos_of(an, mo);
+    if (!(match_matvec(an, mpos, cg) && cg.a.prologue == MV_GATE_SILU && (const void *) cg.a.x == h->data && cg.a.K == F && cg.a.ncols == 1) ||
+        !claimable(pl, cg.members, mpos)) return;
+    float * gbuf = (float *) pl.em.ws((size_t) F * 4);
+    a.pair_F = F;
+    a.y = gbuf;
+    pl.paired_gate[h->data] = gbuf;
+}
+
+// linear_out of a pair: the producer already wrote g = silu(left) * right - plain activation, quantised in this kernel's prologue. True: taken
+static bool take_paired_gate(planner & pl, mv_args & a) {
+    if (a.prologue != MV_GATE_SILU || !is_qblock((enum ggml_type) a.wtype) || a.K <= 4096 || !pl.paired_gate.count((const void *) a.x)) return false;
+    a.x = pl.paired_gate[(const void *) a.x];
+    a.prologue = MV_PLAIN;
+    a.x_cs = a.K;
+    return true;
+}
+
+// long gated rows (no pair): quantise the activation once, in a launch in front of the projection, not once per workgroup
+static void prequantise_long_gate(planner & pl, const mv_group & grp, mv_args & a) {
+    if (a.prologue != MV_GATE_SILU || !is_qblock((enum ggml_type) a.wtype) || a.K <= 4096) return;
+    void * blocks = pl.em.ws((size_t) (a.K / 256) * MV_XBLK_BYTES);
+    const float * h = a.x; const int64_t K = a.K;
+    const int wt = a.wtype;
+    pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_gate_quant_q8k(s, h, K, blocks, wt); });
+    a.prologue = MV_PREQ8K;
+    a.x = (const float *) blocks;
+}
+
+// mat-vecs with prologue / epilogue (and, where several rows ride one product, the batched mat-mul). Its members count as fused only when the launch
+// replaces more than the mul_mat itself
+static void pass_matvecs(planner & pl) {
+    static const bool no_batched_fusion = getenv("MI355X_NO_BATCHED_MM") != nullptr || getenv("MI355X_NO_BATCHED_FUSION") != nullptr;
+    size_t paired_consumed = 0;
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_MUL_MAT) continue;
+        mv_group grp;
+        if (!match_matvec(pl.an, i, grp)) {
+            bmm_group bg;
+            if (!no_batched_fusion && match_batched_mm(pl.an, i, pl.em, bg) && claim_group(pl, bg, i)) pl.at_pos[bg.emit_pos].push_back(bg.run);
+            continue;
+        }
+        if (!claim(pl, grp.members, i)) continue;
+        const int n_members = grp.members.size() > 1 ? (int) grp.members.size() : 0;
+        mv_args a = grp.a;
+        fold_argmax_epilogue(pl, grp, a);
+        fold_short_ring_attention(pl, grp, a);
+        if (merge_inproj_attention(pl, i, grp, a)) { pl.p->n_fused += n_members; continue; }   // (emitted with the attention)
+        pair_gate_producer(pl, i, grp, a);
+        if (take_paired_gate(pl, a)) paired_consumed++;
+        prequantise_long_gate(pl, grp, a);
+        pl.at_pos[grp.emit_pos].push_back(pstep(a));
+        pl.p->n_fused += n_members;
+    }
+    GGML_ASSERT(paired_consumed == pl.paired_gate.size() && "a linear_in was redirected to the paired gate form but its linear_out did not pick the gate vector up");
+}
+
+// LayerNorm with weight (and bias) over one row that no mat-vec prologue took
+static void pass_norm_affine(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        norm_affine_group grp;
+        if (pl.an.skip[(size_t) i] || !match_norm_affine(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: the matcher tests position and an.skip of the mul and of the add; the norm is node i)
+        const tdesc a = grp.x; const float eps = grp.eps; const int rms = grp.rms;
+        const float * wp = grp.w, * bp = grp.b; float * out = grp.out;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_norm_affine(s, a, eps, rms, wp, bp, out); });
+    }
+}
+
+// ---- after the fusion passes ----
+// slot prefill: the column groups of one layer of one pass (consecutive groups of one shape with nothing but layout nodes and their own members
+// between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase
+static void merge_column_attention_blocks(planner & pl) {
+    std::vector<attn_group> & attn_groups = pl.attn_groups;
     for (size_t gi = 0; gi < attn_groups.size(); ) {
         if (!attn_groups[gi].column || attn_groups[gi].emit_pos < 0) { gi++; continue; }
         const attn_args & a0 = attn_groups[gi].a;
@@ -2446,7 +2526,7 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             both.insert(n.members.begin(), n.members.end());
             const int nlo = n.emit_pos < lo ? n.emit_pos : lo, nhi = n.emit_pos > hi ? n.emit_pos : hi;
             bool clean = true;
-            for (int i = nlo + 1; i < nhi && clean; i++) if (!is_view_op(g->nodes[i]->op) && !both.count(i)) clean = false;
+            for (int i = nlo + 1; i < nhi && clean; i++) if (!is_view_op(pl.g->nodes[i]->op) && !both.count(i)) clean = false;
             if (!clean) break;
             inside.swap(both); lo = nlo; hi = nhi;
             if (b.T > 1 && !rows) rows = &b;
@@ -2462,26 +2542,32 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             ba.job[k - gi] = { b.q, b.k, b.v, b.kcache, b.vcache, b.mask, b.rot, b.index, b.out, b.T };
             attn_groups[k].emit_pos = -1;
         }
-        unsigned * err = c->err_dev;
-        auto & at = at_pos[hi];
+        unsigned * err = pl.c->err_dev;
+        auto & at = pl.at_pos[hi];
         at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 0; k_attn_blocks(s, b, err); });
         at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 1; k_attn_blocks(s, b, err); });
-        p->n_attn_block_launches += 2; p->n_attn_block_jobs += ba.n_jobs;
+        pl.p->n_attn_block_launches += 2; pl.p->n_attn_block_jobs += ba.n_jobs;
         gi = ge;
     }
-    for (auto & ag : attn_groups) {
+}
+
+// the attention groups nothing absorbed, each in FRONT of whatever else is emitted at its position
+static void emit_attention_groups(planner & pl) {
+    hip_ctx * c = pl.c;
+    for (auto & ag : pl.attn_groups) {
         if (ag.emit_pos < 0) continue;
         const attn_args a = ag.a;
         unsigned * err = c->err_dev;
+        auto & at = pl.at_pos[ag.emit_pos];
         if (ag.B > 1) {   // lockstep streams: one launch for every (head, stream)
             const attn_streams_args sa = ag.sa;
-            at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), [=](hipStream_t s) { k_attn_streams(s, sa, err); });
+            at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams(s, sa, err); });
             continue;
         }
         if (a.T > 4) {
             // a block of T > 4 new rows (batched prompt prefill): one workgroup per head and group of 4 rows; first every row's K / V
             // goes into the ring, then all groups attend at once (causality is in the mask rows)
-            at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), [=](hipStream_t s) {
+            at.insert(at.begin(), [=](hipStream_t s) {
                 attn_args b = a;
                 b.n_groups = (a.T + 3) / 4;
                 b.write_only = 1; k_attn_decode(s, b, nullptr, err);
@@ -2490,96 +2576,149 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
             continue;
         }
         void * ws = nullptr;
-        if (const size_t n = k_attn_split_resident(a, c->usable_cus) ? k_attn_decode_ws_size(a) : 0) { ws = em.ws(n); HIP_CHECK(hipMemsetAsync(ws, 0, n, c->stream)); }   // sequence numbers start at zero
+        if (const size_t n = k_attn_split_resident(a, c->usable_cus) ? k_attn_decode_ws_size(a) : 0) { ws = pl.em.ws(n); HIP_CHECK(hipMemsetAsync(ws, 0, n, c->stream)); }   // sequence numbers start at zero
         if (a.T <= 4 && a.n_groups <= 1 && !ws) {
-            p->attn_copies.emplace_back(new attn_args(a));
-            at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), pstep::special_step([=](hipStream_t s) { k_attn_decode(s, a, ws, err); }, 1, p->attn_copies.back().get(), nullptr));
+            pl.p->attn_copies.emplace_back(new attn_args(a));
+            at.insert(at.begin(), pstep::special_step([=](hipStream_t s) { k_attn_decode(s, a, ws, err); }, 1, pl.p->attn_copies.back().get(), nullptr));
         } else
-        at_pos[ag.emit_pos].insert(at_pos[ag.emit_pos].begin(), [=](hipStream_t s) { k_attn_decode(s, a, ws, err); });
+            at.insert(at.begin(), [=](hipStream_t s) { k_attn_decode(s, a, ws, err); });
     }
-    const bool dump = getenv("MI355X_DUMP_PLAN") != nullptr;
+}
+
+static bool dump_plan() { return getenv("MI355X_DUMP_PLAN") != nullptr; }
+
+// the plan's steps in node order: a generic launch for every node nobody claimed, then the groups emitted at that position (MI355X_DUMP_PLAN lists both)
+static void lay_out_steps(planner & pl) {
+    const bool dump = dump_plan();
+    const ggml_cgraph * g = pl.g;
     for (int i = 0; i < g->n_nodes; i++) {
+        auto it = pl.at_pos.find(i);
         if (dump) {
             const ggml_tensor * n = g->nodes[i];
-            const bool layout = n->op == GGML_OP_VIEW || n->op == GGML_OP_RESHAPE || n->op == GGML_OP_PERMUTE || n->op == GGML_OP_TRANSPOSE;
-            auto itd = at_pos.find(i);
-            if (!layout || itd != at_pos.end())
+            const bool layout = is_layout_op(n->op);
+            if (!layout || it != pl.at_pos.end())
                 fprintf(stderr, "plan %4d %-18s [%5lld %5lld %4lld %2lld] %s%s%s\n", i, ggml_op_name(n->op), (long long) n->ne[0], (long long) n->ne[1], (long long) n->ne[2],
-                        (long long) n->ne[3], an.skip[(size_t) i] ? "fused" : (layout ? "-" : "GENERIC"), itd != at_pos.end() ? " <emit group>" : "", n->view_src ? " (alias)" : "");
+                        (long long) n->ne[3], pl.an.skip[(size_t) i] ? "fused" : (layout ? "-" : "GENERIC"), it != pl.at_pos.end() ? " <emit group>" : "", n->view_src ? " (alias)" : "");
         }
-        if (!an.skip[(size_t) i]) {
-            if (g->nodes[i]->op == GGML_OP_SOFT_MAX || g->nodes[i]->op == GGML_OP_SET_ROWS) p->n_generic_attn_nodes++;
-            emit_generic(em, g->nodes[i]);
+        if (!pl.an.skip[(size_t) i]) {
+            if (g->nodes[i]->op == GGML_OP_SOFT_MAX || g->nodes[i]->op == GGML_OP_SET_ROWS) pl.p->n_generic_attn_nodes++;
+            emit_generic(pl.em, g->nodes[i]);
         }
-        auto it = at_pos.find(i);
-        if (it != at_pos.end()) for (auto & f : it->second) p->steps.push_back(f);
+        if (it != pl.at_pos.end()) for (auto & f : it->second) pl.p->steps.push_back(f);
     }
-    // Persistent chains: a run of consecutive block mat-vecs each of which waits on its predecessor (the chained Depth transformer,
-    // lm.h:446-553: 26 mat-vecs per step, 8 / 16 steps per graph) becomes ONE launch of the chain engine (hip_chain.hip).
-    // (only for plans that are kept - cached graphs, profile mode: a one-off plan is launched once and freed at once, a chain's tables would be built,
-    // uploaded and torn down per compute)
-    if (fuse && keep && !(c->flags & 16) && ((c->flags & 32) || k_chain_default_on()) && spin_kernels_possible(c)) {
-        // The codec transformers' RoPE table sits between layer 0's in_proj and its attention in node order: moved in front of that in_proj (whose operands it
-        // does not touch), the whole stack is one run (hip_chain_mimi.h takes it from in_proj 0; otherwise the program starts at layer 0's attention).
-        for (size_t i = 1; i + 1 < p->steps.size(); i++) {
-            pstep & h = p->steps[i];
-            const pstep & m = p->steps[i - 1];
-            if (!h.hoist_dst || !m.is_mv || m.mv.special || m.mv.wtype != GGML_TYPE_F32 || m.mv.ncols != 2 || !p->steps[i + 1].is_mv) continue;
-            auto clash = [&](const float * q, int64_t n_floats) { return q && (const char *) q < h.hoist_dst + h.hoist_bytes && h.hoist_dst < (const char *) (q + n_floats); };
-            const mv_args & a = m.mv;
-            if (clash(a.x, a.x_cs * (a.ncols - 1) + a.K) || clash(a.y, a.y_cs * (a.ncols - 1) + a.M) || clash(a.x_out, a.K * a.ncols) || clash(a.residual, a.r_cs * (a.ncols - 1) + a.M) ||
-                clash(a.alpha, a.K) || clash(a.beta, a.K)) continue;
-            std::swap(p->steps[i - 1], p->steps[i]);
-        }
-        std::vector<pstep> merged;
-        size_t i = 0;
-        while (i < p->steps.size()) {
-            if (p->steps[i].vq) {
-                // consecutive levels of one RVQ encode stack (vq.h:97-114): one persistent launch with a candidate hand-off per level (hip_chain.hip, vq_chain_kernel)
-                size_t e = i;
-                std::vector<vq_level_args> lv;
-                while (e < p->steps.size() && p->steps[e].vq && lv.size() < 32 && (lv.empty() || ((const void *) p->steps[e].vq->resid == (const void *) lv.back().resid_out && p->steps[e].vq->resid_stride == 4))) {
-                    lv.push_back(*p->steps[e].vq); e++;
-                }
-                if (lv.size() >= 2 && k_vq_chain_accept(lv.data(), (int) lv.size(), c->usable_cus) && spin_kernels_allowed(c)) {
-                    void * ws = em.ws(k_vq_chain_ws_size((int) lv.size()));
-                    vq_chain_plan * vc = k_vq_chain_create(c->stream, lv.data(), (int) lv.size(), ws, c->err_dev);
-                    p->vq_chains.push_back(vc);
-                    p->n_vq_chained += (int) lv.size();
-                    merged.push_back(pstep([vc](hipStream_t s) { k_vq_chain_launch(s, vc); }));
-                    if (dump) fprintf(stderr, "plan: %zu consecutive RVQ levels -> one launch\n", lv.size());
-                    i = e;
-                    continue;
-                }
-                merged.push_back(std::move(p->steps[i])); i++; continue;
-            }
-            if (!p->steps[i].is_mv) { merged.push_back(std::move(p->steps[i])); i++; continue; }
+}
+
+// The codec transformers' RoPE table sits between layer 0's in_proj and its attention in node order: moved in front of that in_proj (whose operands it
+// does not touch), the whole stack is one run (hip_chain_mimi.h takes it from in_proj 0; otherwise the program starts at layer 0's attention).
+static void hoist_rope_tables(planner & pl) {
+    plan_t * p = pl.p;
+    for (size_t i = 1; i + 1 < p->steps.size(); i++) {
+        pstep & h = p->steps[i];
+        const pstep & m = p->steps[i - 1];
+        if (!h.hoist_dst || !m.is_mv || m.mv.special || m.mv.wtype != GGML_TYPE_F32 || m.mv.ncols != 2 || !p->steps[i + 1].is_mv) continue;
+        auto clash = [&](const float * q, int64_t n_floats) { return q && (const char *) q < h.hoist_dst + h.hoist_bytes && h.hoist_dst < (const char *) (q + n_floats); };
+        const mv_args & a = m.mv;
+        if (clash(a.x, a.x_cs * (a.ncols - 1) + a.K) || clash(a.y, a.y_cs * (a.ncols - 1) + a.M) || clash(a.x_out, a.K * a.ncols) || clash(a.residual, a.r_cs * (a.ncols - 1) + a.M) ||
+            clash(a.alpha, a.K) || clash(a.beta, a.K)) continue;
+        std::swap(p->steps[i - 1], p->steps[i]);
+    }
+}
+
+// Persistent chains: a run of consecutive block mat-vecs each of which waits on its predecessor (the chained Depth transformer,
+// lm.h:446-553: 26 mat-vecs per step, 8 / 16 steps per graph) becomes ONE launch of the chain engine (hip_chain.hip).
+// (only for plans that are kept - cached graphs, profile mode: a one-off plan is launched once and freed at once, a chain's tables would be built,
+// uploaded and torn down per compute)
+static bool chains_wanted(const planner & pl) {
+    return pl.fuse && pl.keep && !(pl.c->flags & 16) && ((pl.c->flags & 32) || k_chain_default_on()) && spin_kernels_possible(pl.c);
+}
+static void merge_chains(planner & pl) {
+    const bool dump = dump_plan();
+    hip_ctx * c = pl.c; plan_t * p = pl.p; emitter & em = pl.em;
+    std::vector<pstep> merged;
+    size_t i = 0;
+    while (i < p->steps.size()) {
+        if (p->steps[i].vq) {
+            // consecutive levels of one RVQ encode stack (vq.h:97-114): one persistent launch with a candidate hand-off per level (hip_chain.hip, vq_chain_kernel)
             size_t e = i;
-            while (e < p->steps.size() && p->steps[e].is_mv) e++;
-            std::vector<mv_args> run;
-            for (size_t k = i; k < e; k++) run.push_back(p->steps[k].mv);
-            size_t k = 0;
-            while (k < run.size()) {
-                int len = k_chain_accept(run.data() + k, (int) (run.size() - k), c->usable_cus, !(c->flags & 1024));
-                if (len > 0 && !spin_kernels_allowed(c)) len = 0;
-                if (len <= 0) {
-                    merged.push_back(std::move(p->steps[i + k])); k++; continue;
-                }
-                void * ws = em.ws(k_chain_ws_size(run.data() + k, len, c->usable_cus, !(c->flags & 1024)));
-                chain_plan * ch = k_chain_create(c->stream, run.data() + k, len, ws, c->err_dev, c->usable_cus, !(c->flags & 1024));
-                p->chains.push_back(ch);
-                if (k_chain_is_step_program(ch)) p->n_step_programs++;
-                merged.push_back(pstep([ch](hipStream_t s) { k_chain_launch(s, ch); }));
-                merged.back().chain = ch;
-                p->n_chained += len;
-                if (dump) fprintf(stderr, "plan: %d consecutive mat-vecs -> one chain launch (%.1f MB of weights)\n", len, (double) k_chain_weight_bytes(ch) / 1e6);
-                k += (size_t) len;
+            std::vector<vq_level_args> lv;
+            while (e < p->steps.size() && p->steps[e].vq && lv.size() < 32 && (lv.empty() || ((const void *) p->steps[e].vq->resid == (const void *) lv.back().resid_out && p->steps[e].vq->resid_stride == 4))) {
+                lv.push_back(*p->steps[e].vq); e++;
             }
-            i = e;
+            if (lv.size() >= 2 && k_vq_chain_accept(lv.data(), (int) lv.size(), c->usable_cus) && spin_kernels_allowed(c)) {
+                void * ws = em.ws(k_vq_chain_ws_size((int) lv.size()));
+                vq_chain_plan * vc = k_vq_chain_create(c->stream, lv.data(), (int) lv.size(), ws, c->err_dev);
+                p->vq_chains.push_back(vc);
+                p->n_vq_chained += (int) lv.size();
+                merged.push_back(pstep([vc](hipStream_t s) { k_vq_chain_launch(s, vc); }));
+                if (dump) fprintf(stderr, "plan: %zu consecutive RVQ levels -> one launch\n", lv.size());
+                i = e;
+                continue;
+            }
+            merged.push_back(std::move(p->steps[i])); i++; continue;
         }
-        p->steps.swap(merged);
+        if (!p->steps[i].is_mv) { merged.push_back(std::move(p->steps[i])); i++; continue; }
+        size_t e = i;
+        while (e < p->steps.size() && p->steps[e].is_mv) e++;
+        std::vector<mv_args> run;
+        for (size_t k = i; k < e; k++) run.push_back(p->steps[k].mv);
+        size_t k = 0;
+        while (k < run.size()) {
+            int len = k_chain_accept(run.data() + k, (int) (run.size() - k), c->usable_cus, !(c->flags & 1024));
+            if (len > 0 && !spin_kernels_allowed(c)) len = 0;
+            if (len <= 0) {
+                merged.push_back(std::move(p->steps[i + k])); k++; continue;
+            }
+            void * ws = em.ws(k_chain_ws_size(run.data() + k, len, c->usable_cus, !(c->flags & 1024)));
+            chain_plan * ch = k_chain_create(c->stream, run.data() + k, len, ws, c->err_dev, c->usable_cus, !(c->flags & 1024));
+            p->chains.push_back(ch);
+            if (k_chain_is_step_program(ch)) p->n_step_programs++;
+            merged.push_back(pstep([ch](hipStream_t s) { k_chain_launch(s, ch); }));
+            merged.back().chain = ch;
+            p->n_chained += len;
+            if (dump) fprintf(stderr, "plan: %d consecutive mat-vecs -> one chain launch (%.1f MB of weights)\n", len, (double) k_chain_weight_bytes(ch) / 1e6);
+            k += (size_t) len;
+        }
+        i = e;
     }
-    return p;
+    p->steps.swap(merged);
+}
+
+// THE PASS ORDER. A node belongs to the first group that claims it, so the order of this list is part of what a plan is. The reasons on record:
+//   pass_heads_streams     before the generic mat-vecs, which would take the heads' mul_mats one by one; first of all, which its claim relies on
+//   pass_attention         attention blocks first: they swallow set_rows / soft_max / two mul_mats. Collected before the mat-vec pass and emitted after
+//                          it, because that pass may absorb a short-ring attention into the projection that consumes it, or run a long-ring one as
+//                          the tail of its in_proj
+//   pass_scalar_gathers    bottom-up over the node list: the top-most node first, so it claims the whole tree
+//   pass_samplers          bottom-up as well: matched at the sampler's last node
+//   pass_sampler_streams   the B-column form of the same samplers, same direction
+//   pass_embed_sums        bottom-up (a left-deep sum is matched at its last add); before the row copies
+//   pass_row_copies        one launch for all rows instead of one per row: before pass_cpy_of_cont, whose pattern every single row is
+//   pass_matvecs           after the attention pass (see there); every remaining mul_mat of a supported shape
+//   pass_norm_affine       after the mat-vec pass: only a norm that no mat-vec prologue took
+// (pass_ring_copies, pass_codec_convs, pass_cross_attention, pass_lowrank_embed, pass_cpy_of_cont, pass_timestep_of_add: no reason on record but their place)
+static void (* const fusion_passes[])(planner &) = {
+    pass_heads_streams, pass_ring_copies, pass_attention, pass_codec_convs, pass_scalar_gathers, pass_samplers, pass_sampler_streams, pass_cross_attention,
+    pass_lowrank_embed, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
+};
+
+static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
+    planner pl;
+    pl.c = c; pl.p = new plan_t; pl.g = g;
+    pl.keep = keep; pl.fuse = !(c->flags & 1);
+    pl.em.c = c; pl.em.p = pl.p;
+    pl.p->n_nodes = g->n_nodes;
+    analyse(pl.an, g);
+    collect_plan_buffers(pl.p, g);
+    if (pl.fuse) for (auto pass : fusion_passes) pass(pl);
+    // the attention groups no projection absorbed: the column groups of a slot prefill pass as launch pairs, the others one by one
+    merge_column_attention_blocks(pl);
+    emit_attention_groups(pl);
+    lay_out_steps(pl);
+    if (chains_wanted(pl)) {
+        hoist_rope_tables(pl);   // (so that the codec stacks are one run of mat-vecs)
+        merge_chains(pl);
+    }
+    return pl.p;
 }
 
 static void run_steps(hip_ctx * c, plan_t * p) { for (auto & st : p->steps) st.fn(c->stream); }
@@ -2621,6 +2760,16 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
+// the eleven *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
+    c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
+    c->stats.nodes_in_last_plan = p->n_nodes;
+    c->stats.fused_nodes_in_last_plan = p->n_fused;
+    c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
+    c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
+    c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
+}
+
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
     hip_ctx * c = (hip_ctx *) backend->context;
     ctx_init_lazy(c);
@@ -2639,12 +2788,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
     if (!cacheable) {
         plan_t * p = build_plan(c, g, false);
         run_steps(c, p);
-        c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
-        c->stats.nodes_in_last_plan = p->n_nodes;
-        c->stats.fused_nodes_in_last_plan = p->n_fused;
-        c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
-        c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
-        c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
+        publish_plan_stats(c, p);
         plan_free(c, p);   // workspaces return to the pool; reuse is stream-ordered
         return GGML_STATUS_SUCCESS;
     }
@@ -2680,12 +2824,7 @@ static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cg
     if (time_plan && g->n_nodes > 500)
         fprintf(stderr, "graph %p nodes %d: plan %s %.2f ms, capture %.2f ms, launch %.2f ms (%zu kernels)\n", (void *) g, g->n_nodes, fresh ? "built" : "reused",
                 (tp1 - tp0) / 1e3, (tp2 - tp1) / 1e3, (ggml_time_us() - tp2) / 1e3, p->steps.size());
-    c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
-    c->stats.nodes_in_last_plan = p->n_nodes;
-    c->stats.fused_nodes_in_last_plan = p->n_fused;
-    c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
-    c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
-    c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
+    publish_plan_stats(c, p);
     return GGML_STATUS_SUCCESS;
 }
 

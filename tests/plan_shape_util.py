@@ -1,0 +1,139 @@
+"""The plan counters of every model kind, graph by graph: one two-layer synthetic model per kind, two steps (plus the frames a tts model waits
+before its first Depth step), the counters read after every call that computes graphs, then each cached graph computed once more on its own and
+read again. Shared by tests/test_plan_shape_gpu.py (asserts the counters) and tests/microbench/plan_dump_shapes.py (prints them)."""
+import hot_util as hu
+import sampling_util as sp
+import slot_prefill_util as pu
+import slot_state_util as ss
+import slots_util as sl
+import streams_util as su
+import stt_slots_util as st
+import tts_slots_util as tu
+from ggml_util import Q4_0, Q4_K
+
+L = hu.L
+
+COUNTERS = ("kernels_in_last_plan", "fused_nodes_in_last_plan", "nodes_in_last_plan", "chained_matvecs_in_last_plan", "chain_step_programs_in_last_plan",
+            "vq_levels_chained_in_last_plan", "attn_block_launches_in_last_plan", "attn_block_jobs_in_last_plan", "generic_attention_nodes_in_last_plan",
+            "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan", "attention_folds_planned")
+GRAPHS = ((0, "temporal graph"), (1, "depth graph"))
+RING = 8
+
+
+def counters(model):
+    s = model.stats()
+    return tuple(int(getattr(s, n)) for n in COUNTERS)
+
+
+def cached_graphs(model, out):
+    """each cached LM graph once more on its own (same inputs, same ring slots): its plan is then the last one"""
+    for which, name in GRAPHS:
+        g = L.moshi_hot_graph(model.m, which)
+        if g:
+            assert L.ggml_backend_graph_compute(model.be, g) == 0
+            out.append((name, counters(model)))
+    model.free()
+    return out
+
+
+def moshika(sampled):
+    # moshika's widths with two layers: the in_proj + attention merge and the paired gate need the real widths (tests/test_attn_fold.py)
+    cfg = su.lm_only(hu.hot.moshika(L))
+    cfg.num_layers = 2
+    if sampled:
+        cfg.temp, cfg.temp_text = 0.8, 0.7
+    m = hu.Model("hip", cfg)
+    out = []
+    for k in range(2):
+        m.lm_step([0] * 8)
+        out.append((f"step {k}", counters(m)))
+    return cached_graphs(m, out)
+
+
+def tiny(context=RING):
+    cfg = su.lm_only(hu.hot.tiny(L, linear_type=Q4_K, embed_type=Q4_0, context=context))
+    cfg.update_scale = 1.0 / 256
+    return cfg
+
+
+def lockstep_streams():
+    cfg = tiny()                                           # tests/test_streams_gpu.py
+    s = su.Streams("hip", cfg, 2)
+    out = []
+    for k, fr in enumerate(su.stream_codes(cfg, 2, 2, seed=2)):
+        s.step(fr)
+        out.append((f"step {k}", counters(s)))
+    return cached_graphs(s, out)
+
+
+def slots_prefill_fork():
+    cfg = tiny(context=24)                                 # tests/test_slot_prefill_gpu.py, tests/test_slot_state_gpu.py
+    s = ss.Slots("hip", cfg, 2)
+    codes = pu.live_codes(cfg, 2, seed=81)
+    out = []
+    assert s.open(0) == 0
+    assert s.prefill([(0, pu.history(cfg, 3, seed=60))], 8) == 3
+    out.append(("prefill pass", counters(s)))
+    pu.step_all(s, {0: codes[0]})
+    out.append(("step 0", counters(s)))
+    assert s.fork(0, 1) == 0
+    out.append(("fork", counters(s)))
+    pu.step_all(s, {0: codes[1], 1: codes[1]})
+    out.append(("step 1", counters(s)))
+    return cached_graphs(s, out)
+
+
+def stt_slots():
+    cfg = hu.hot.tiny_stt(L, linear_type=Q4_K, embed_type=Q4_0, context=RING)   # tests/test_stt_slots_gpu.py
+    cfg.update_scale = 1.0 / 256
+    s = st.Slots("hip", cfg, 2)
+    out = []
+    for b in range(2):
+        assert s.open(b) == 0
+    for k, fr in enumerate(sl.slot_codes(cfg, 2, 2, seed=2)):
+        s.step(fr)
+        out.append((f"step {k}", counters(s)))
+    return cached_graphs(s, out)
+
+
+def tts_slots():
+    cfg = tu.tts_cfg(linear_type=Q4_K, embed_type=Q4_0, layers=2, cross_len=5)   # tests/test_tts_slots_gpu.py
+    cfg.context = RING
+    cfg.update_scale = 1.0 / 256
+    s = tu.Slots("hip", cfg, 2)
+    n = 2 + cfg.delay_steps                                # the Depth graph first runs in frame delay_steps
+    out = []
+    for b in range(2):
+        assert s.set_conditions(b, 4 + b) == 0
+        assert s.open(b) == 0
+    streams = [tu.text_stream(cfg, b, n) for b in range(2)]
+    for k in range(n):
+        s.step([streams[b][k] for b in range(2)])
+        out.append((f"step {k}", counters(s)))
+    return cached_graphs(s, out)
+
+
+def wide_slots():
+    cfg = sp.sampled(tiny())                               # tests/test_wide_streams_gpu.py: the 3-tile mat-mul and the raised sampler width
+    cfg.wide_streams = 1
+    B = 33
+    s = sp.Slots("hip", cfg, B)
+    out = []
+    for b in range(B):
+        assert s.open(b) == 0
+        assert s.set_sampling(b, 4000 + 17 * b, 0.6 + 0.1 * (b % 5), 0.5 + 0.1 * (b % 4), 20 if b % 3 else 6, 25 if b % 3 != 1 else 4) == 0
+    for k, fr in enumerate(sl.slot_codes(cfg, B, 2, seed=2)):
+        s.step(fr)
+        out.append((f"step {k}", counters(s)))
+    return cached_graphs(s, out)
+
+
+CASES = {
+    "moshika_greedy": lambda: moshika(False),
+    "moshika_sampled": lambda: moshika(True),
+    "lockstep_streams_b2": lockstep_streams,
+    "slots_b2_prefill_fork": slots_prefill_fork,
+    "stt_slots_b2": stt_slots,
+    "tts_slots_b2": tts_slots,
+    "wide_slots_b33": wide_slots,
+}
