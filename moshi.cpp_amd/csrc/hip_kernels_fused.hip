@@ -364,18 +364,10 @@ __global__ void __launch_bounds__(NW * 64) matvec_q4k_kernel(mv_args a, int rows
         }
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the activation loads ahead of the weight tile in program (= return) order
-#if defined(MV_HEAD_EXP) && MV_HEAD_EXP == 1
-    __builtin_amdgcn_s_barrier();
-#elif defined(MV_HEAD_EXP) && MV_HEAD_EXP == 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 
     u32x4 r[WS == 0 ? NLOAD : 1];
     u32x4 dh[WS == 1 ? MVD_PMAX : 1], dq[WS == 1 ? MVD_PMAX : 1];   // WS = 1: header / nibble chunk of this lane group's super-block, per pass
     int t = wave;
-    constexpr bool first_is_last = false;
-    if (WS == 0 && first_is_last) {
-    } else
     if (WS == 0) {   // unconditional (no branch around a load, see above): chunks past the end re-read the last valid chunk, and a wave without
         // a tile reads chunk 0 in every lane - one 16-byte request instead of a 9 KB tile in the CU's load queue; neither is consumed
         const bool has_tile = t < ntiles;
@@ -528,33 +520,45 @@ __global__ void __launch_bounds__(NW * 64) matvec_q4k_kernel(mv_args a, int rows
             }
         }
     }
-#define MV_LOOP_MORE true
-    for (; WS == 0 && t < ntiles && MV_LOOP_MORE; t += nwaves) {
-        {
+    if (WS == 0) {
+        // a tile goes registers -> the wave's LDS image -> one super-block per lane
+        auto stage_tile = [&]() {
 #pragma unroll
             for (int i = 0; i < NLOAD; i++) ((u32x4 *) stage)[i * 64 + lane] = r[i];
-        }
-        MV_STAMP(4);
-        {
-            const int tn = t + nwaves < ntiles ? t + nwaves : ntiles - 1;
+        };
+        auto dot_tile = [&](int tt) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int bi = tt * 64 + lane;
+            if (bi < nblk) {
+                const char * wb = stage + lane * SB;
+                const xblk * xb = xs + (bi % nb);
+                if (FMT == MVF_Q4K) part[bi] = q4k_q8k_block_dot((const block_q4_K *) wb, xb->q, xb->bsums, xb->d);
+                else if (FMT == MVF_Q80) part[bi] = q80_q80_sb_dot(wb, (const xblk80 *) xb);
+                else part[bi] = q40_q80_sb_dot(wb, (const xblk80 *) xb);
+            }
+            __builtin_amdgcn_wave_barrier();
+        };
+        // steady rounds: the wave's next tile is requested, unconditionally (no branch around a load, see above), between the staging and the dots
+        for (; t + nwaves < ntiles; t += nwaves) {
+            stage_tile();
+            MV_STAMP(4);
+            const int tn = t + nwaves;
 #pragma unroll
             for (int i = 0; i < NLOAD; i++) {
                 const int g = tn * (NLOAD * 64) + i * 64 + lane;
                 r[i] = __builtin_nontemporal_load((tn >= tiles_half ? wsrc_r : wsrc) + (g < nchunks ? g : nchunks - 1));
             }
+            dot_tile(t);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int bi = t * 64 + lane;
-        if (bi < nblk) {
-            const char * wb = stage + lane * SB;
-            const xblk * xb = xs + (bi % nb);
-            if (FMT == MVF_Q4K) part[bi] = q4k_q8k_block_dot((const block_q4_K *) wb, xb->q, xb->bsums, xb->d);
-            else if (FMT == MVF_Q80) part[bi] = q80_q80_sb_dot(wb, (const xblk80 *) xb);
-            else part[bi] = q40_q80_sb_dot(wb, (const xblk80 *) xb);
+        // the wave's last tile: nothing left to request (a clamped re-read of the workgroup's last tile here used to put 9 KB per wave into the
+        // CU's load queue next to the other waves' real tiles, and a wait for it into the epilogue)
+        if (t < ntiles) {
+            stage_tile();
+            MV_STAMP(4);
+            dot_tile(t);
         }
-        __builtin_amdgcn_wave_barrier();
     }
     MV_STAMP(5);
     __syncthreads();
@@ -2000,11 +2004,6 @@ __global__ void __launch_bounds__(FOLD_NW * 64) inproj_attn_kernel(mv_args a, at
         aux[j] = *(const float4 *) (a.alpha + e);
     }
     __builtin_amdgcn_sched_barrier(0);
-#if defined(MV_HEAD_EXP) && MV_HEAD_EXP == 1
-    __builtin_amdgcn_s_barrier();
-#elif defined(MV_HEAD_EXP) && MV_HEAD_EXP == 2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     u32x4 r[NLOAD];
     int t = wave;
     {
@@ -2052,22 +2051,29 @@ __global__ void __launch_bounds__(FOLD_NW * 64) inproj_attn_kernel(mv_args a, at
     __syncthreads();
     FD_STAMP(1);
     // ---- phase 3: tiles registers -> LDS image -> one super-block per lane (next tile requested first)
-    for (; t < ntiles; t += NW) {
+    auto stage_tile = [&]() {
 #pragma unroll
         for (int i = 0; i < NLOAD; i++) ((u32x4 *) stage)[i * 64 + lane] = r[i];
-        {
-            const int tn = t + NW < ntiles ? t + NW : ntiles - 1;
-            const u32x4 * src = tile_src(tn);
-#pragma unroll
-            for (int i = 0; i < NLOAD; i++) r[i] = __builtin_nontemporal_load(src + i * 64 + lane);
-        }
+    };
+    auto dot_tile = [&](int tt) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int bi = t * 64 + lane;
+        const int bi = tt * 64 + lane;
         const xblk * xb = xs + (bi % nb);
         part[bi] = q4k_q8k_block_dot((const block_q4_K *) (stage + lane * SB), xb->q, xb->bsums, xb->d);
         __builtin_amdgcn_wave_barrier();
+    };
+    for (; t + NW < ntiles; t += NW) {
+        stage_tile();
+        const u32x4 * src = tile_src(t + NW);
+#pragma unroll
+        for (int i = 0; i < NLOAD; i++) r[i] = __builtin_nontemporal_load(src + i * 64 + lane);
+        dot_tile(t);
+    }
+    if (t < ntiles) {   // the wave's last tile: no request behind it (matvec_q4k_kernel's peeled tail)
+        stage_tile();
+        dot_tile(t);
     }
     __syncthreads();
     FD_STAMP(2);
