@@ -124,6 +124,9 @@ struct ggml_mi355x_stats {
     int64_t generic_attention_nodes_in_last_plan;   // soft_max / set_rows nodes of the last plan that run as generic launches
     int64_t ring_copy_launches_in_last_plan;    // k_ring_copy launches of the last plan (slot snapshots: every ring copy of a fork, a save or a load in one launch) ...
     int64_t ring_copy_jobs_in_last_plan;        // ... and the cpy nodes (jobs) they hold
+    int64_t attn_row_launches_in_last_plan;     // k_attn_rows launches of the last plan (slot prefill past the ring's end: the ring-ordered rows of one layer of a pass) ...
+    int64_t attn_row_jobs_in_last_plan;         // ... the rows jobs they hold (one per ring column) ...
+    int64_t attn_row_rows_in_last_plan;         // ... and the rows of those jobs
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

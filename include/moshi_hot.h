@@ -163,9 +163,20 @@ GGML_API int moshi_hot_last_heads(moshi_hot_model_t * m, float * out, int64_t n)
 // job may span passes, a pass may hold several jobs - the weights stream once per pass whatever the number of jobs. Nothing outside the jobs' own
 // columns is touched. Returns the number of frames prefilled (0 with no device work for n_jobs == 0 or no frames at all), or -1 with no state changed
 // when the model is not a slots model, n_jobs > B, a slot index is bad, closed or named twice, or a job would pass the ring's end
-// (position + n_frames > context: the T > 1 mask is causal only before the wrap).
+// (position + n_frames > context: the T > 1 mask is causal only before the wrap; moshi_hot_slots_prefill_long below takes such a job).
 GGML_API int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk);
 GGML_API int moshi_hot_slot_prefill(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk);   // one job
+// Slot prefill past the ring's end: arguments, return values and refusals of moshi_hot_slots_prefill / _slot_prefill, except that position + n_frames has
+// no upper bound - a job may cross the ring's end, start at or past `context` (a slot stepped live past the wrap) and go round the ring several times.
+// The contract is the same: afterwards the slot is what a fresh single-stream model is after moshi_hot_prefill over the same frames, which steps single
+// provided frames at and after the wrap - bit for bit on the oracle for every `chunk`. A job's rows before the ring's end run as above (a piece that would
+// cross it stops there and closes its pass); its rows at and past it are RING-ORDERED: inside every layer they run one by one in row order, each writing
+// ring row position % context and attending under the mask row of a live step at its position, while the projections, norms and the FFN stay one call
+// over all rows of the pass. A pass holds at most 16 ring-ordered rows. With no job past the ring's end the passes, graphs and plans are those of
+// moshi_hot_slots_prefill. moshi_hot_slot_hold works between calls as above (past the wrap the frozen step's write lands on the row of position - context,
+// which leaves the window in the frame that writes `position`).
+GGML_API int moshi_hot_slots_prefill_long(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk);
+GGML_API int moshi_hot_slot_prefill_long(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk);   // one job
 // hold != 0: moshi_hot_lm_step_slots steps open slot b as it steps a closed one (fed the initial tokens at its frozen position, nothing of its column
 // advances; only ring row position % context of its own column is written, which the next prefill row or live frame rewrites before a mask row admits
 // it) and reports status -2 with outputs -1 - a long history can be prefilled one pass at a time between the frames of the live slots. hold == 0
@@ -175,7 +186,7 @@ GGML_API int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold);
 // stream position), its sampling setting with the seeded flag, its row of transformer_out and the LIVE rows of its column of every Temporal K and V ring:
 // ring rows 0 .. n - 1 of every head with n = min(position, context) - before the wrap the mask admits no other row, after it all of them. The Depth rings
 // start afresh every frame (the chained Depth graph rewrites every row it reads) and carry nothing between frames: they are not part of a snapshot.
-// A snapshot works at any position, past the ring's end included (where moshi_hot_slots_prefill refuses), costs one copy of those rows instead of a
+// A snapshot works at any position, past the ring's end included (where moshi_hot_slots_prefill refuses and moshi_hot_slots_prefill_long recomputes), costs one copy of those rows instead of a
 // recomputation, and the restored or forked slot continues bit for bit - sampled conversations included, which prefill cannot reproduce. The calls block;
 // no other slot's rings, delay ring, position, hold or sampling state is touched. Each returns -1 and changes nothing on a model that is not a slots
 // model, for a bad index, and where a slot is not in the state the call requires.
@@ -198,7 +209,7 @@ GGML_API int     moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * 
 // demux_second_stream, depformer_low_rank, dep_schedule_len > 0 (dep_context == 0: ring = schedule length) and delay_steps >= 0, applied per column by the
 // column's own frame count: while it is below delay_steps the column is REPLACED (src/moshi.cpp:905, lm.h:910-921: its Depth tokens are -1, nothing is read
 // out; the Depth graph is skipped when every stepping column is replaced), and audio[q] = -1 while it is below delays[q + 1] + delay_steps.
-// moshi_hot_slots_prefill / _slot_prefill and moshi_hot_slot_fork / _save / _load return -1 on this shape and change nothing.
+// moshi_hot_slots_prefill / _slot_prefill (and their _long forms) and moshi_hot_slot_fork / _save / _load return -1 on this shape and change nothing.
 //
 // Column b's conditions (the B > 1 form of moshi_hot_set_conditions, which does nothing on such a model): sum F32[dim] and cross F32[dim * cross_len], either
 // may be NULL to leave that half as it is. cross also runs init() (transformer.h:343-396) for column b of every layer's K / V. The setting belongs to

@@ -59,7 +59,8 @@ class Stats(C.Structure):
                                          "fused_nodes_in_last_plan", "nodes_in_last_plan", "uploads_batched", "chained_matvecs_in_last_plan",
                                          "attention_folds_planned", "chain_step_programs_in_last_plan", "vq_levels_chained_in_last_plan",
                                          "attn_block_launches_in_last_plan", "attn_block_jobs_in_last_plan", "generic_attention_nodes_in_last_plan",
-                                         "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan")]
+                                         "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan",
+                                         "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

@@ -341,7 +341,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -973,19 +973,23 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
         for (int s = 0; s < GGML_MAX_SRC; s++) if (t->src[s]) stack.push_back(t->src[s]);
     }
     if (n_mm != 2 || n_sm != 1 || n_sr != 2) return false;
-    // no interior value may be consumed outside the block (x2 is the block's output)
-    std::unordered_map<int, bool> inside;
-    for (int p : members) inside[p] = true;
-    for (int i = 0; i < an.g->n_nodes; i++) {
-        if (inside.count(i)) continue;
-        const ggml_tensor * c = an.g->nodes[i];
+    // no interior value may be consumed outside the block (x2 is the block's output): every consumer of a member is a member - counted from the
+    // members' side (the analysis holds every tensor's number of consuming nodes), so a graph of many blocks is not walked once per block
+    std::unordered_map<int, int> consumed;   // member position -> consuming nodes inside the block
+    for (int p : members) consumed[p] = 0;
+    for (int p : members) {
+        const ggml_tensor * c = an.g->nodes[p];
         for (int s = 0; s < GGML_MAX_SRC; s++) {
             const ggml_tensor * t = c->src[s];
-            if (!t || t == x2) continue;
-            const int tp = pos_of(an, t);
-            if (tp >= 0 && inside.count(tp)) return false;
+            if (!t || t == c) continue;
+            bool dup = false;
+            for (int s2 = 0; s2 < s; s2++) if (c->src[s2] == t) dup = true;
+            if (dup) continue;
+            auto it = consumed.find(pos_of(an, t));
+            if (it != consumed.end()) it->second++;
         }
     }
+    for (auto & kv : consumed) if (an.g->nodes[kv.first] != x2 && kv.second != uses_of(an, an.g->nodes[kv.first])) return false;
     attn_args & a = grp.a;
     memset(&a, 0, sizeof(a));
     a.q = (const float *) qs.base; a.k = (const float *) ks.base; a.v = (const float *) vs.base;
@@ -2504,6 +2508,95 @@ static void pass_norm_affine(planner & pl) {
 }
 
 // ---- after the fusion passes ----
+// slot prefill past the ring's end: the ring-ordered rows of a pass. Each row is a one-row `column` group; a run of at least two of them, consecutive in
+// emit order, on the SAME ring column, of one shape, whose q / k / v / out / mask / rot / index bases advance by constant strides, with nothing but
+// layout nodes and their own members between their outputs, is a ROWS JOB: the rows must run in order (row t + 1 attends over the ring row that row t
+// wrote). The rows jobs of one layer of one pass (consecutive, different columns, same shape) become ONE k_attn_rows launch - at most ATTN_ROWS_MAX
+// jobs per launch, further launches beyond - emitted where the last member stood. THE CLAIM: the groups were claimed by pass_attention; a group this
+// pass takes leaves the list of groups to emit (emit_pos = -1) and belongs to one rows job only. A run that cannot be proven regular is declined: it
+// stays with merge_column_attention_blocks, which never puts two groups of one ring column into a launch pair - a declined row shares a pair only with
+// groups of other columns and the pairs run in node order: correct, only slower. A lone one-row group is a block of one row and stays with the block launches. Runs before merge_column_attention_blocks.
+static bool no_attn_rows() { static const bool off = getenv("MI355X_NO_ATTN_ROWS") != nullptr; return off; }
+static void pass_column_attention_rows(planner & pl) {
+    if (no_attn_rows()) return;
+    std::vector<attn_group> & groups = pl.attn_groups;
+    std::vector<size_t> order;   // the column groups in emit order (the order their outputs stand in the graph)
+    for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return groups[x].emit_pos < groups[y].emit_pos; });
+    auto same_shape = [](const attn_args & a, const attn_args & b) {
+        return b.T == 1 && b.H == a.H && b.D == a.D && b.C == a.C && b.scale == a.scale && b.out_ts == a.out_ts && (b.rot != nullptr) == (a.rot != nullptr) &&
+               b.q_hs == a.q_hs && b.k_hs == a.k_hs && b.v_hs == a.v_hs && b.k_nb1 == a.k_nb1 && b.k_nb2 == a.k_nb2 && b.v_nb1 == a.v_nb1 && b.v_nb2 == a.v_nb2;
+    };
+    // only layout nodes and members of `inside` between two emit positions
+    auto clean_between = [&](int lo, int hi, const std::set<int> & inside) {
+        for (int i = lo + 1; i < hi; i++) if (!is_view_op(pl.g->nodes[i]->op) && !inside.count(i)) return false;
+        return true;
+    };
+    auto stride = [](const void * a, const void * b) { return (int64_t) ((const char *) b - (const char *) a); };
+    attn_rows_args ra;
+    int launch_hi = -1;           // emit position of the launch being filled (ra.n_jobs > 0)
+    std::set<int> rows_inside;    // the members of the rows jobs of that launch
+    auto flush = [&]() {
+        if (!ra.n_jobs) return;
+        const attn_rows_args la = ra;
+        unsigned * err = pl.c->err_dev;
+        auto & at = pl.at_pos[launch_hi];
+        at.insert(at.begin(), [=](hipStream_t s) { k_attn_rows(s, la, err); });
+        pl.p->n_attn_row_launches++; pl.p->n_attn_row_jobs += la.n_jobs;
+        for (int j = 0; j < la.n_jobs; j++) pl.p->n_attn_row_rows += la.job[j].n;
+        ra.n_jobs = 0;
+    };
+    memset(&ra, 0, sizeof(ra));
+    for (size_t oi = 0; oi < order.size(); ) {
+        const attn_group & g0 = groups[order[oi]];
+        const attn_args & a0 = g0.a;
+        size_t oe = oi + 1;
+        std::set<int> inside(g0.members.begin(), g0.members.end());
+        int hi = g0.emit_pos;
+        attn_rows_job jb;
+        memset(&jb, 0, sizeof(jb));
+        if (a0.T == 1) {
+            while (oe < order.size() && oe - oi < 64) {
+                const attn_group & gn = groups[order[oe]];
+                const attn_args & b = gn.a, & prev = groups[order[oe - 1]].a;
+                if (!same_shape(a0, b) || b.kcache != a0.kcache || b.vcache != a0.vcache) break;
+                const int64_t d[7] = { stride(prev.q, b.q), stride(prev.k, b.k), stride(prev.v, b.v), stride(prev.mask, b.mask), b.rot ? stride(prev.rot, b.rot) : 0,
+                                       stride(prev.index, b.index), stride(prev.out, b.out) };
+                if (oe == oi + 1) { jb.q_rs = d[0]; jb.k_rs = d[1]; jb.v_rs = d[2]; jb.mask_rs = d[3]; jb.rot_rs = d[4]; jb.index_rs = d[5]; jb.out_rs = d[6]; }
+                else if (d[0] != jb.q_rs || d[1] != jb.k_rs || d[2] != jb.v_rs || d[3] != jb.mask_rs || d[4] != jb.rot_rs || d[5] != jb.index_rs || d[6] != jb.out_rs) break;
+                if (d[0] % 4 || d[1] % 4 || d[2] % 4 || d[3] % 4 || d[4] % 4 || d[5] % 4 || d[6] % 4) break;
+                std::set<int> both = inside;
+                both.insert(gn.members.begin(), gn.members.end());
+                if (!clean_between(hi, gn.emit_pos, both)) break;
+                inside.swap(both); hi = gn.emit_pos;
+                oe++;
+            }
+        }
+        const int n = (int) (oe - oi);
+        if (n < 2) { flush(); oi = oe; continue; }   // a block-form job (or a lone row): not this pass's; it also ends the layer's run of rows jobs
+        // a further rows job of the same launch: same shape, another column, nothing foreign between the launch so far and this job
+        if (ra.n_jobs) {
+            bool joins = ra.n_jobs < ATTN_ROWS_MAX && same_shape(ra.a, a0);
+            for (int j = 0; j < ra.n_jobs && joins; j++) joins = ra.job[j].kcache != a0.kcache && ra.job[j].vcache != a0.vcache;
+            if (joins) {
+                std::set<int> both = inside;
+                both.insert(rows_inside.begin(), rows_inside.end());
+                joins = clean_between(launch_hi, g0.emit_pos, both);
+            }
+            if (!joins) flush();
+        }
+        if (!ra.n_jobs) { ra.a = a0; rows_inside.clear(); }
+        jb.q = (const char *) a0.q; jb.k = (const char *) a0.k; jb.v = (const char *) a0.v; jb.kcache = a0.kcache; jb.vcache = a0.vcache;
+        jb.mask = (const char *) a0.mask; jb.rot = (const char *) a0.rot; jb.index = (const char *) a0.index; jb.out = (char *) a0.out; jb.n = n;
+        ra.job[ra.n_jobs++] = jb;
+        rows_inside.insert(inside.begin(), inside.end());
+        launch_hi = hi;
+        for (size_t k = oi; k < oe; k++) groups[order[k]].emit_pos = -1;
+        oi = oe;
+    }
+    flush();
+}
+
 // slot prefill: the column groups of one layer of one pass (consecutive groups of one shape with nothing but layout nodes and their own members
 // between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase
 static void merge_column_attention_blocks(planner & pl) {
@@ -2521,7 +2614,12 @@ static void merge_column_attention_blocks(planner & pl) {
             const attn_args & b = n.a;
             if (!n.column || n.emit_pos < 0 || b.H != a0.H || b.D != a0.D || b.C != a0.C || b.scale != a0.scale || b.out_ts != a0.out_ts || (b.rot != nullptr) != (a0.rot != nullptr) ||
                 (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts)) || b.q_hs != a0.q_hs || b.k_hs != a0.k_hs || b.v_hs != a0.v_hs ||
-                b.k_nb1 != a0.k_nb1 || b.k_nb2 != a0.k_nb2 || b.v_nb1 != a0.v_nb1 || b.v_nb2 != a0.v_nb2 || b.kcache == a0.kcache) break;
+                b.k_nb1 != a0.k_nb1 || b.k_nb2 != a0.k_nb2 || b.v_nb1 != a0.v_nb1 || b.v_nb2 != a0.v_nb2) break;
+            // a launch pair never holds two groups of one ring column: it writes every job's rows before any job attends, so a second group of a column
+            // (a ring-ordered row after its predecessor, where pass_column_attention_rows is off or has declined the run) must start a launch of its own
+            bool column_taken = false;
+            for (size_t k = gi; k < ge && !column_taken; k++) column_taken = attn_groups[k].a.kcache == b.kcache || attn_groups[k].a.vcache == b.vcache;
+            if (column_taken) break;
             std::set<int> both = inside;
             both.insert(n.members.begin(), n.members.end());
             const int nlo = n.emit_pos < lo ? n.emit_pos : lo, nhi = n.emit_pos > hi ? n.emit_pos : hi;
@@ -2710,7 +2808,9 @@ static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
     analyse(pl.an, g);
     collect_plan_buffers(pl.p, g);
     if (pl.fuse) for (auto pass : fusion_passes) pass(pl);
-    // the attention groups no projection absorbed: the column groups of a slot prefill pass as launch pairs, the others one by one
+    // the attention groups no projection absorbed: the ring-ordered rows of a slot prefill pass as rows launches, its other column groups as launch
+    // pairs, the rest one by one
+    pass_column_attention_rows(pl);
     merge_column_attention_blocks(pl);
     emit_attention_groups(pl);
     lay_out_steps(pl);
@@ -2760,7 +2860,7 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
-// the eleven *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+// the fourteen *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
 static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
     c->stats.nodes_in_last_plan = p->n_nodes;
@@ -2768,6 +2868,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.chained_matvecs_in_last_plan = p->n_chained; c->stats.chain_step_programs_in_last_plan = p->n_step_programs; c->stats.vq_levels_chained_in_last_plan = p->n_vq_chained;
     c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
     c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
+    c->stats.attn_row_launches_in_last_plan = p->n_attn_row_launches; c->stats.attn_row_jobs_in_last_plan = p->n_attn_row_jobs; c->stats.attn_row_rows_in_last_plan = p->n_attn_row_rows;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

@@ -212,6 +212,16 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err =
 struct attn_block_job { const float * q, * k, * v; char * kcache, * vcache; const float * mask, * rot; const int32_t * index; float * out; int T; };
 struct attn_blocks_args { attn_args a; int n_jobs, write_only; attn_block_job job[ATTN_BLOCKS_MAX]; };
 void k_attn_blocks(hipStream_t s, const attn_blocks_args & a, unsigned * err = nullptr);
+// Slot prefill past the ring's end (moshi_hot_slots_prefill_long): the RING-ORDERED rows of one layer of one pass. Job j = n_j consecutive one-row
+// attention sequences on ONE ring column: row t has its own q / k / v row, mask row, RoPE row, ring slot and output row, each at the job's base plus t
+// times a byte stride. Workgroup (h, j) walks job j's rows in order and runs attn_decode_body on each with T = 1 - write the row's K / V at its ring slot,
+// then attend: what k_attn_streams does for a live step of that slot, so the operations and their order per row are those of stepping the frames one
+// by one, across the wrap included. One launch; no workgroup waits for another. `a` holds what the rows share (head strides, ring strides, H / D / C, scale).
+#define ATTN_ROWS_MAX 16
+struct attn_rows_job { const char * q, * k, * v; char * kcache, * vcache; const char * mask, * rot, * index; char * out;
+                       int64_t q_rs, k_rs, v_rs, mask_rs, rot_rs, index_rs, out_rs; int n; };   // *_rs: bytes from one row to the next
+struct attn_rows_args { attn_args a; int n_jobs; attn_rows_job job[ATTN_ROWS_MAX]; };
+void k_attn_rows(hipStream_t s, const attn_rows_args & a, unsigned * err = nullptr);
 // rows consecutive rows of n floats, row r copied from its own source src[r] (stream slots: the B mask rows, each a window of the bias table at the
 // slot's own column, transformer.h:1259-1289) - one launch instead of one per row
 #define COPY_ROWS_MAX 64   // (64 pointers by value: 512 bytes of kernel arguments)

@@ -1866,6 +1866,67 @@ void k_attn_blocks(hipStream_t s, const attn_blocks_args & ba, unsigned * err) {
     else      attn_blocks_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(ba, w);
 }
 
+// Slot prefill past the ring's end: workgroup (h, j) walks the rows of job j in order and runs attn_decode_body on each as a one-row block - the call
+// attn_streams_kernel makes for a live step: the row's K / V go to its ring slot, then the row attends over the ring under its own mask row. The body is
+// the shared one, so a row is computed exactly as a live slots step computes it, across the wrap included.
+// BETWEEN ROWS. Row t + 1 reads from memory the ring row that other waves of this workgroup stored for row t, and it reuses the body's LDS. After each
+// row: every wave drains its stores and issues a workgroup-scope release, the workgroup barrier, then a workgroup-scope acquire. That is enough because
+// producer and consumer are ONE workgroup: its waves sit on one compute unit and share that unit's vector L1, which is what workgroup scope covers; one
+// (head, ring column) pair is touched by exactly one workgroup of the launch (the planner puts a column into one job, the grid gives a head one
+// workgroup per job), so nothing here is another compute unit's data and no agent-scope fence is needed. No workgroup waits for another - there is no
+// flag, counter or spin in this kernel - so residency does not matter and a hang is impossible by construction. The ring rows are read with per-lane
+// addresses off the by-value job table (vector loads; nothing on that path is const __restrict__ data the compiler could route through the scalar cache).
+template <int NWA>
+__global__ void __launch_bounds__(NWA * 64) __attribute__((amdgpu_waves_per_eu(2)))
+attn_rows_kernel(attn_rows_args ra, attn_split_ws w) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = ra.job[blockIdx.y].n;
+    for (int t = 0; t < n; t++) {
+        // the job's table entry is read from the kernel arguments again in every row (scalar loads, uniform over the workgroup): held across the body
+        // its sixteen bases and strides cost more scalar registers than the body leaves, and the spills reach scratch
+        int j = (int) blockIdx.y;
+        asm volatile("" : "+s"(j));
+        const attn_rows_job & jb = ra.job[j];
+        attn_args a = ra.a;
+        a.q = (const float *) (jb.q + t * jb.q_rs); a.k = (const float *) (jb.k + t * jb.k_rs); a.v = (const float *) (jb.v + t * jb.v_rs);
+        a.kcache = jb.kcache; a.vcache = jb.vcache;
+        a.mask = (const float *) (jb.mask + t * jb.mask_rs);
+        a.rot = jb.rot ? (const float *) (jb.rot + t * jb.rot_rs) : nullptr;
+        a.index = (const int32_t *) (jb.index + t * jb.index_rs);
+        a.out = (float *) (jb.out + t * jb.out_rs);
+        a.T = 1; a.n_groups = 0; a.write_only = 0; a.row_split = 0;
+        attn_decode_body<false, NWA, AT_PLAIN>(a, w, smem, (int) blockIdx.x, 0, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the row's ring stores have left this wave, whatever the fence's own wait becomes)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+void k_attn_rows(hipStream_t s, const attn_rows_args & ra, unsigned * err) {
+    const attn_args & a = ra.a;
+    GGML_ASSERT(ra.n_jobs >= 1 && ra.n_jobs <= ATTN_ROWS_MAX);
+    GGML_ASSERT(a.D % 8 == 0 && 64 % (a.D / 8) == 0 && a.D <= 2 * ATTN_NW_BASE * 64);
+    for (int j = 0; j < ra.n_jobs; j++) GGML_ASSERT(ra.job[j].n >= 1 && ra.job[j].n <= 64);
+    static const int wide_on = env_int("MI355X_ATTN_WIDE", 1);
+    const bool wide = wide_on && a.D <= 64 && a.C >= 128;   // (attn_streams_kernel's choice for the same head)
+    attn_args sized = a; sized.T = 1; sized.n_groups = 0;
+    const size_t smem = attn_smem_bytes(sized, false, wide);
+    GGML_ASSERT(smem <= 160 * 1024);
+    if (smem > 64 * 1024) {
+        static size_t granted[2] = { 0, 0 };
+        if (granted[wide] < smem) {
+            HIP_CHECK(hipFuncSetAttribute(wide ? (const void *) attn_rows_kernel<ATTN_NW_WIDE> : (const void *) attn_rows_kernel<ATTN_NW_BASE>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int) smem));
+            granted[wide] = smem;
+        }
+    }
+    static const int single_max = env_int("MI355X_ATTN_SINGLE_MAX", ATTN_SINGLE_MAX), big_min = env_int("MI355X_ATTN_BIG_MIN", ATTN_SPLIT_BIG_MIN);
+    const attn_split_ws w = { nullptr, nullptr, nullptr, 1, err, ATTN_SPLIT_SLOTS, single_max, big_min };
+    const dim3 grid((unsigned) a.H, (unsigned) ra.n_jobs);
+    if (wide) attn_rows_kernel<ATTN_NW_WIDE><<<grid, ATTN_NW_WIDE * 64, smem, s>>>(ra, w);
+    else      attn_rows_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(ra, w);
+}
+
 // row r of the destination <- src[r]: workgroup (x, r) copies 256 floats of row r (the row pointer is uniform: a kernel-argument load)
 __global__ void __launch_bounds__(256) copy_rows_kernel(copy_rows_args a) {
     const int r = (int) blockIdx.y;

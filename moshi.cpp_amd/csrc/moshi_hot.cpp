@@ -63,6 +63,7 @@ struct Builder {
     ggml_backend_t be;
     struct ggml_context * ctx;
     struct ggml_cgraph * gf = nullptr;
+    size_t graph_size = GGML_DEFAULT_GRAPH_SIZE * 4;   // nodes (and leafs) a graph of this builder may hold
     ggml_backend_buffer_t buf = nullptr;
     struct upload { T t; std::vector<uint8_t> data; };
     std::vector<upload> consts;
@@ -95,7 +96,7 @@ struct Builder {
     void set_later(T t, const void * data, size_t n) { consts.push_back({ t, std::vector<uint8_t>((const uint8_t *) data, (const uint8_t *) data + n) }); }
 
     void expand(T t) {
-        if (!gf) gf = ggml_new_graph_custom(ctx, GGML_DEFAULT_GRAPH_SIZE * 4, false);
+        if (!gf) gf = ggml_new_graph_custom(ctx, graph_size, false);
         ggml_build_forward_expand(gf, t);
     }
     void alloc() {
@@ -808,7 +809,7 @@ struct moshi_hot_model {
     Weights * W = nullptr;
     // persistent state (StateContext, src/context.h:656-780)
     struct ggml_context * st_ctx = nullptr; ggml_backend_buffer_t st_buf = nullptr;
-    Builder * scratch = nullptr, * scratch_codec = nullptr;
+    Builder * scratch = nullptr, * scratch_codec = nullptr, * scratch_rows = nullptr;   // scratch_rows: slot prefill passes with ring-ordered rows
 
     // LM
     Transformer temporal, depth;
@@ -1560,7 +1561,7 @@ extern "C" void moshi_hot_free(moshi_hot_model_t * m) {
     for (auto & f : m->inflight) if (f.ev) ggml_backend_event_free(f.ev);
     for (auto e : m->ev_pool) ggml_backend_event_free(e);
     if (m->own_codec_be) ggml_backend_synchronize(m->be_codec);
-    delete m->g_temporal; delete m->g_depth; delete m->g_dec; delete m->g_enc; if (m->scratch_codec != m->scratch) delete m->scratch_codec; delete m->scratch; delete m->g_shard_begin;
+    delete m->g_temporal; delete m->g_depth; delete m->g_dec; delete m->g_enc; if (m->scratch_codec != m->scratch) delete m->scratch_codec; delete m->scratch; delete m->scratch_rows; delete m->g_shard_begin;
     for (auto * b : m->g_shard_step) delete b;
     for (auto * b : m->g_shard_import) delete b;
     for (auto * b : m->g_tp) delete b;
@@ -2467,8 +2468,14 @@ extern "C" void moshi_hot_prefill(moshi_hot_model_t * m, const int32_t * tokens,
 
 // ---- slot prefill (moshi_hot.h): provided frames of one or several slots as batched [dim, T] passes ------------------------------------------------
 namespace {
-// rows [row, row + n) of a pass belong to slot b, whose stream position before the pass is pos
-struct PassJob { int b, row, n; int64_t pos; T mask = nullptr, indices = nullptr; Rot rot; };
+// rows [row, row + n) of a pass belong to slot b, whose stream position before the pass is pos. A piece with pos + n <= context is in BLOCK form: one
+// attention sequence of n rows (causal mask block, the write-all-then-attend order of a [dim, T] pass). A piece past the ring's end is RING-ORDERED
+// (ordered): in every layer its rows run as n consecutive one-row sequences in row order - the order of stepping the frames one by one, which is
+// what the single-stream moshi_hot_prefill does there.
+struct PassJob { int b, row, n; int64_t pos; bool ordered = false, in_order = false; T mask = nullptr, indices = nullptr; Rot rot; };   // in_order: see attention_jobs
+// rows of ring-ordered pieces a pass may hold (R): a one-row sequence is ~53 graph nodes per layer, so 16 rows x 32 layers of moshika are a graph of
+// 28 279 nodes to build per pass and to plan once per pass shape (DESIGN.md section 21 has the times)
+constexpr int RING_ORDERED_ROWS_MAX = 16;
 
 // moshi_streaming_multihead_attention (attention() above) over the rows of a pass: ONE in_proj and ONE out_proj for all rows; between them job j's rows
 // of q / k / v run the single-stream op sequence against column b_j of the [D, C, H, B] rings (a [D, C, H] view), with the job's own ring slots, mask
@@ -2498,6 +2505,10 @@ T attention_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std:
         T dst = ggml_view_3d(c, out, D, H, j.n, (size_t) D * 4, out_row, (size_t) ((int64_t) (j.row - out_at) * (int64_t) out_row));
         out = ggml_cpy(c, ggml_permute(c, o, 0, 2, 1, 3), dst);
         out_at = j.row;
+        // a pass with ring-ordered rows: every sequence enters the graph before the next one is built. The set_rows of a row then precede the next
+        // row's mul_mat in node order - the sequences share no tensor that would order them otherwise - so an old ring row is read by exactly the
+        // rows that should still see it, and the node order is the order of stepping the frames one by one.
+        if (j.in_order) c.expand(out);
     }
     T all = ggml_view_3d(c, out, D * H, Tn, 1, out_row, out_row * (size_t) Tn, (size_t) (-(int64_t) out_at * (int64_t) out_row));
     return linear(c, L.out_proj[0], all);
@@ -2513,25 +2524,46 @@ T transformer_layer_jobs(Builder & c, const Transformer & tr, Layer & L, T x, co
     return ggml_add(c, x, update);
 }
 
+// the scratch builder of passes that hold ring-ordered rows: room for RING_ORDERED_ROWS_MAX one-row sequences in every layer (host memory only; the
+// ordinary scratch context and its graphs stay as they are for everything else)
+Builder & ring_ordered_scratch(moshi_hot_model * m) {
+    if (!m->scratch_rows) {
+        m->scratch_rows = new Builder(m->be, 96);
+        m->scratch_rows->graph_size = GGML_DEFAULT_GRAPH_SIZE * 16;
+    }
+    return *m->scratch_rows;
+}
 // one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
 void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames) {
     const int C = m->temporal.capacity;
     int Tn = 0;
-    for (const PassJob & j : jobs) Tn += j.n;
+    bool any_ordered = false;
+    for (const PassJob & j : jobs) { Tn += j.n; any_ordered = any_ordered || j.ordered; }
     PassInputs in(m->cfg.n_q + 1, Tn);
     for (size_t ji = 0; ji < jobs.size(); ji++) provided_frames(m->cols[(size_t) jobs[ji].b].ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
     PhaseTimer pt(m, 1);
-    Builder & s = *m->scratch;
+    Builder & s = any_ordered ? ring_ordered_scratch(m) : *m->scratch;
     T input = embedding_sum_rows(m, s, in, Tn);
-    for (PassJob & j : jobs) {   // the job's mask block (causal from its position: no job passes the ring's end), ring slots and RoPE rows
+    // the attention sequences of the pass: a block piece is one (causal from its position: it ends at or before the ring's end); a ring-ordered piece is
+    // one per row - the job of one row at position p: ring slot p % C, the RoPE row of offset p and the mask row of a live step at p (slot cc is open
+    // iff cc <= p, the whole ring from p = C - 1 on; bias_pattern_index(T = 1, p)). All uploaded constants: passes of one shape reuse one plan.
+    std::vector<PassJob> seqs;
+    for (const PassJob & j : jobs) {
+        if (!j.ordered) { seqs.push_back(j); continue; }
+        for (int t = 0; t < j.n; t++) { PassJob r = j; r.row = j.row + t; r.n = 1; r.pos = j.pos + t; seqs.push_back(r); }
+    }
+    for (PassJob & j : seqs) {
         std::vector<int32_t> idx((size_t) j.n);
         for (int t = 0; t < j.n; t++) idx[(size_t) t] = (int32_t) ((j.pos + t) % C);
         j.mask = causal_mask_block(s, C, j.pos, j.n);
         j.indices = s.i32s(idx);
         if (m->temporal.max_period) j.rot = timestep_embedding(s, j.n, m->temporal.dim / m->temporal.heads, s.f32((float) j.pos), m->temporal.max_period);
+        // (a pass with ring-ordered rows: the RoPE tables ahead of layer 0 rather than between its sequences - every layer then has the same node pattern)
+        j.in_order = any_ordered;
+        if (any_ordered && j.rot.rotr) s.expand(j.rot.rotr);
     }
     T x = input;
-    for (auto & L : m->temporal.layers) x = transformer_layer_jobs(s, m->temporal, L, x, jobs);
+    for (auto & L : m->temporal.layers) x = transformer_layer_jobs(s, m->temporal, L, x, seqs);
     for (const PassJob & j : jobs) {   // the slot's row of transformer_out as the last of its frames leaves it (lm.h:434, 847-849)
         T last = ggml_view_2d(s, x, x->ne[0], 1, x->nb[1], (size_t) (j.row + j.n - 1) * x->nb[1]);
         T dst = ggml_view_1d(s, m->transformer_out, x->ne[0], (size_t) j.b * m->transformer_out->nb[2]);
@@ -2540,15 +2572,19 @@ void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
     }
     s.compute_scratch();
 }
-}  // namespace
 
-extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
+// moshi_hot_slots_prefill (past_end == false: a job that would pass the ring's end is refused) and moshi_hot_slots_prefill_long (true). The cutter:
+// pieces in job order, a pass of at most `chunk` rows; a piece that would cross the ring's end stops there (everything before the wrap stays in block
+// form) and closes its pass, so that no pass holds two pieces of one slot; a piece at or past the ring's end is ring-ordered, and a pass holds at most
+// RING_ORDERED_ROWS_MAX such rows. With no job past the ring's end none of the three rules ever applies: the passes are those of the refusing call.
+int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end) {
     if (m->kind != ModelKind::slots || tts_shape(m) || n_jobs < 0 || n_jobs > m->n_streams) return -1;
     const int ncb = m->cfg.n_q + 1;
+    const int64_t C = m->temporal.capacity;
     int total = 0;
     for (int j = 0; j < n_jobs; j++) {
         const moshi_hot_model::Column * s = slot(m, slots[j]);
-        if (!s || !s->open || n_frames[j] < 0 || (n_frames[j] > 0 && !tokens[j]) || s->pos + n_frames[j] > m->temporal.capacity) return -1;
+        if (!s || !s->open || n_frames[j] < 0 || (n_frames[j] > 0 && !tokens[j]) || (!past_end && s->pos + n_frames[j] > C)) return -1;
         for (int i = 0; i < j; i++) if (slots[i] == slots[j]) return -1;
         total += n_frames[j];
     }
@@ -2557,18 +2593,23 @@ extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const 
     ggml_backend_mi355x_set_capture(m->be, 0);   // same-shaped pass graphs reuse one plan; none is replayed often enough to pay for a hipGraph capture
     std::vector<PassJob> jobs;
     std::vector<const int32_t *> frames;
-    int rows = 0;
+    int rows = 0, ordered_rows = 0;
     for (int j = 0; j < n_jobs; j++) {
         int done = 0;
         while (done < n_frames[j]) {
-            const int Tj = n_frames[j] - done < chunk - rows ? n_frames[j] - done : chunk - rows;
-            PassJob pj; pj.b = slots[j]; pj.row = rows; pj.n = Tj; pj.pos = m->cols[(size_t) slots[j]].pos;
+            int Tj = n_frames[j] - done < chunk - rows ? n_frames[j] - done : chunk - rows;
+            PassJob pj; pj.b = slots[j]; pj.row = rows; pj.pos = m->cols[(size_t) slots[j]].pos;
+            pj.ordered = pj.pos >= C;
+            if (pj.ordered) { if (Tj > RING_ORDERED_ROWS_MAX - ordered_rows) Tj = RING_ORDERED_ROWS_MAX - ordered_rows; ordered_rows += Tj; }
+            else if (pj.pos + Tj > C) Tj = (int) (C - pj.pos);
+            pj.n = Tj;
             jobs.push_back(pj);
             frames.push_back(tokens[j] + (size_t) done * ncb);
             rows += Tj; done += Tj;
-            if (rows == chunk || (j == n_jobs - 1 && done == n_frames[j])) {
+            const bool at_ring_end = !pj.ordered && pj.pos + Tj == C && done < n_frames[j];   // the job goes on ring-ordered: in a pass of its own
+            if (rows == chunk || ordered_rows == RING_ORDERED_ROWS_MAX || at_ring_end || (j == n_jobs - 1 && done == n_frames[j])) {
                 slots_prefill_pass(m, jobs, frames);
-                jobs.clear(); frames.clear(); rows = 0;
+                jobs.clear(); frames.clear(); rows = 0; ordered_rows = 0;
             }
         }
     }
@@ -2576,9 +2617,21 @@ extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const 
     ggml_backend_mi355x_set_capture(m->be, 1);
     return total;
 }
+}  // namespace
+
+extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
+    return slots_prefill(m, n_jobs, slots, tokens, n_frames, chunk, false);
+}
 extern "C" int moshi_hot_slot_prefill(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk) {
     const int32_t sb = b;
     return moshi_hot_slots_prefill(m, 1, &sb, &tokens, &n_frames, chunk);
+}
+extern "C" int moshi_hot_slots_prefill_long(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
+    return slots_prefill(m, n_jobs, slots, tokens, n_frames, chunk, true);
+}
+extern "C" int moshi_hot_slot_prefill_long(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk) {
+    const int32_t sb = b;
+    return moshi_hot_slots_prefill_long(m, 1, &sb, &tokens, &n_frames, chunk);
 }
 extern "C" int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold) {
     moshi_hot_model::Column * s = slot(m, b);

@@ -88,6 +88,8 @@ SIGNATURES = {
     "moshi_hot_lm_step_slots_text": (C.c_int, [P, P, P, P, P, P]),
     "moshi_hot_slots_prefill": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "moshi_hot_slot_prefill": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
+    "moshi_hot_slots_prefill_long": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
+    "moshi_hot_slot_prefill_long": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
     "moshi_hot_slot_hold": (C.c_int, [P, C.c_int, C.c_int]),
     "moshi_hot_slot_fork": (C.c_int, [P, C.c_int, C.c_int]),
     "moshi_hot_slot_save": (C.c_int64, [P, C.c_int, P, C.c_int64]),
