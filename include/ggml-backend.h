@@ -127,6 +127,8 @@ struct ggml_mi355x_stats {
     int64_t attn_row_launches_in_last_plan;     // k_attn_rows launches of the last plan (slot prefill past the ring's end: the ring-ordered rows of one layer of a pass) ...
     int64_t attn_row_jobs_in_last_plan;         // ... the rows jobs they hold (one per ring column) ...
     int64_t attn_row_rows_in_last_plan;         // ... and the rows of those jobs
+    int64_t cross_block_launches_in_last_plan;  // k_cross_attn_blocks launches of the last plan (tts replay: the cross-attention of one layer of a pass) ...
+    int64_t cross_block_jobs_in_last_plan;      // ... and the jobs they hold
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

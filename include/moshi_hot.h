@@ -209,7 +209,8 @@ GGML_API int     moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * 
 // demux_second_stream, depformer_low_rank, dep_schedule_len > 0 (dep_context == 0: ring = schedule length) and delay_steps >= 0, applied per column by the
 // column's own frame count: while it is below delay_steps the column is REPLACED (src/moshi.cpp:905, lm.h:910-921: its Depth tokens are -1, nothing is read
 // out; the Depth graph is skipped when every stepping column is replaced), and audio[q] = -1 while it is below delays[q + 1] + delay_steps.
-// moshi_hot_slots_prefill / _slot_prefill (and their _long forms) and moshi_hot_slot_fork / _save / _load return -1 on this shape and change nothing.
+// moshi_hot_slots_prefill / _slot_prefill (and their _long forms) and moshi_hot_slot_fork / _save / _load return -1 on this shape and change nothing: a
+// history goes in through moshi_hot_slots_replay, a snapshot is taken with moshi_hot_slot_fork_full / _save_full / _load_full (below).
 //
 // Column b's conditions (the B > 1 form of moshi_hot_set_conditions, which does nothing on such a model): sum F32[dim] and cross F32[dim * cross_len], either
 // may be NULL to leave that half as it is. cross also runs init() (transformer.h:343-396) for column b of every layer's K / V. The setting belongs to
@@ -225,6 +226,35 @@ GGML_API int moshi_hot_set_conditions_column(moshi_hot_model_t * m, int b, const
 #define MOSHI_HOT_TEXT_KEEP INT32_MIN
 GGML_API int moshi_hot_lm_step_streams_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token, int32_t * out_audio);
 GGML_API int moshi_hot_lm_step_slots_text(moshi_hot_model_t * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token, int32_t * out_audio, int32_t * status);
+
+// Replay: a tts-shaped slots model has no provided frames (n_q == dep_q: needed_tokens == 0, lm.h:807-809), so a history is the frames a conversation
+// COMMITTED: n_q + 1 tokens each, the text value (what text_in gave, a demuxed pair as one value) and then the dep_q raw audio samples of the frame, the
+// -1 of delay_steps (lm.h:910-921) included - what moshi_hot_slot_last_raw returns after a live frame. The tokens are taken verbatim, as the
+// reference's text_prefixes / audio_prefixes override a frame's samples (lm.h:883-885, 922-930): a forced voice prefix and a recorded conversation are
+// the same call. Arguments, return values, passes and refusals of moshi_hot_slots_prefill_long, on a tts-shaped slots model only (any other model: -1,
+// nothing changes). Per frame the column's model inputs are read from its delay ring as a live step reads them (lm.h:826-834), the frame's tokens are
+// written to it (lm.h:935-943), the frame count and the stream position advance; no Depth graph runs and no sampler noise is drawn. Afterwards the slot is
+// what a fresh single-stream model with the same conditions is after n_frames steps with moshi_hot_force_last(text_f, audio_f) after each: delay ring,
+// frame count, stream position, its column's rows of every Temporal K / V ring and its row of transformer_out - on the oracle the frames that follow are
+// that model's bit for bit, for every chunk and any number of jobs per pass. The rows of a pass run moshi_streaming_transformer_layer
+// (transformer.h:910-1039) with the cross-attention (transformer.h:714-762, 936-944) of every job against its own column's condition, the condition sum
+// (lm.h:579-581) of its column and the demuxed text embedding (lm_utils.h:48-66).
+GGML_API int moshi_hot_slots_replay(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk);
+GGML_API int moshi_hot_slot_replay(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk);   // one job
+// The n_q + 1 tokens slot b committed in its latest frame (row `frames` of its delay ring, lm.h:935-943): the text, then the raw audio tokens. The delayed
+// read-out of a step lags by max(delays) frames (lm.h:950-964), so this is what a server logs per frame to hold the history that replay takes. Any slots
+// model. Returns 0, or -1 for a bad or closed slot, a slot that has stepped no frame yet, or a model that is not a slots model.
+GGML_API int moshi_hot_slot_last_raw(moshi_hot_model_t * m, int b, int32_t * tokens);
+// Snapshots that carry the conditions: signatures, states and refusals of moshi_hot_slot_fork / _save / _load. On a model that is not tts-shaped they ARE
+// those calls (same graphs, same bytes). On the tts shape a conversation's state also holds its column of cond_sum and cond_cross and of every layer's
+// cross-attention K / V (transformer.h:343-396); the destination column's own conditions are overwritten. fork copies all of it on the device. save writes
+// blob version 2 - the fingerprint also mixes cross_attention, cross_len, condition_sum, demux_second_stream and delay_steps; cond_sum (dim F32) and
+// cond_cross (dim x cross_len F32) follow transformer_out where the model has them - and load uploads both and runs init() for the column as
+// moshi_hot_set_conditions_column does: on the backend that saved it the copy continues bit for bit, on another as a conversation with those conditions
+// does there. A version-1 blob, a blob of another shape or cross_len, a truncated or an oversized one is refused and changes nothing.
+GGML_API int     moshi_hot_slot_fork_full(moshi_hot_model_t * m, int src, int dst);
+GGML_API int64_t moshi_hot_slot_save_full(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes);
+GGML_API int     moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes);
 
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute

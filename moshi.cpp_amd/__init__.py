@@ -60,7 +60,8 @@ class Stats(C.Structure):
                                          "attention_folds_planned", "chain_step_programs_in_last_plan", "vq_levels_chained_in_last_plan",
                                          "attn_block_launches_in_last_plan", "attn_block_jobs_in_last_plan", "generic_attention_nodes_in_last_plan",
                                          "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan",
-                                         "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan")]
+                                         "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan",
+                                         "cross_block_launches_in_last_plan", "cross_block_jobs_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

@@ -56,6 +56,7 @@ struct DelayRing {
         for (int q = 0; q < p->dep_q; q++)
             if (!(keep_user_codes && q >= p->io_dep_q && p->delays[q + 1] == 0)) cell(frames, q + 1) = audio[q];
     }
+    int32_t last(int i) const { return rows[index(frames, i)]; }   // column i of the row the last frame committed
     void export_rows(int32_t * dst) const { memcpy(dst, rows.data(), rows.size() * sizeof(int32_t)); }
     void import_rows(const int32_t * src, int64_t frames_) { memcpy(rows.data(), src, rows.size() * sizeof(int32_t)); frames = frames_; }
 

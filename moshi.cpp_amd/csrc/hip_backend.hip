@@ -341,7 +341,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -1395,6 +1395,62 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
     return true;
 }
 
+// B''. one job of a replay pass's cross-attention (moshi_hot.cpp cross_attention_jobs), ending at the copy into the job's rows of the layer's shared
+//      [D, H, T] tensor: x2 = cpy(permute(mul_mat(cont(transpose(V_b)), soft_max(mul_mat(K_b, q_j)))), rows), K_b / V_b = [D, Tc, H] views of one
+//      column of the cached [D, Tc, H, B] states, q_j = the job's rows of the layer's query projection [D * H, T] seen as [D, T_j, H]
+struct xattn_job_group : group { xattn_args a; xattn_block_job job; int64_t q_rs, out_rs; };
+static bool match_cross_attention_job(const analysis & an, int pos, xattn_job_group & grp) {
+    const ggml_tensor * x2 = an.g->nodes[pos];
+    if (x2->op != GGML_OP_CPY || x2->type != GGML_TYPE_F32 || !x2->data || !ggml_is_contiguous(x2)) return false;
+    const ggml_tensor * x1 = x2->src[0];
+    if (x1->op != GGML_OP_PERMUTE || uses_of(an, x1) != 1) return false;
+    const ggml_tensor * pv = x1->src[0];
+    if (pv->op != GGML_OP_MUL_MAT || uses_of(an, pv) != 1) return false;
+    const ggml_tensor * vt = pv->src[0], * sm = pv->src[1];
+    if (vt->op != GGML_OP_CONT || uses_of(an, vt) != 1 || vt->src[0]->op != GGML_OP_TRANSPOSE || uses_of(an, vt->src[0]) != 1) return false;
+    const ggml_tensor * vx = vt->src[0]->src[0];
+    if (sm->op != GGML_OP_SOFT_MAX || uses_of(an, sm) != 1 || sm->src[1] != NULL || ggml_get_op_params_f32(sm, 1) != 0.0f) return false;
+    const ggml_tensor * kq = sm->src[0];
+    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1) return false;
+    const ggml_tensor * kx = kq->src[0], * qp = kq->src[1];
+    // K / V: whole-column views of cached states (leaves of the graph), F32 [D, Tc, H]
+    for (const ggml_tensor * t : { kx, vx }) {
+        if (t->op != GGML_OP_VIEW || !t->view_src || !t->data || t->type != GGML_TYPE_F32 || uses_of(an, t) != 1) return false;
+        const ggml_tensor * root = t->view_src;
+        if (pos_of(an, root) >= 0 || !root->data || root->view_src || root->ne[0] != t->ne[0] || root->ne[1] != t->ne[1] || root->ne[2] != t->ne[2]) return false;
+        if (t->nb[0] != 4 || t->nb[1] != root->nb[1] || t->nb[2] != root->nb[2] || t->ne[3] != 1) return false;
+        const int64_t off = (const char *) t->data - (const char *) root->data;
+        if (off < 0 || off % (int64_t) root->nb[3] != 0 || off / (int64_t) root->nb[3] >= root->ne[3]) return false;
+    }
+    const int64_t D = kx->ne[0], Tc = kx->ne[1], H = kx->ne[2], Tn = qp->ne[1];
+    if (D < 1 || D > 256 || Tc < 1 || H < 1 || Tn < 1 || Tn > 64 || vx->ne[0] != D || vx->ne[1] != Tc || vx->ne[2] != H) return false;
+    if ((int64_t) kx->nb[1] < D * 4 || (int64_t) kx->nb[2] < Tc * (int64_t) kx->nb[1] || (int64_t) vx->nb[1] < D * 4 || (int64_t) vx->nb[2] < Tc * (int64_t) vx->nb[1]) return false;
+    // q: [D, T_j, H] permuted view of T_j rows of a dense [D * H, T] projection
+    if (qp->op != GGML_OP_PERMUTE || qp->type != GGML_TYPE_F32 || uses_of(an, qp) != 1 || qp->ne[0] != D || qp->ne[2] != H || qp->ne[3] != 1) return false;
+    if (qp->nb[0] != 4 || (int64_t) qp->nb[2] != D * 4 || (int64_t) qp->nb[1] != D * H * 4) return false;
+    const ggml_tensor * qv = qp->src[0];
+    if (qv->op != GGML_OP_VIEW || uses_of(an, qv) != 1 || qv->data != qp->data) return false;
+    const ggml_tensor * qsrc = qv->src[0];
+    if (!qsrc->data || qsrc->type != GGML_TYPE_F32 || !ggml_is_contiguous(qsrc) || qsrc->ne[0] != D * H) return false;
+    const int64_t q_off = (const char *) qp->data - (const char *) qsrc->data;
+    if (q_off < 0 || q_off % (D * H * 4) != 0 || q_off + Tn * D * H * 4 > (int64_t) ggml_nbytes(qsrc)) return false;
+    // out: rows of the shared tensor, dense [D, H, T_j], inside its root
+    if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != Tn || x2->ne[3] != 1) return false;
+    const ggml_tensor * oroot = x2;
+    while (oroot->view_src) oroot = oroot->view_src;
+    if (!oroot->data || (const char *) x2->data < (const char *) oroot->data || (const char *) x2->data + Tn * D * H * 4 > (const char *) oroot->data + ggml_nbytes(oroot)) return false;
+    xattn_args & a = grp.a;
+    a.q = nullptr; a.k = nullptr; a.v = nullptr; a.out = nullptr;
+    a.k_nb1 = (int64_t) kx->nb[1]; a.k_nb2 = (int64_t) kx->nb[2]; a.v_nb1 = (int64_t) vx->nb[1]; a.v_nb2 = (int64_t) vx->nb[2];
+    a.H = (int) H; a.D = (int) D; a.Tc = (int) Tc;
+    a.scale = ggml_get_op_params_f32(sm, 0);
+    grp.job = { (const float *) qp->data, (const char *) kx->data, (const char *) vx->data, (float *) x2->data, (int) Tn };
+    grp.q_rs = D * H; grp.out_rs = D * H;
+    grp.members = { pos, pos_of(an, pv), pos_of(an, vt), pos_of(an, sm), pos_of(an, kq) };
+    grp.emit_pos = pos;
+    return true;
+}
+
 // C. left-deep sum of (scaled) embedding rows ending at node `pos`
 struct embed_group : group { embed_sum_args a; };
 
@@ -2271,6 +2327,43 @@ static void pass_cross_attention(planner & pl) {
     }
 }
 
+// the cross-attention of a replay pass (tts slots): the run of per-job sequences of one layer - consecutive jobs of one shape with nothing but layout
+// nodes and their own members between their copies - as ONE k_cross_attn_blocks launch, emitted where the last of them stood (every job's inputs, the
+// layer's query projection and the cached states, are older than the first job; its output rows are read after the last). A run of more than
+// XATTN_BLOCKS_MAX jobs takes a further launch.
+static void pass_cross_attention_blocks(planner & pl) {
+    static const bool no_xattn = getenv("MI355X_NO_CROSS_ATTN_FUSION") != nullptr;
+    if (no_xattn) return;
+    xattn_blocks_args ba;
+    memset(&ba, 0, sizeof(ba));
+    int hi = -1;   // emit position of the launch being filled (ba.n_jobs > 0)
+    auto flush = [&]() {
+        if (!ba.n_jobs) return;
+        const xattn_blocks_args la = ba;
+        pl.at_pos[hi].push_back([=](hipStream_t s) { k_cross_attn_blocks(s, la); });
+        pl.p->n_cross_block_launches++; pl.p->n_cross_block_jobs += la.n_jobs;
+        ba.n_jobs = 0;
+    };
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CPY) continue;
+        xattn_job_group grp;
+        if (!match_cross_attention_job(pl.an, i, grp) || !claimable(pl, grp.members)) continue;
+        if (ba.n_jobs) {
+            const xattn_args & a = ba.a, & b = grp.a;
+            bool joins = ba.n_jobs < XATTN_BLOCKS_MAX && b.H == a.H && b.D == a.D && b.Tc == a.Tc && b.scale == a.scale && b.k_nb1 == a.k_nb1 && b.k_nb2 == a.k_nb2 &&
+                         b.v_nb1 == a.v_nb1 && b.v_nb2 == a.v_nb2 && grp.q_rs == ba.q_rs && grp.out_rs == ba.out_rs;
+            const std::set<int> inside(grp.members.begin(), grp.members.end());
+            for (int k = hi + 1; k < i && joins; k++) if (!is_view_op(pl.g->nodes[k]->op) && !inside.count(k)) joins = false;
+            if (!joins) flush();
+        }
+        claim_group(pl, grp);
+        if (!ba.n_jobs) { ba.a = grp.a; ba.q_rs = grp.q_rs; ba.out_rs = grp.out_rs; }
+        ba.job[ba.n_jobs++] = grp.job;
+        hi = grp.emit_pos;
+    }
+    flush();
+}
+
 // one embedding row through a small Q8_0 projection (tts: low-rank Depth embeddings)
 static void pass_lowrank_embed(planner & pl) {
     static const bool no_lowrank = getenv("MI355X_NO_LOWRANK_FUSION") != nullptr;
@@ -2789,6 +2882,8 @@ static void merge_chains(planner & pl) {
 //   pass_scalar_gathers    bottom-up over the node list: the top-most node first, so it claims the whole tree
 //   pass_samplers          bottom-up as well: matched at the sampler's last node
 //   pass_sampler_streams   the B-column form of the same samplers, same direction
+//   pass_cross_attention_blocks   the per-job cross-attention of a tts replay pass: before the row copies and the mat-vec pass, which would take a job's
+//                          copy and its F32 mul_mats one by one
 //   pass_embed_sums        bottom-up (a left-deep sum is matched at its last add); before the row copies
 //   pass_row_copies        one launch for all rows instead of one per row: before pass_cpy_of_cont, whose pattern every single row is
 //   pass_matvecs           after the attention pass (see there); every remaining mul_mat of a supported shape
@@ -2796,7 +2891,7 @@ static void merge_chains(planner & pl) {
 // (pass_ring_copies, pass_codec_convs, pass_cross_attention, pass_lowrank_embed, pass_cpy_of_cont, pass_timestep_of_add: no reason on record but their place)
 static void (* const fusion_passes[])(planner &) = {
     pass_heads_streams, pass_ring_copies, pass_attention, pass_codec_convs, pass_scalar_gathers, pass_samplers, pass_sampler_streams, pass_cross_attention,
-    pass_lowrank_embed, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
+    pass_cross_attention_blocks, pass_lowrank_embed, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
 };
 
 static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
@@ -2860,7 +2955,7 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
-// the fourteen *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+// the sixteen *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
 static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
     c->stats.nodes_in_last_plan = p->n_nodes;
@@ -2869,6 +2964,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.attn_block_launches_in_last_plan = p->n_attn_block_launches; c->stats.attn_block_jobs_in_last_plan = p->n_attn_block_jobs; c->stats.generic_attention_nodes_in_last_plan = p->n_generic_attn_nodes;
     c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
     c->stats.attn_row_launches_in_last_plan = p->n_attn_row_launches; c->stats.attn_row_jobs_in_last_plan = p->n_attn_row_jobs; c->stats.attn_row_rows_in_last_plan = p->n_attn_row_rows;
+    c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

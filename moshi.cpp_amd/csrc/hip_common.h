@@ -250,6 +250,16 @@ void   k_inproj_attn(hipStream_t s, const mv_args & a, const attn_args & at, voi
 struct xattn_args { const float * q; const char * k; const char * v; int64_t k_nb1, k_nb2, v_nb1, v_nb2; int H, D, Tc; float scale; float * out;
                     int B = 1; int64_t q_cs = 0, out_cs = 0, k_nb3 = 0, v_nb3 = 0; };
 void k_cross_attn(hipStream_t s, const xattn_args & a);
+// Replay of a tts-shaped slots model (moshi_hot_slots_replay): the cross-attention blocks of one layer of one [dim, T] pass as ONE launch. Job j = T_j
+// consecutive rows of the pass that belong to one slot: its rows of the shared query projection (row t at q + t * q_rs floats), its own column of the
+// [D, Tc, H, B] K / V states (k / v: the column's base) and its rows of the shared [D, H, T] output (row t at out + t * out_rs floats). Workgroup
+// (head, row) runs cross_attn_body on that row's query and its job's column, so every row's result is bit-equal to k_cross_attn on that row alone;
+// no workgroup waits for another. `a` holds what the jobs share (H, D, Tc, scale, the K / V strides); the table goes by value in the kernel
+// arguments, a pass of more jobs takes a further launch.
+#define XATTN_BLOCKS_MAX 16
+struct xattn_block_job { const float * q; const char * k, * v; float * out; int T; };
+struct xattn_blocks_args { xattn_args a; int64_t q_rs, out_rs; int n_jobs; xattn_block_job job[XATTN_BLOCKS_MAX]; };
+void k_cross_attn_blocks(hipStream_t s, const xattn_blocks_args & a);
 
 // sum of (scaled) embedding rows, left-to-right
 #define EMBED_SUM_MAX 40      // terms of one fused embedding sum (tts: 32 audio codebooks + the demuxed text pair); the kernel is instantiated for 24 and 40

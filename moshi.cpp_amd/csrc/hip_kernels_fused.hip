@@ -2326,6 +2326,31 @@ void k_cross_attn(hipStream_t s, const xattn_args & a) {
     if (a.B == 1) cross_attn_kernel<<<a.H, 256, smem, s>>>(a);
     else cross_attn_streams_kernel<<<dim3((unsigned) a.H, (unsigned) a.B), 256, smem, s>>>(a);
 }
+// The rows of a replay pass: workgroup (h, r) is cross_attn_kernel's workgroup h over row r of the pass - the query row of the job that row belongs to,
+// that job's column of K / V and its output row. The job is found by walking the by-value table (at most XATTN_BLOCKS_MAX uniform compares, scalar
+// loads from the kernel arguments); gridDim.y is the sum of the jobs' rows, so the walk ends inside the table.
+__global__ void __launch_bounds__(256) cross_attn_blocks_kernel(xattn_blocks_args ba) {
+    extern __shared__ float xsm[];
+    __shared__ float sh_f[4];
+    __shared__ double sh_d[4];
+    const int h = blockIdx.x;
+    int t = blockIdx.y, j = 0;
+    while (j < ba.n_jobs - 1 && t >= ba.job[j].T) { t -= ba.job[j].T; j++; }
+    const xattn_block_job & jb = ba.job[j];
+    if (t >= jb.T) return;   // (never: the grid has exactly the jobs' rows)
+    cross_attn_body(ba.a, jb.q + (int64_t) t * ba.q_rs + (int64_t) h * ba.a.D, jb.k + (int64_t) h * ba.a.k_nb2, jb.v + (int64_t) h * ba.a.v_nb2,
+                    jb.out + (int64_t) t * ba.out_rs + (int64_t) h * ba.a.D, xsm, sh_f, sh_d);
+}
+void k_cross_attn_blocks(hipStream_t s, const xattn_blocks_args & ba) {
+    const xattn_args & a = ba.a;
+    GGML_ASSERT(a.D >= 1 && a.D <= 256 && a.Tc >= 1 && a.H >= 1 && ba.n_jobs >= 1 && ba.n_jobs <= XATTN_BLOCKS_MAX);
+    int rows = 0;
+    for (int j = 0; j < ba.n_jobs; j++) { GGML_ASSERT(ba.job[j].T >= 1 && ba.job[j].T <= 64); rows += ba.job[j].T; }
+    GGML_ASSERT(rows <= 65535);
+    const size_t smem = (size_t) ((a.D + a.Tc + 1) & ~1) * 4 + (size_t) (256 / a.D > 0 ? 256 / a.D : 1) * a.D * 8;   // the body's [D] | [Tc] | [G][D], as k_cross_attn
+    GGML_ASSERT(smem <= 64 * 1024);
+    cross_attn_blocks_kernel<<<dim3((unsigned) a.H, (unsigned) rows), 256, smem, s>>>(ba);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // embedding sum: out = (((e_0 + e_1) + e_2) + ...), e_i = dequant(table_i[row idx_i]) * scale_i

@@ -1267,7 +1267,8 @@ extern "C" int moshi_hot_n_streams(moshi_hot_model_t * m) { return m->n_streams;
 extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
     return create_columns(backend, cfg, seed, n_slots, ModelKind::slots);
 }
-// the tts shape of a B > 1 model (no codebook is an input): a conversation's conditions would have to travel with its prefill or snapshot, which refuse it
+// the tts shape of a B > 1 model (no codebook is an input): a conversation's conditions travel with its history or snapshot, so prefill and the plain
+// snapshot calls refuse it (moshi_hot_slots_replay, moshi_hot_slot_fork_full / _save_full / _load_full take it)
 static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m->cfg.n_q == m->cfg.dep_q; }
 // slot b of a slots model, or NULL (a bad index or a model of another kind)
 static moshi_hot_model::Column * slot(moshi_hot_model_t * m, int b) {
@@ -1619,26 +1620,25 @@ extern "C" void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, 
 
 // moshi_lmgen_step (lm.h:778-979) for the plain moshi model: no state machine, no prefixes
 namespace {
-// moshi_scaled_embedding_demux_step (lm_utils.h:68-85)
-void demux_set(const moshi_hot_config & c, int32_t input, T left, T right, T right_scale) {
+// moshi_scaled_embedding_demux_step (lm_utils.h:68-85): the two rows a text value stands for, and the scale of the right one (0: no right half)
+struct DemuxInput { int32_t left, right; float right_scale; };
+DemuxInput demux_split(const moshi_hot_config & c, int32_t input) {
     if (input < 0) input = 0;
-    const int32_t n = c.text_card + 1;
-    int32_t l = input % n, r = input / n - 1;
-    const float sc = r < 0 ? 0.f : 1.f;
-    if (r < 0) r = 0;
-    ggml_backend_tensor_set(left, &l, 0, 4);
-    ggml_backend_tensor_set(right, &r, 0, 4);
-    ggml_backend_tensor_set(right_scale, &sc, 0, 4);
+    const int32_t n = c.text_card + 1, r = input / n - 1;
+    return { input % n, r < 0 ? 0 : r, r < 0 ? 0.f : 1.f };
+}
+void demux_set(const moshi_hot_config & c, int32_t input, T left, T right, T right_scale) {
+    const DemuxInput d = demux_split(c, input);
+    ggml_backend_tensor_set(left, &d.left, 0, 4);
+    ggml_backend_tensor_set(right, &d.right, 0, 4);
+    ggml_backend_tensor_set(right_scale, &d.right_scale, 0, 4);
 }
 // the same for the B columns of a B > 1 model: left / right I32 [B], right_scale F32 [1, B]
 void demux_set_columns(const moshi_hot_config & c, const std::vector<int32_t> & inputs, T left, T right, T right_scale) {
-    const int32_t n = c.text_card + 1;
     std::vector<int32_t> l(inputs.size()), r(inputs.size()); std::vector<float> sc(inputs.size());
     for (size_t b = 0; b < inputs.size(); b++) {
-        const int32_t input = inputs[b] < 0 ? 0 : inputs[b];
-        l[b] = input % n; r[b] = input / n - 1;
-        sc[b] = r[b] < 0 ? 0.f : 1.f;
-        if (r[b] < 0) r[b] = 0;
+        const DemuxInput d = demux_split(c, inputs[b]);
+        l[b] = d.left; r[b] = d.right; sc[b] = d.right_scale;
     }
     ggml_backend_tensor_set(left, l.data(), 0, l.size() * 4);
     ggml_backend_tensor_set(right, r.data(), 0, r.size() * 4);
@@ -2212,6 +2212,8 @@ struct PassInputs {   // per embedding, one id and one scale per row of the pass
     std::vector<std::vector<int32_t>> ids; std::vector<std::vector<float>> scales;
     PassInputs(int ncb, int Tn) : ids((size_t) ncb, std::vector<int32_t>((size_t) Tn)), scales((size_t) ncb, std::vector<float>((size_t) Tn)) {}
     void set(int i, int row, TokenInput in) { ids[(size_t) i][(size_t) row] = in.row; scales[(size_t) i][(size_t) row] = in.scale; }
+    // a replay pass of a tts-shaped slots model (empty otherwise): the right half of every row's demuxed text value, and the column whose conditions the row takes
+    std::vector<int32_t> right, col; std::vector<float> right_scale;
 };
 // host side of n provided frames of one ring (lm.h:812-817, 826-834, 933), filling rows [row0, row0 + n) of the pass: ring writes, model inputs, frame count
 void provided_frames(DelayRing & ring, const int32_t * tokens, int n, int row0, PassInputs & in) {
@@ -2222,16 +2224,46 @@ void provided_frames(DelayRing & ring, const int32_t * tokens, int n, int row0, 
         ring.commit(0, nullptr, true);
     }
 }
-// moshi_lmmodel_text_token_embed over the Tn rows of a pass, plus the condition sum of a model that has one (no B > 1 model does)
+// host side of n history frames of one tts column (moshi_hot_slots_replay), filling rows [row0, row0 + n) of the pass: a frame is what a live frame
+// committed - its model inputs are read from the ring as a live step reads them (lm.h:826-834, the text through the demux split), then its tokens go
+// into the ring verbatim (lm.h:935-943: the -1 rules are the recorder's, as with the reference's audio_prefixes, lm.h:922-930) and the count advances
+void replayed_frames(const moshi_hot_config & c, DelayRing & ring, int b, const int32_t * tokens, int n, int row0, PassInputs & in) {
+    const int ncb = ring.p->cols();
+    if (in.col.empty()) { in.col.resize(in.ids[0].size()); in.right.resize(in.ids[0].size()); in.right_scale.resize(in.ids[0].size()); }
+    for (int t = 0; t < n; t++) {
+        const size_t row = (size_t) (row0 + t);
+        for (int i = 0; i < ncb; i++) {
+            const int32_t id = ring.input(i, ring.frames);
+            if (i == 0 && c.demux_second_stream) {
+                const DemuxInput d = demux_split(c, id);
+                in.set(0, row0 + t, { d.left, 1.f });
+                in.right[row] = d.right; in.right_scale[row] = d.right_scale;
+            } else in.set(i, row0 + t, token_input(id));
+        }
+        in.col[row] = b;
+        ring.commit(tokens[(size_t) t * ncb], tokens + (size_t) t * ncb + 1, false);
+    }
+}
+// moshi_lmmodel_text_token_embed over the Tn rows of a pass, plus the condition sum of a model that has one. A replay pass (in.col set): the demuxed text
+// terms of build_input_embedding in its order of additions, and column col[t] of cond_sum on row t (the rows gathered by get_rows: an exact copy)
 T embedding_sum_rows(moshi_hot_model * m, Builder & s, const PassInputs & in, int Tn) {
+    const bool replay = !in.col.empty();
     T input = nullptr;
-    for (size_t i = 0; i < in.ids.size(); i++) {
+    size_t first = 0;
+    if (replay && m->cfg.demux_second_stream) {   // moshi_scaled_embedding_demux_build (lm_utils.h:48-66)
+        T l = ggml_get_rows(s, m->text_emb, s.i32s(in.ids[0])), r = ggml_get_rows(s, m->text_emb, s.i32s(in.right));
+        T ry = linear(s, m->text_out2, r), ly = linear(s, m->text_out1, l);
+        input = ggml_add(s, ly, ggml_mul(s, ry, s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), in.right_scale.data())));
+        first = 1;
+    }
+    for (size_t i = first; i < in.ids.size(); i++) {
         T idx = s.i32s(in.ids[i]);
         T sc = s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), in.scales[i].data());
         T e = ggml_mul(s, ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[i - 1], idx), sc);
         input = input ? ggml_add(s, input, e) : e;
     }
-    return m->cfg.condition_sum ? ggml_add(s, m->cond_sum, input) : input;
+    if (!m->cfg.condition_sum) return input;
+    return ggml_add(s, replay ? ggml_get_rows(s, m->cond_sum, s.i32s(in.col)) : m->cond_sum, input);   // lm.h:579-581
 }
 // the [C, n] block of the bias table for n rows from stream position pos on, as an uploaded constant (before the ring's wrap it is plainly causal:
 // slot cc is open to row t iff cc <= pos + t, torch.h:170-223): passes of one shape are then structurally identical and the backend reuses one plan
@@ -2514,10 +2546,42 @@ T attention_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std:
     return linear(c, L.out_proj[0], all);
 }
 
-// transformer_layer over the rows of a pass (the Temporal stack of a B > 1 model: RMS norms, gated FFN, no cross-attention, no layer scales)
-T transformer_layer_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std::vector<PassJob> & jobs) {
+// moshi_streaming_multihead_cross_attention (cross_attention() above) over the rows of a replay pass: ONE query projection and ONE cross_out for all
+// rows; between them piece j's rows run the single-stream op sequence against column b_j of k_cross / v_cross ([D, cross_len, H] views of the
+// [D, cross_len, H, B] states) and leave their result in rows [row_j, row_j + T_j) of one [D, H, T] tensor, as attention_jobs does. Cross-attention
+// has no position: a ring-ordered piece is one block here.
+T cross_attention_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std::vector<PassJob> & pieces) {
+    const int64_t H = tr.heads, D = tr.dim / tr.heads, Tn = x->ne[1], Tc = L.k_cross->ne[1];
+    T q_all = linear_view(c, L.cross_in, 0, (int) L.cross_in->ne[1] / 3, x);   // [dim, T]
+    const size_t out_row = (size_t) (D * H) * 4;
+    T out = c.tensor(GGML_TYPE_F32, D, H, Tn);
+    int out_at = 0;
+    for (const PassJob & j : pieces) {
+        T q = ggml_view_3d(c, q_all, D, H, j.n, (size_t) D * 4, q_all->nb[1], (size_t) j.row * q_all->nb[1]);
+        q = ggml_permute(c, q, 0, 2, 1, 3);
+        T k = ggml_view_3d(c, L.k_cross, D, Tc, H, L.k_cross->nb[1], L.k_cross->nb[2], (size_t) j.b * L.k_cross->nb[3]);
+        T v = ggml_view_3d(c, L.v_cross, D, Tc, H, L.v_cross->nb[1], L.v_cross->nb[2], (size_t) j.b * L.v_cross->nb[3]);
+        T w = ggml_mul_mat(c, k, q);
+        w = ggml_soft_max_ext(c, w, nullptr, 1.f / sqrtf((float) D), 0.0f);
+        v = ggml_cont(c, ggml_transpose(c, v));
+        T o = ggml_mul_mat(c, v, w);
+        T dst = ggml_view_3d(c, out, D, H, j.n, (size_t) D * 4, out_row, (size_t) ((int64_t) (j.row - out_at) * (int64_t) out_row));
+        out = ggml_cpy(c, ggml_permute(c, o, 0, 2, 1, 3), dst);
+        out_at = j.row;
+    }
+    T all = ggml_view_3d(c, out, D * H, Tn, 1, out_row, out_row * (size_t) Tn, (size_t) (-(int64_t) out_at * (int64_t) out_row));
+    return linear(c, L.cross_out, all);
+}
+
+// transformer_layer over the rows of a pass (the Temporal stack of a B > 1 model: RMS norms, gated FFN, no layer scales; cross-attention over the pieces
+// of a replay pass, transformer.h:936-944). jobs: the attention sequences, pieces: the pass as it was cut (a ring-ordered piece is one entry)
+T transformer_layer_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std::vector<PassJob> & jobs, const std::vector<PassJob> & pieces) {
     T nx = apply_norm(c, L.norm1, x);
     x = ggml_add(c, x, attention_jobs(c, tr, L, nx, jobs, tr.max_period != 0));
+    if (L.cross_in) {
+        nx = apply_norm(c, L.norm_cross, x);
+        x = ggml_add(c, x, cross_attention_jobs(c, tr, L, nx, pieces));
+    }
     nx = apply_norm(c, L.norm2, x);
     T update = gating(c, L.gate_in[0], L.gate_out[0], nx);
     if (x->ne[1] > 1 || x->ne[2] > 1) update = ggml_reshape_3d(c, update, update->ne[0], x->ne[1], x->ne[2]);   // (transformer_layer's fold)
@@ -2534,13 +2598,17 @@ Builder & ring_ordered_scratch(moshi_hot_model * m) {
     return *m->scratch_rows;
 }
 // one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
-void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames) {
+void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames, bool replay) {
     const int C = m->temporal.capacity;
     int Tn = 0;
     bool any_ordered = false;
     for (const PassJob & j : jobs) { Tn += j.n; any_ordered = any_ordered || j.ordered; }
     PassInputs in(m->cfg.n_q + 1, Tn);
-    for (size_t ji = 0; ji < jobs.size(); ji++) provided_frames(m->cols[(size_t) jobs[ji].b].ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
+    for (size_t ji = 0; ji < jobs.size(); ji++) {
+        DelayRing & ring = m->cols[(size_t) jobs[ji].b].ring;
+        if (replay) replayed_frames(m->cfg, ring, jobs[ji].b, frames[ji], jobs[ji].n, jobs[ji].row, in);
+        else provided_frames(ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
+    }
     PhaseTimer pt(m, 1);
     Builder & s = any_ordered ? ring_ordered_scratch(m) : *m->scratch;
     T input = embedding_sum_rows(m, s, in, Tn);
@@ -2563,7 +2631,7 @@ void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
         if (any_ordered && j.rot.rotr) s.expand(j.rot.rotr);
     }
     T x = input;
-    for (auto & L : m->temporal.layers) x = transformer_layer_jobs(s, m->temporal, L, x, seqs);
+    for (auto & L : m->temporal.layers) x = transformer_layer_jobs(s, m->temporal, L, x, seqs, jobs);
     for (const PassJob & j : jobs) {   // the slot's row of transformer_out as the last of its frames leaves it (lm.h:434, 847-849)
         T last = ggml_view_2d(s, x, x->ne[0], 1, x->nb[1], (size_t) (j.row + j.n - 1) * x->nb[1]);
         T dst = ggml_view_1d(s, m->transformer_out, x->ne[0], (size_t) j.b * m->transformer_out->nb[2]);
@@ -2577,8 +2645,10 @@ void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
 // pieces in job order, a pass of at most `chunk` rows; a piece that would cross the ring's end stops there (everything before the wrap stays in block
 // form) and closes its pass, so that no pass holds two pieces of one slot; a piece at or past the ring's end is ring-ordered, and a pass holds at most
 // RING_ORDERED_ROWS_MAX such rows. With no job past the ring's end none of the three rules ever applies: the passes are those of the refusing call.
-int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end) {
-    if (m->kind != ModelKind::slots || tts_shape(m) || n_jobs < 0 || n_jobs > m->n_streams) return -1;
+// replay: moshi_hot_slots_replay - the same passes over history frames of a tts-shaped model (which has no provided frames: needed_tokens == 0,
+// lm.h:807-809), and of no other; the prefill calls keep refusing that shape.
+int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end, bool replay = false) {
+    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams) return -1;
     const int ncb = m->cfg.n_q + 1;
     const int64_t C = m->temporal.capacity;
     int total = 0;
@@ -2608,12 +2678,12 @@ int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const 
             rows += Tj; done += Tj;
             const bool at_ring_end = !pj.ordered && pj.pos + Tj == C && done < n_frames[j];   // the job goes on ring-ordered: in a pass of its own
             if (rows == chunk || ordered_rows == RING_ORDERED_ROWS_MAX || at_ring_end || (j == n_jobs - 1 && done == n_frames[j])) {
-                slots_prefill_pass(m, jobs, frames);
+                slots_prefill_pass(m, jobs, frames, replay);
                 jobs.clear(); frames.clear(); rows = 0; ordered_rows = 0;
             }
         }
     }
-    if (!jobs.empty()) slots_prefill_pass(m, jobs, frames);   // (the last jobs had no frames)
+    if (!jobs.empty()) slots_prefill_pass(m, jobs, frames, replay);   // (the last jobs had no frames)
     ggml_backend_mi355x_set_capture(m->be, 1);
     return total;
 }
@@ -2632,6 +2702,21 @@ extern "C" int moshi_hot_slots_prefill_long(moshi_hot_model_t * m, int n_jobs, c
 extern "C" int moshi_hot_slot_prefill_long(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk) {
     const int32_t sb = b;
     return moshi_hot_slots_prefill_long(m, 1, &sb, &tokens, &n_frames, chunk);
+}
+// a tts-shaped slots model: history frames (what live frames committed) instead of provided ones; any length, as the _long calls
+extern "C" int moshi_hot_slots_replay(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
+    return slots_prefill(m, n_jobs, slots, tokens, n_frames, chunk, true, true);
+}
+extern "C" int moshi_hot_slot_replay(moshi_hot_model_t * m, int b, const int32_t * tokens, int n_frames, int chunk) {
+    const int32_t sb = b;
+    return moshi_hot_slots_replay(m, 1, &sb, &tokens, &n_frames, chunk);
+}
+// the tokens slot b committed in its latest frame: row `frames` of its delay ring (lm.h:935-943)
+extern "C" int moshi_hot_slot_last_raw(moshi_hot_model_t * m, int b, int32_t * tokens) {
+    const moshi_hot_model::Column * s = slot(m, b);
+    if (!s || !s->open || s->ring.frames < 1 || !tokens) return -1;
+    for (int i = 0; i <= m->cfg.n_q; i++) tokens[i] = s->ring.last(i);
+    return 0;
 }
 extern "C" int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold) {
     moshi_hot_model::Column * s = slot(m, b);
@@ -2652,6 +2737,9 @@ struct SlotBlobHeader {
     moshi_hot_sampling sampling;
 };
 const uint32_t SLOT_BLOB_MAGIC = 0x544C534Du, SLOT_BLOB_VERSION = 1;   // "MSLT"
+// Version 2, the blob of a tts-shaped slot (moshi_hot_slot_save_full): behind transformer_out come the column's cond_sum (dim F32) and cond_cross
+// (dim x cross_len F32) where the model has them, then the padding and the ring rows. K / V of the cross-attention are not in it: load recomputes them.
+const uint32_t SLOT_BLOB_VERSION_FULL = 2;
 static_assert(sizeof(SlotBlobHeader) == 88, "the blob header has no padding");
 
 // FNV-1a over what a blob's bytes depend on: a blob only loads into a model that would have laid the same conversation out the same way
@@ -2663,10 +2751,14 @@ uint64_t slot_fingerprint(const moshi_hot_model * m) {
     for (int i = 0; i <= c.n_q; i++) mix(c.delays[i]);
     mix(m->temporal.layers[0].kcache->type);
     mix(sampled_model(m) ? 1 : 0);
+    if (tts_shape(m)) { mix(c.cross_attention); mix(c.cross_attention ? c.cross_len : 0); mix(c.condition_sum); mix(c.demux_second_stream); mix(c.delay_steps); }   // (version 2)
     return h;
 }
+int64_t slot_cond_floats(const moshi_hot_model * m) {   // a version-2 blob's conditions
+    return (m->cond_sum ? (int64_t) m->cfg.dim : 0) + (m->cond_cross ? (int64_t) m->cfg.dim * m->cfg.cross_len : 0);
+}
 int64_t slot_host_bytes(const moshi_hot_model * m) {   // everything in front of the ring rows
-    const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->proto.rows * m->proto.cols() * 4 + (int64_t) m->cfg.dim * 4;
+    const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->proto.rows * m->proto.cols() * 4 + (int64_t) m->cfg.dim * 4 + (tts_shape(m) ? slot_cond_floats(m) * 4 : 0);
     return (n + 15) / 16 * 16;
 }
 int64_t slot_ring_bytes(const moshi_hot_model * m, int64_t n_rows) {
@@ -2678,7 +2770,9 @@ int64_t slot_live_rows(const moshi_hot_model * m, const moshi_hot_model::Column 
 // src (src < 0: of a contiguous BF16 staging tensor [D, n, H, 2 L], uploaded from rings_in first) into the same rows of column dst (dst < 0: into the
 // staging tensor, read back to rings_out) - and the row copy of transformer_out (staged through an F32[dim] tensor likewise). The device plan turns the
 // ring copies into one launch (hip_backend.hip match_ring_copies); the oracle and a plan without fusion run them as the generic strided copies they are.
-void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * tout_in, const void * rings_in, void * tout_out, void * rings_out) {
+// conditions (a fork of a tts-shaped slot, src and dst >= 0): also column src's conditions into column dst - every layer's k_cross and v_cross column, which
+// are [D, cross_len, H] views like the ring rows and follow them as a second run of ring copies, then the cond_sum and cond_cross columns as plain copies.
+void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * tout_in, const void * rings_in, void * tout_out, void * rings_out, bool conditions = false) {
     Builder & s = *m->scratch;
     const Transformer & tr = m->temporal;
     const int64_t dim = m->cfg.dim, H = tr.heads, D = dim / H;
@@ -2693,7 +2787,15 @@ void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const vo
         j++;
         s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
     }
+    if (conditions) for (const Layer & L : tr.layers) for (T st : { L.k_cross, L.v_cross }) if (st)
+        s.expand(ggml_cpy(s, ggml_view_3d(s, st, st->ne[0], st->ne[1], st->ne[2], st->nb[1], st->nb[2], (size_t) src * st->nb[3]),
+                          ggml_view_3d(s, st, st->ne[0], st->ne[1], st->ne[2], st->nb[1], st->nb[2], (size_t) dst * st->nb[3])));
     s.expand(ggml_cpy(s, src >= 0 ? tout_row(src) : tout_stage, dst >= 0 ? tout_row(dst) : tout_stage));
+    if (conditions && m->cond_sum) s.expand(ggml_cpy(s, ggml_view_1d(s, m->cond_sum, dim, (size_t) src * m->cond_sum->nb[1]), ggml_view_1d(s, m->cond_sum, dim, (size_t) dst * m->cond_sum->nb[1])));
+    if (conditions && m->cond_cross) {
+        T cc = m->cond_cross;
+        s.expand(ggml_cpy(s, ggml_view_2d(s, cc, cc->ne[0], cc->ne[1], cc->nb[1], (size_t) src * cc->nb[2]), ggml_view_2d(s, cc, cc->ne[0], cc->ne[1], cc->nb[1], (size_t) dst * cc->nb[2])));
+    }
     ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph: a repeated fork of the same pair must not pay for a hipGraph capture
     s.alloc();
     if (src < 0) {
@@ -2709,12 +2811,12 @@ void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const vo
     s.release_scratch();
     ggml_backend_mi355x_set_capture(m->be, 1);
 }
-}  // namespace
 
-extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) {
+// full: the _full calls, which take a tts-shaped model (and are the plain calls on any other); the plain calls refuse it
+int slot_fork(moshi_hot_model_t * m, int src, int dst, bool full) {
     moshi_hot_model::Column * a = slot(m, src), * b = slot(m, dst);
-    if (!a || !b || src == dst || !a->open || b->open || tts_shape(m)) return -1;
-    slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr);
+    if (!a || !b || src == dst || !a->open || b->open || (tts_shape(m) && !full)) return -1;
+    slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr, tts_shape(m));
     *b = *a;
     b->held = false;
     m->sampling[(size_t) dst] = m->sampling[(size_t) src];
@@ -2722,9 +2824,9 @@ extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) {
     return 0;
 }
 
-extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) {
+int64_t slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes, bool full) {
     const moshi_hot_model::Column * col = slot(m, b);
-    if (!col || !col->open || tts_shape(m) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || !col->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m), total = host + slot_ring_bytes(m, n);
     if (!buf) return total;
     if (nbytes < total) return -1;
@@ -2732,7 +2834,7 @@ extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf,
     memset(out, 0, (size_t) host);
     SlotBlobHeader h;
     memset(&h, 0, sizeof(h));
-    h.magic = SLOT_BLOB_MAGIC; h.version = SLOT_BLOB_VERSION; h.fingerprint = slot_fingerprint(m);
+    h.magic = SLOT_BLOB_MAGIC; h.version = tts_shape(m) ? SLOT_BLOB_VERSION_FULL : SLOT_BLOB_VERSION; h.fingerprint = slot_fingerprint(m);
     h.total_bytes = total; h.frames = col->ring.frames; h.pos = col->pos; h.n_rows = n;
     h.ring_rows = m->proto.rows; h.ring_cols = m->proto.cols();
     h.seeded = m->sampling[(size_t) b].seeded ? 1 : 0; h.sampling = m->sampling[(size_t) b].s;
@@ -2740,23 +2842,34 @@ extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf,
     int32_t * ring = (int32_t *) (out + sizeof(h));
     col->ring.export_rows(ring);
     slot_state_graph(m, b, -1, n, nullptr, nullptr, ring + col->ring.rows.size(), out + host);
+    if (tts_shape(m)) {   // the column's conditions, behind transformer_out
+        float * cond = (float *) (ring + col->ring.rows.size()) + m->cfg.dim;
+        if (m->cond_sum) { ggml_backend_tensor_get(m->cond_sum, cond, (size_t) b * m->cond_sum->nb[1], (size_t) m->cfg.dim * 4); cond += m->cfg.dim; }
+        if (m->cond_cross) ggml_backend_tensor_get(m->cond_cross, cond, (size_t) b * m->cond_cross->nb[2], (size_t) m->cfg.dim * (size_t) m->cfg.cross_len * 4);
+    }
     return total;
 }
 
-extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) {
+int slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes, bool full) {
     moshi_hot_model::Column * col = slot(m, b);
-    if (!col || col->open || tts_shape(m) || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || col->open || (tts_shape(m) && !full) || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     const uint8_t * in = (const uint8_t *) buf;
     SlotBlobHeader h;
     memcpy(&h, in, sizeof(h));
     const moshi_hot_config & c = m->cfg;
     const int64_t host = slot_host_bytes(m), C = m->temporal.capacity;
-    if (h.magic != SLOT_BLOB_MAGIC || h.version != SLOT_BLOB_VERSION || h.fingerprint != slot_fingerprint(m)) return -1;
+    if (h.magic != SLOT_BLOB_MAGIC || h.version != (tts_shape(m) ? SLOT_BLOB_VERSION_FULL : SLOT_BLOB_VERSION) || h.fingerprint != slot_fingerprint(m)) return -1;
     if (h.pos < 0 || h.frames < 0 || h.n_rows != (h.pos < C ? h.pos : C) || h.ring_rows != m->proto.rows || h.ring_cols != m->proto.cols()) return -1;
     if (h.total_bytes != host + slot_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
     const moshi_hot_sampling & sp = h.sampling;
     if (sampled_model(m) && (!(sp.temp > 0.f) || !(sp.temp_text > 0.f) || sp.top_k < 1 || sp.top_k > c.top_k || sp.top_k_text < 1 || sp.top_k_text > c.top_k_text)) return -1;
     const int32_t * ring = (const int32_t *) (in + sizeof(h));
+    if (tts_shape(m) && slot_cond_floats(m)) {
+        // the conversation's conditions take the column over: uploaded, and the cross-attention state recomputed, exactly as moshi_hot_set_conditions_column
+        // does (on the backend that saved the blob the same arithmetic as before the save)
+        const float * cond = (const float *) (ring + (size_t) h.ring_rows * (size_t) h.ring_cols) + c.dim;
+        moshi_hot_set_conditions_column(m, b, m->cond_sum ? cond : nullptr, m->cond_cross ? cond + (m->cond_sum ? c.dim : 0) : nullptr);
+    }
     slot_state_graph(m, -1, b, h.n_rows, ring + (size_t) h.ring_rows * (size_t) h.ring_cols, in + host, nullptr, nullptr);
     col->ring.import_rows(ring, h.frames);
     col->pos = h.pos; col->open = true; col->held = false;
@@ -2765,6 +2878,15 @@ extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * bu
     m->sampling_dirty = true;
     return 0;
 }
+}  // namespace
+
+extern "C" int moshi_hot_slot_fork(moshi_hot_model_t * m, int src, int dst) { return slot_fork(m, src, dst, false); }
+extern "C" int64_t moshi_hot_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) { return slot_save(m, b, buf, nbytes, false); }
+extern "C" int moshi_hot_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) { return slot_load(m, b, buf, nbytes, false); }
+// the same with the conversation's conditions in the state (moshi_hot.h): what a tts-shaped slots model takes; the plain calls on any other model
+extern "C" int moshi_hot_slot_fork_full(moshi_hot_model_t * m, int src, int dst) { return slot_fork(m, src, dst, true); }
+extern "C" int64_t moshi_hot_slot_save_full(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) { return slot_save(m, b, buf, nbytes, true); }
+extern "C" int moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) { return slot_load(m, b, buf, nbytes, true); }
 
 static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }

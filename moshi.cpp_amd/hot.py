@@ -94,6 +94,12 @@ SIGNATURES = {
     "moshi_hot_slot_fork": (C.c_int, [P, C.c_int, C.c_int]),
     "moshi_hot_slot_save": (C.c_int64, [P, C.c_int, P, C.c_int64]),
     "moshi_hot_slot_load": (C.c_int, [P, C.c_int, P, C.c_int64]),
+    "moshi_hot_slots_replay": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
+    "moshi_hot_slot_replay": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
+    "moshi_hot_slot_last_raw": (C.c_int, [P, C.c_int, P]),
+    "moshi_hot_slot_fork_full": (C.c_int, [P, C.c_int, C.c_int]),
+    "moshi_hot_slot_save_full": (C.c_int64, [P, C.c_int, P, C.c_int64]),
+    "moshi_hot_slot_load_full": (C.c_int, [P, C.c_int, P, C.c_int64]),
     "moshi_hot_set_sampling": (C.c_int, [P, C.c_int, P]),
     "moshi_hot_get_sampling": (C.c_int, [P, C.c_int, P, P]),
     "moshi_hot_sampling_noise": (None, [C.c_uint64, C.c_int64, C.c_int, C.c_int, P]),
