@@ -129,6 +129,7 @@ struct ggml_mi355x_stats {
     int64_t attn_row_rows_in_last_plan;         // ... and the rows of those jobs
     int64_t cross_block_launches_in_last_plan;  // k_cross_attn_blocks launches of the last plan (tts replay: the cross-attention of one layer of a pass) ...
     int64_t cross_block_jobs_in_last_plan;      // ... and the jobs they hold
+    int64_t float_batched_mms_in_last_plan;     // k_mm_f_batched launches of the last plan (BF16 / F16 weights against 2..64 activation rows on f64 MFMA tiles)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

@@ -61,7 +61,8 @@ class Stats(C.Structure):
                                          "attn_block_launches_in_last_plan", "attn_block_jobs_in_last_plan", "generic_attention_nodes_in_last_plan",
                                          "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan",
                                          "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan",
-                                         "cross_block_launches_in_last_plan", "cross_block_jobs_in_last_plan")]
+                                         "cross_block_launches_in_last_plan", "cross_block_jobs_in_last_plan",
+                                         "float_batched_mms_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

@@ -341,7 +341,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -536,6 +536,13 @@ struct emitter {
 };
 
 static bool is_qblock(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0; }
+// BF16 / F16 weights against 2..64 activation rows: the f64-MFMA mat-mul (k_mm_f_batched). MI355X_MMF=0 sends them back to the generic product (the A/B of DESIGN.md 23)
+static bool float_batched_ok(const ggml_tensor * w, int64_t T) {
+    static const bool off = [] { const char * v = getenv("MI355X_MMF"); return v != nullptr && atoi(v) == 0; }();
+    return !off && w->data && (uintptr_t) w->data % 16 == 0 && w->nb[1] % 16 == 0 && k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
+}
+// its row converters read the activation rows (and alpha) as float4
+static bool aligned16(const void * p) { return p != nullptr && (uintptr_t) p % 16 == 0; }
 
 static bool fill_matvec_base(mv_args & a, const ggml_tensor * mm) {
     const ggml_tensor * w = mm->src[0], * b = mm->src[1];
@@ -648,6 +655,17 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
                     void * ws = em.ws(k_mm_q4k_batched_ws_size(K, Tn));
                     const int wt = (int) w0->type;
                     em.push([=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); });
+                    return;
+                }
+                // ... against BF16 / F16 weights: f64 MFMA tiles
+                if (!no_batched && x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) && ggml_is_contiguous(w0) &&
+                    w0->ne[2] == 1 && w0->ne[3] == 1 && aligned16(x1->data) && float_batched_ok(w0, Tn)) {
+                    const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
+                    const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                    void * ws = em.ws(k_mm_f_batched_ws_size(K, Tn));
+                    const int wt = (int) w0->type;
+                    em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); });
+                    em.p->n_float_batched_mms++;
                     return;
                 }
             }
@@ -1287,16 +1305,19 @@ static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & gr
 }
 
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
-//     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue
-struct bmm_group : group { std::function<void(hipStream_t)> run; };
+//     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue.
+//     BF16 / F16 weights: the f64-MFMA mat-mul with the same folds in its row converter and epilogue
+struct bmm_group : group { std::function<void(hipStream_t)> run; bool float_weights = false; };
 static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_group & grp) {
     const ggml_tensor * mm = an.g->nodes[pos];
     if (mm->op != GGML_OP_MUL_MAT) return false;
     const ggml_tensor * w0 = mm->src[0], * x1 = mm->src[1];
-    if (!is_qblock(w0->type) || !ggml_is_contiguous(w0) || w0->ne[2] != 1 || w0->ne[3] != 1) return false;
+    const bool fw = w0->type == GGML_TYPE_BF16 || w0->type == GGML_TYPE_F16;
+    if (!(is_qblock(w0->type) || fw) || !ggml_is_contiguous(w0) || w0->ne[2] != 1 || w0->ne[3] != 1) return false;
     if (x1->type != GGML_TYPE_F32 || !ggml_is_contiguous(x1) || mm->type != GGML_TYPE_F32 || !ggml_is_contiguous(mm) || mm->view_src) return false;
     const int64_t K = w0->ne[0], M = w0->ne[1], Tn = ggml_nelements(x1) / K;
-    if (!k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
+    if (fw ? !float_batched_ok(w0, Tn) : !k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
+    grp.float_weights = fw;
     grp.members.assign(1, pos);
     grp.emit_pos = pos;
     int prologue = MV_PLAIN;
@@ -1347,11 +1368,13 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
         }
     }
     for (int m : grp.members) if (m < 0) return false;
+    if (fw && (!aligned16(xp) || (alpha && !aligned16(alpha)))) return false;   // (x_cs is K or 2 K floats, K % 32 == 0: every row is then aligned)
     const char * wp = (const char *) w0->data;
     const int64_t rb = (int64_t) w0->nb[1];
-    void * ws = em.ws(k_mm_q4k_batched_ws_size(K, Tn));
+    void * ws = em.ws(fw ? k_mm_f_batched_ws_size(K, Tn) : k_mm_q4k_batched_ws_size(K, Tn));
     const int wt = (int) w0->type;
-    grp.run = [=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
+    if (fw) grp.run = [=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
+    else grp.run = [=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
     return true;
 }
 
@@ -2570,7 +2593,7 @@ static void pass_matvecs(planner & pl) {
         mv_group grp;
         if (!match_matvec(pl.an, i, grp)) {
             bmm_group bg;
-            if (!no_batched_fusion && match_batched_mm(pl.an, i, pl.em, bg) && claim_group(pl, bg, i)) pl.at_pos[bg.emit_pos].push_back(bg.run);
+            if (!no_batched_fusion && match_batched_mm(pl.an, i, pl.em, bg) && claim_group(pl, bg, i)) { pl.at_pos[bg.emit_pos].push_back(bg.run); pl.p->n_float_batched_mms += bg.float_weights; }
             continue;
         }
         if (!claim(pl, grp.members, i)) continue;
@@ -2965,6 +2988,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.ring_copy_launches_in_last_plan = p->n_ring_copy_launches; c->stats.ring_copy_jobs_in_last_plan = p->n_ring_copy_jobs;
     c->stats.attn_row_launches_in_last_plan = p->n_attn_row_launches; c->stats.attn_row_jobs_in_last_plan = p->n_attn_row_jobs; c->stats.attn_row_rows_in_last_plan = p->n_attn_row_rows;
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
+    c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

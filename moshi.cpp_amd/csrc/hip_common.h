@@ -162,6 +162,13 @@ bool k_mm_q4k_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
 void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
                       void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
 
+// the same for BF16 / F16 weights (K % 32 == 0, dense rows): rows rounded to the weight's type into `ws`, then 16x16x4 f64 MFMA tiles - exact products,
+// double accumulation, one rounding to float (ggml's generic BF16 / F16 product); all T <= 64 columns in one pass, a column's bits independent of T
+size_t k_mm_f_batched_ws_size(int64_t K, int64_t T);
+bool k_mm_f_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
+void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                    void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
+
 // streaming self-attention over a ring KV cache (T <= 4 new tokens): RoPE(q,k) -> cache write -> masked
 // softmax(K q) V restricted to un-masked slots; see hip_kernels_fused.hip
 struct attn_args {

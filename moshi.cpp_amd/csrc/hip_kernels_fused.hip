@@ -1529,6 +1529,30 @@ void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_byte
     }
 }
 
+// ---- the batched mat-mul for BF16 / F16 weights: double-accumulating f64 MFMA tiles (hip_mm_float.h) ------------------------------------------
+#include "hip_mm_float.h"
+size_t k_mm_f_batched_ws_size(int64_t K, int64_t T) { return (size_t) K * (size_t) T * 2; }
+bool k_mm_f_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) {
+    return (wtype == GGML_TYPE_BF16 || wtype == GGML_TYPE_F16) && K % 32 == 0 && T >= 2 && T <= 64 && M >= 16;
+}
+template <int WT>
+static void mm_f_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                         uint16_t * xa, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
+    const int64_t total8 = K * T / 8;
+    if (prologue == MV_RMSNORM) rms_cvt_rows_kernel<WT><<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, xa);
+    else if (prologue == MV_GATE_SILU) gate_cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
+    else cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
+    const int nch = (int) (K / 32), grid = (int) ((M + 15) / 16);
+#define MMF_LAUNCH(NT) mm_f_mfma_kernel<WT, NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, xa, y, y_cs, residual, r_cs)
+    if (T <= 16) MMF_LAUNCH(1); else if (T <= 32) MMF_LAUNCH(2); else if (T <= 48) MMF_LAUNCH(3); else MMF_LAUNCH(4);
+#undef MMF_LAUNCH
+}
+void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                    void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
+    if (wtype == GGML_TYPE_BF16) mm_f_batched<GGML_TYPE_BF16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
+    else mm_f_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
+}
+
 static mv_profile * g_mv_profile = nullptr;
 void k_matvec_set_profile(mv_profile * p) { g_mv_profile = p; }
 
