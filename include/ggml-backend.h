@@ -130,6 +130,7 @@ struct ggml_mi355x_stats {
     int64_t cross_block_launches_in_last_plan;  // k_cross_attn_blocks launches of the last plan (tts replay: the cross-attention of one layer of a pass) ...
     int64_t cross_block_jobs_in_last_plan;      // ... and the jobs they hold
     int64_t float_batched_mms_in_last_plan;     // k_mm_f_batched launches of the last plan (BF16 / F16 weights against 2..64 activation rows on f64 MFMA tiles)
+    int64_t float_acc_mms_in_last_plan;         // k_mm_f32acc_batched launches of the last plan (the same products on float-accumulating BF16 / F16 MFMA tiles, set_float_accumulate)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -164,6 +165,14 @@ GGML_API void ggml_backend_mi355x_set_capture(ggml_backend_t backend, int enable
 // graphs of more columns existed (those run their node chain, with the same tokens); a model of 17 .. 64 columns raises it to its width for the
 // handle it was created on. Values are clamped to 16 .. 64; plans made so far are kept. No-op on other backends.
 GGML_API void ggml_backend_mi355x_set_max_columns(ggml_backend_t backend, int n_columns);
+// How this handle multiplies BF16 / F16 weights by 2 .. 64 activation rows. 0 (a fresh handle): the f64-MFMA mat-mul, which keeps the generic product's
+// arithmetic (exact products, a double sum, one rounding) and is bound by the f64 matrix pipe. 1: the float-accumulating mat-mul
+// (v_mfma_f32_16x16x32_bf16 / _f16) - the same rounded activation rows and exact products, the sums in float: no longer bit-comparable with the CPU
+// product, still bit-reproducible and column-independent (a column's bits depend on K and its own values only). Single-column products, F32 weights
+// and block-quantised weights are untouched. A change of value drops the handle's cached plans; ggml_backend_mi355x_init_stream inherits the value.
+// The environment variable MI355X_MMF=2 (read once per process) makes 1 the starting value of every fresh handle; MI355X_MMF=0 keeps turning both
+// mat-muls off. No-op on other backends.
+GGML_API void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t backend, int mode);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 // Makes the backend's HIP device current on the calling thread. A caller that talks to another HIP-based library itself on this backend's stream (RCCL:

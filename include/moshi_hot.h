@@ -82,6 +82,16 @@ struct moshi_hot_config {
     // before wide batches existed keeps; 1 = up to MOSHI_HOT_MAX_STREAMS (64). A caller opts in because a column is not free: its K / V rings are
     // 2 x num_layers x dim x context BF16 values of device memory (1.57 GB at moshika's widths and context 3000). Nothing else depends on it.
     int32_t wide_streams;
+    // 1: moshi_hot_create / _create_streams / _create_slots / _create_from_gguf switch the handle the model is created on (and its codec sibling stream,
+    // if one is made) to the float-accumulating mat-mul, ggml_backend_mi355x_set_float_accumulate(backend, 1): every B-column product of BF16 / F16
+    // linears - streams and slots steps, moshi_hot_slots_prefill / _long, moshi_hot_slots_replay, the [dim, T] passes of moshi_hot_prefill - sums in
+    // float on the BF16 / F16 matrix unit instead of in double. Single-column products, F32 weights, the ring products and the codec stay where they
+    // are. Ignored on any other backend. The setting belongs to the HANDLE, as wide_streams' sampler width does: a model never lowers it, models
+    // created on the handle later run in this mode too, and a caller who wants both contracts in one process uses two handles.
+    // Contract with 1: a BF16 / F16 model is no longer bit-comparable with the CPU reference (sums of K exact products in float, not in double). It
+    // stays bit-reproducible (same inputs, same bits) and column-independent (the same conversation in any column of any B, prefilled in any chunk,
+    // gets the same bits); snapshots, prefill and replay continue bit for bit on the same backend and mode.
+    int32_t float_accumulate;
 };
 
 typedef struct moshi_hot_model moshi_hot_model_t;

@@ -62,7 +62,7 @@ class Stats(C.Structure):
                                          "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan",
                                          "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan",
                                          "cross_block_launches_in_last_plan", "cross_block_jobs_in_last_plan",
-                                         "float_batched_mms_in_last_plan")]
+                                         "float_batched_mms_in_last_plan", "float_acc_mms_in_last_plan")]
 
 
 class KernelProfile(C.Structure):
@@ -142,6 +142,7 @@ SIGNATURES = {
     "ggml_backend_tensor_memset": (None, [TP, C.c_uint8, Z, Z]), "ggml_backend_tensor_copy": (None, [TP, TP]),
     "ggml_backend_graph_compute": (I, [P, P]), "ggml_backend_supports_op": (B, [P, TP]),
     "ggml_backend_mi355x_get_stats": (None, [P, C.POINTER(Stats)]), "ggml_backend_mi355x_set_flags": (None, [P, I]), "ggml_backend_mi355x_set_capture": (None, [P, I]), "ggml_backend_mi355x_set_max_columns": (None, [P, I]),
+    "ggml_backend_mi355x_set_float_accumulate": (None, [P, I]),
     "ggml_backend_mi355x_get_stream": (P, [P]),
     "ggml_backend_mi355x_make_current": (None, [P]),
     "ggml_backend_mi355x_init_stream": (P, [P]),

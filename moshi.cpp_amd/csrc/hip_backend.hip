@@ -58,6 +58,7 @@ struct hip_ctx {
     hipStream_t stream = nullptr;
     int flags = 0;
     int max_columns = 16;        // ggml_backend_mi355x_set_max_columns: the widest B-column sampler graph planned as one launch
+    int float_acc = 0;           // ggml_backend_mi355x_set_float_accumulate: 1 = BF16 / F16 weights against 2..64 rows take the float-accumulating mat-mul
     bool no_capture = false;     // ggml_backend_mi355x_set_capture(.., 0): plans of repeated graphs are reused but not captured into hipGraphs
     ggml_mi355x_stats stats = {};
     // pooled allocations: size class -> free pointers
@@ -341,7 +342,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -537,9 +538,11 @@ struct emitter {
 
 static bool is_qblock(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0; }
 // BF16 / F16 weights against 2..64 activation rows: the f64-MFMA mat-mul (k_mm_f_batched). MI355X_MMF=0 sends them back to the generic product (the A/B of DESIGN.md 23)
-static bool float_batched_ok(const ggml_tensor * w, int64_t T) {
-    static const bool off = [] { const char * v = getenv("MI355X_MMF"); return v != nullptr && atoi(v) == 0; }();
-    return !off && w->data && (uintptr_t) w->data % 16 == 0 && w->nb[1] % 16 == 0 && k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
+// MI355X_MMF=2 makes the float-accumulating mat-mul (k_mm_f32acc_batched) the starting mode of every fresh handle
+static int mmf_env() { static const int v = [] { const char * e = getenv("MI355X_MMF"); return e ? atoi(e) : 1; }(); return v; }
+static bool float_batched_ok(const ggml_tensor * w, int64_t T, bool float_acc) {
+    if (mmf_env() == 0 || !w->data || (uintptr_t) w->data % 16 != 0 || w->nb[1] % 16 != 0) return false;
+    return float_acc ? k_mm_f32acc_batched_supported(w->type, w->ne[0], w->ne[1], T) : k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
 }
 // its row converters read the activation rows (and alpha) as float4
 static bool aligned16(const void * p) { return p != nullptr && (uintptr_t) p % 16 == 0; }
@@ -659,13 +662,13 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
                 }
                 // ... against BF16 / F16 weights: f64 MFMA tiles
                 if (!no_batched && x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) && ggml_is_contiguous(w0) &&
-                    w0->ne[2] == 1 && w0->ne[3] == 1 && aligned16(x1->data) && float_batched_ok(w0, Tn)) {
+                    w0->ne[2] == 1 && w0->ne[3] == 1 && aligned16(x1->data) && float_batched_ok(w0, Tn, em.c->float_acc != 0)) {
                     const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
                     const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
                     void * ws = em.ws(k_mm_f_batched_ws_size(K, Tn));
                     const int wt = (int) w0->type;
-                    em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); });
-                    em.p->n_float_batched_mms++;
+                    if (em.c->float_acc) { em.push([=](hipStream_t s) { k_mm_f32acc_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_acc_mms++; }
+                    else { em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_batched_mms++; }
                     return;
                 }
             }
@@ -1307,7 +1310,7 @@ static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & gr
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
 //     (alpha * rms_norm(x), or silu(h[:n]) * h[n:]) folded into its row quantiser and the residual add into its epilogue.
 //     BF16 / F16 weights: the f64-MFMA mat-mul with the same folds in its row converter and epilogue
-struct bmm_group : group { std::function<void(hipStream_t)> run; bool float_weights = false; };
+struct bmm_group : group { std::function<void(hipStream_t)> run; bool float_weights = false, float_acc = false; };
 static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_group & grp) {
     const ggml_tensor * mm = an.g->nodes[pos];
     if (mm->op != GGML_OP_MUL_MAT) return false;
@@ -1316,8 +1319,9 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
     if (!(is_qblock(w0->type) || fw) || !ggml_is_contiguous(w0) || w0->ne[2] != 1 || w0->ne[3] != 1) return false;
     if (x1->type != GGML_TYPE_F32 || !ggml_is_contiguous(x1) || mm->type != GGML_TYPE_F32 || !ggml_is_contiguous(mm) || mm->view_src) return false;
     const int64_t K = w0->ne[0], M = w0->ne[1], Tn = ggml_nelements(x1) / K;
-    if (fw ? !float_batched_ok(w0, Tn) : !k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
-    grp.float_weights = fw;
+    const bool facc = fw && em.c->float_acc != 0;
+    if (fw ? !float_batched_ok(w0, Tn, facc) : !k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
+    grp.float_weights = fw; grp.float_acc = facc;
     grp.members.assign(1, pos);
     grp.emit_pos = pos;
     int prologue = MV_PLAIN;
@@ -1373,7 +1377,8 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
     const int64_t rb = (int64_t) w0->nb[1];
     void * ws = em.ws(fw ? k_mm_f_batched_ws_size(K, Tn) : k_mm_q4k_batched_ws_size(K, Tn));
     const int wt = (int) w0->type;
-    if (fw) grp.run = [=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
+    if (facc) grp.run = [=](hipStream_t s) { k_mm_f32acc_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
+    else if (fw) grp.run = [=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
     else grp.run = [=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
     return true;
 }
@@ -2593,7 +2598,7 @@ static void pass_matvecs(planner & pl) {
         mv_group grp;
         if (!match_matvec(pl.an, i, grp)) {
             bmm_group bg;
-            if (!no_batched_fusion && match_batched_mm(pl.an, i, pl.em, bg) && claim_group(pl, bg, i)) { pl.at_pos[bg.emit_pos].push_back(bg.run); pl.p->n_float_batched_mms += bg.float_weights; }
+            if (!no_batched_fusion && match_batched_mm(pl.an, i, pl.em, bg) && claim_group(pl, bg, i)) { pl.at_pos[bg.emit_pos].push_back(bg.run); pl.p->n_float_batched_mms += bg.float_weights && !bg.float_acc; pl.p->n_float_acc_mms += bg.float_acc; }
             continue;
         }
         if (!claim(pl, grp.members, i)) continue;
@@ -2989,6 +2994,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.attn_row_launches_in_last_plan = p->n_attn_row_launches; c->stats.attn_row_jobs_in_last_plan = p->n_attn_row_jobs; c->stats.attn_row_rows_in_last_plan = p->n_attn_row_rows;
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
+    c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
@@ -3147,8 +3153,9 @@ static ggml_backend_t hip_dev_init(ggml_backend_dev_t d, const char *) {
     hip_ctx * c = (hip_ctx *) d->context;
     ctx_init_lazy(c);
     // a fresh backend handle starts from default flags, the default sampler width and zeroed counters (the device context is shared)
-    if (c->flags != 0 || c->max_columns != 16) {
-        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16;
+    const int float_acc0 = mmf_env() == 2 ? 1 : 0;   // MI355X_MMF=2: the float-accumulating mat-mul from the start
+    if (c->flags != 0 || c->max_columns != 16 || c->float_acc != float_acc0) {
+        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16; c->float_acc = float_acc0;
     }
     c->stats = {};
     auto * b = new ggml_backend;
@@ -3197,6 +3204,16 @@ extern "C" void ggml_backend_mi355x_set_capture(ggml_backend_t b, int enabled) {
 extern "C" void ggml_backend_mi355x_set_max_columns(ggml_backend_t b, int n) {
     if (b && b->iface.get_name == hip_backend_name) { hip_ctx * c = (hip_ctx *) b->context; n = n < 16 ? 16 : n > SAMPLE_MAX_B ? SAMPLE_MAX_B : n; if (n > c->max_columns) c->max_columns = n; }
 }
+extern "C" void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t b, int mode) {
+    if (!b || b->iface.get_name != hip_backend_name) return;   // any other backend: nothing to do
+    hip_ctx * c = (hip_ctx *) b->context;
+    mode = mode ? 1 : 0;
+    if (mode == c->float_acc) return;
+    if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
+    for (auto & kv : c->plans) plan_free(c, kv.second);   // the plans hold the other kernel's launches
+    c->plans.clear();
+    c->float_acc = mode;
+}
 extern "C" void ggml_backend_mi355x_set_flags(ggml_backend_t b, int flags) {
     hip_ctx * c = ctx_of(b);
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
@@ -3235,5 +3252,6 @@ extern "C" ggml_backend_t ggml_backend_mi355x_init_stream(ggml_backend_t base) {
     c->flags = b0->flags;             // the debug flags in force on `base` (no fusion / no hipGraph / ...) apply to its sibling stream too
     c->no_capture = b0->no_capture;
     c->max_columns = b0->max_columns;
+    c->float_acc = b0->float_acc;     // (a fresh handle holds no plans yet)
     return b;
 }

@@ -168,6 +168,11 @@ size_t k_mm_f_batched_ws_size(int64_t K, int64_t T);
 bool k_mm_f_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
 void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
                     void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
+// the opt-in float-accumulating form (ggml_backend_mi355x_set_float_accumulate): the same rows, workspace (k_mm_f_batched_ws_size) and folds, the sums
+// in float on 16x16x32 BF16 / F16 MFMA tiles - not bit-comparable with the generic product, a column's bits still independent of T and its neighbours
+bool k_mm_f32acc_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
+void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                         void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
 
 // streaming self-attention over a ring KV cache (T <= 4 new tokens): RoPE(q,k) -> cache write -> masked
 // softmax(K q) V restricted to un-masked slots; see hip_kernels_fused.hip

@@ -1553,6 +1553,27 @@ void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes,
     else mm_f_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
 }
 
+// ---- the same product with float sums: v_mfma_f32_16x16x32_bf16 / _f16 tiles (hip_mm_float_acc.h); the row converters and the workspace are shared ----
+#include "hip_mm_float_acc.h"
+bool k_mm_f32acc_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) { return k_mm_f_batched_supported(wtype, K, M, T); }
+template <int WT>
+static void mm_f32acc_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                              uint16_t * xa, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
+    const int64_t total8 = K * T / 8;
+    if (prologue == MV_RMSNORM) rms_cvt_rows_kernel<WT><<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, xa);
+    else if (prologue == MV_GATE_SILU) gate_cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
+    else cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
+    const int nch = (int) (K / 32), grid = (int) ((M + 15) / 16);
+#define MMA_LAUNCH(NT) mm_f32acc_mfma_kernel<WT, NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, xa, y, y_cs, residual, r_cs)
+    if (T <= 16) MMA_LAUNCH(1); else if (T <= 32) MMA_LAUNCH(2); else if (T <= 48) MMA_LAUNCH(3); else MMA_LAUNCH(4);
+#undef MMA_LAUNCH
+}
+void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                         void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
+    if (wtype == GGML_TYPE_BF16) mm_f32acc_batched<GGML_TYPE_BF16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
+    else mm_f32acc_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
+}
+
 static mv_profile * g_mv_profile = nullptr;
 void k_matvec_set_profile(mv_profile * p) { g_mv_profile = p; }
 

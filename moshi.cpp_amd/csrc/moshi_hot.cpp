@@ -1382,6 +1382,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     m->n_streams = n_streams;
     m->kind = kind;   // (build_temporal_graph reads it)
     if (n_streams > MOSHI_HOT_DEFAULT_MAX_STREAMS) ggml_backend_mi355x_set_max_columns(backend, n_streams);   // its samplers stay one launch per site
+    if (cfg->float_accumulate) ggml_backend_mi355x_set_float_accumulate(backend, 1);   // the handle's setting (a sibling stream inherits it); never lowered here
     m->sampling.assign((size_t) n_streams, { { 0, cfg->temp, cfg->temp_text, cfg->top_k, cfg->top_k_text }, false });
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
