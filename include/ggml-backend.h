@@ -156,7 +156,9 @@ GGML_API void ggml_backend_mi355x_get_kernel_profile(ggml_backend_t backend, str
 // 32 = persistent chain launches on even when the MI355X_CHAIN environment variable says 0 (default: on),
 // 64 = every codec convolution keeps its im2col launch (default: the launch producing a convolution's input also writes its F16 im2col panel),
 // 512 = the Temporal attention stays a launch of its own (default: it runs as the tail of its in_proj launch, inproj_attn_kernel),
-// 1024 = chain launches always take the descriptor-driven kernel (default: the Depth transformer's steps run as a compile-time step program)
+// 1024 = chain launches always take the descriptor-driven kernel (default: the Depth transformer's steps run as a compile-time step program),
+// 2048 = the attention tail of inproj_attn_kernel keeps its general body at every live length (default: heads with at most 128 live ring slots take the
+//        short-ring form, which computes the same bits; the MI355X_ATTN_SHORT_TAIL=0 environment switch does the same for every handle)
 GGML_API void ggml_backend_mi355x_set_flags(ggml_backend_t backend, int flags);
 // hipGraph capture of repeated graphs on / off without touching cached plans (off: a repeated graph still reuses its plan, launched eagerly -
 // for sequences of same-shaped one-off graphs such as prompt-prefill chunks, where a capture costs more than it saves). No-op on other backends.

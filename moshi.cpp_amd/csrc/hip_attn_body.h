@@ -62,14 +62,128 @@ struct attn_gout { unsigned long long * out; unsigned tag; int64_t ts;      // g
 #else
 #define R256_STAMP(i) do {} while (0)
 #endif
+// ---- the short-ring form of the merged launch's tail (inproj_attn_kernel: D = 128, T = 1, AT_GQKV, 8 waves, one workgroup per head) -----------------------
+// Entered by attn_decode_body - block-uniformly, behind the barrier that publishes the rotated q and the new k / v rows in LDS - when the head's live range
+// n_end is at most ATTN_SHORT_MAX = ATTN_NPRE x 8 waves x 4 slots: every K / V row it needs was requested at kernel entry (pass pi of wave w holds slot
+// 4 w + 32 pi + sub), and the mask row was scanned and staged in LDS BEFORE the granules were polled (mpre: the mask values of the own slots, -inf beyond
+// n_end). What is left behind the hand-off has fixed trip counts and two more LDS-only barriers (scores -> statistics, partial outputs -> sum); no barrier
+// waits for the ring store. Measured (profiles/r12_frame_stamps_in_graph.txt): the dependent chain 3.16 -> 2.56 us, the launch 14.9 -> 13.5 us.
+// The numbers are the general body's at 8 waves, bit for bit:
+//  * scores: the same float products summed in double over a slot's 16 lanes (group_allsum_f64), scaled, masked;
+//  * maximum: order-free; every wave takes it from the scores in LDS;
+//  * sum of the exponentials: the general body's thread c holds e[c] alone (n_end <= 512), sums a wave's 64 with wave_allsum_f64 and adds the waves in
+//    index order - here every wave forms the same two wave sums (slots 0 .. 63, 64 .. 127) itself and adds them; waves 2 .. 7 contribute 0.0 there;
+//  * p = bf16(e * float(1 / sum)): a lane takes the e of its four slots from the lanes that hold them (ds_bpermute) - the same expf results;
+//  * P x V: per (wave, slot group) over the passes in order in double, then the 32 groups in index order by the thread that owns the dim.
+// The slot written this step comes from LDS (last writer wins), packed by the one wave that owns it.
+#define ATTN_SHORT_MAX 128
+template <int NW = 8>
+__device__ __forceinline__ void attn_short_tail(const attn_args & a_in, const int h, const int n_end, const int slot, uint4 (&kpre)[ATTN_NPRE], uint4 (&vpre)[ATTN_NPRE],
+                                                const float (&mpre)[ATTN_NPRE], float * sc, const float * qf, const float * knew, const float * vnew, double * red,
+                                                unsigned at_log_id) {
+    constexpr int D = 128, SPW = 4, NPRE = ATTN_NPRE;
+    static_assert(NW == 8 && NPRE * NW * SPW == ATTN_SHORT_MAX, "the passes requested at entry cover the short form's slots");
+    const attn_args & a = a_in;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = lane >> 4, dl = (lane & 15) * 8;
+    float qv[8];
+    {
+        const float4 lo = *(const float4 *) (qf + dl), hi = *(const float4 *) (qf + dl + 4);
+        qv[0] = lo.x; qv[1] = lo.y; qv[2] = lo.z; qv[3] = lo.w; qv[4] = hi.x; qv[5] = hi.y; qv[6] = hi.z; qv[7] = hi.w;
+    }
+    if (slot >= 0 && slot < ATTN_SHORT_MAX && ((slot >> 2) & (NW - 1)) == wave) {   // (wave-uniform: slot 4 w + 32 pi + sub belongs to wave w)
+        // knew / vnew hold bf2f(f2bf(x)): the low 16 bits are zero and a NaN already carries f2bf's quiet bit, so f2bf of such a float is its high half -
+        // the general body's pack_row without the sixteen roundings
+        auto pack_row = [&](const float * src) {
+            const float4 lo = *(const float4 *) src, hi = *(const float4 *) (src + 4);
+            auto pair = [](float x, float y) { return (__float_as_uint(x) >> 16) | (__float_as_uint(y) & 0xffff0000u); };
+            uint4 r;
+            r.x = pair(lo.x, lo.y); r.y = pair(lo.z, lo.w); r.z = pair(hi.x, hi.y); r.w = pair(hi.z, hi.w);
+            return r;
+        };
+        const uint4 kf = pack_row(knew + dl), vf = pack_row(vnew + dl);
+        const bool mine = sub == (slot & 3);
+#pragma unroll
+        for (int pi = 0; pi < NPRE; pi++) if (pi == (slot >> 5) && mine) { kpre[pi] = kf; vpre[pi] = vf; }
+    }
+    AT_STAMP(8);
+    // scores of the own slots -> LDS
+#pragma unroll
+    for (int pi = 0; pi < NPRE; pi++) {
+        const int c0 = wave * SPW + pi * NW * SPW, c = c0 + sub;
+        if (c0 < n_end) {
+            const float m = mpre[pi];
+            const uint32_t kw[4] = { kpre[pi].x, kpre[pi].y, kpre[pi].z, kpre[pi].w };
+            double acc = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                acc += (double) (bf2f((uint16_t) (kw[i] & 0xffff)) * qv[2 * i]);
+                acc += (double) (bf2f((uint16_t) (kw[i] >> 16)) * qv[2 * i + 1]);
+            }
+            acc = group_allsum_f64(acc, 16);
+            if (c < n_end && (lane & 15) == 0) sc[c] = m > -INFINITY ? (float) acc * a.scale + m : -INFINITY;
+        }
+    }
+    AT_STAMP(10);
+    lds_barrier();
+    AT_STAMP(3);
+    // soft_max statistics, by every wave for itself
+    const float s0 = lane < n_end ? sc[lane] : -INFINITY, s1 = lane + 64 < n_end ? sc[lane + 64] : -INFINITY;
+    const float gmax = wave_allmax_f32(fmaxf(s0, s1));
+    const float e0 = s0 > -INFINITY ? expf(s0 - gmax) : 0.f, e1 = s1 > -INFINITY ? expf(s1 - gmax) : 0.f;
+    const double sum0 = wave_allsum_f64((double) e0), sum1 = wave_allsum_f64((double) e1);   // (two independent chains: they interleave)
+    const float inv = (float) (1.0 / (sum0 + sum1));
+    const int src_lane = (wave * SPW + sub) * 4;   // byte address of lane 4 w + sub (slots 4 w + sub and + 64); + 128: lane + 32 (slots + 32 and + 96)
+    const float ev[NPRE] = { __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(e0))), __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane + 128, __float_as_int(e0))),
+                             __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(e1))), __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane + 128, __float_as_int(e1))) };
+    AT_STAMP(4);
+    // P x V of the own slots
+    double o8[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) o8[i] = 0;
+#pragma unroll
+    for (int pi = 0; pi < NPRE; pi++) {
+        const int c0 = wave * SPW + pi * NW * SPW, c = c0 + sub;
+        if (c0 < n_end) {
+            const float p = c < n_end ? bf2f(f2bf(ev[pi] * inv)) : 0.f;
+            const uint32_t vw[4] = { vpre[pi].x, vpre[pi].y, vpre[pi].z, vpre[pi].w };
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                o8[2 * i]     += (double) (bf2f((uint16_t) (vw[i] & 0xffff)) * p);
+                o8[2 * i + 1] += (double) (bf2f((uint16_t) (vw[i] >> 16)) * p);
+            }
+        }
+    }
+    AT_STAMP(5);
+    {
+        double * dst = red + (wave * SPW + sub) * D + dl;
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) *(double2 *) (dst + i) = make_double2(o8[i], o8[i + 1]);
+    }
+    lds_barrier();
+    AT_STAMP(6);
+    if (tid < D) {
+        double g[NW * SPW];
+#pragma unroll
+        for (int i = 0; i < NW * SPW; i++) g[i] = red[i * D + tid];
+        double tot = 0;
+#pragma unroll
+        for (int i = 0; i < NW * SPW; i++) tot += g[i];   // fixed order: wave-major, slot group minor
+        a.out[(int64_t) h * D + tid] = (float) tot;
+    }
+    AT_STAMP(7);
+}
+
 template <bool SPLIT, int NWA, int MODE>
 __device__ __forceinline__ void attn_decode_body(const attn_args & a_in, const attn_split_ws & w, char * smem, const int h, const int s_idx, const int group_y,
                                                  const unsigned gtag = 0u, const attn_gqkv gq = attn_gqkv(), const attn_gout go = attn_gout()) {
     constexpr bool GQKV = (MODE & AT_GQKV) != 0, GOUT = (MODE & AT_GOUT) != 0;
     constexpr int ATTN_NW = NWA, ATTN_THREADS = NWA * 64;
-#if defined(MV_LOG)
-    unsigned at_log_id = 0;
-#endif
+    // EARLY (the merged launch's tail): the live-length scan runs BEFORE the granules are polled - the mask row is requested ahead of the ring rows and
+    // vector loads return in order, so a counted wait for the mask alone stages the row in LDS and leaves every wave's last live slot there while the
+    // workgroup would otherwise spin; behind the hand-off only RoPE -> LDS -> one barrier is left, which publishes n_end together with the new rows.
+    // No barrier sits between the poll and a store its producers wait for: producers never wait for consumers.
+    constexpr bool EARLY = MODE == AT_GQKV;
+    unsigned at_log_id = 0;   // (the stamped build's record of this launch)
     AT_STAMP(0);
     attn_args a = a_in;
     if (!SPLIT && a.n_groups > 1) {   // rows 4 g .. 4 g + 3 of a longer block
@@ -212,6 +326,32 @@ __device__ __forceinline__ void attn_decode_body(const attn_args & a_in, const a
         kpre[pi] = *(const uint4 *) (kc + (int64_t) cc * a.k_nb1 + dl * 2);
         if (pi < ATTN_NPRE) vpre[pi] = *(const uint4 *) (vc + (int64_t) cc * a.v_nb1 + dl * 2);   // later V passes: after the scores (registers)
     }
+    // the live range's end, from the mask row (requested first: looked at with the ring rows still in flight)
+    int last_live = -1;
+    auto scan_entry = [&]() {
+        if (scan_fast) {
+            const int row4 = C / 4, n4 = T * row4;
+#pragma unroll
+            for (int u = 0; u < 3; u++) {
+                const int e = tid + u * ATTN_THREADS;
+                if (e < n4) {
+                    ((float4 *) msk)[e] = m4pre[u];
+                    const int i4 = e % row4;
+                    const int hi = m4pre[u].w > -INFINITY ? 3 : m4pre[u].z > -INFINITY ? 2 : m4pre[u].y > -INFINITY ? 1 : m4pre[u].x > -INFINITY ? 0 : -1;
+                    if (hi >= 0) last_live = max(last_live, i4 * 4 + hi);
+                }
+            }
+        } else if (!SPLIT || s_idx == 0) last_live = scan_last_live(0);
+    };
+    // the short-ring form is possible at all (block-uniform, known at entry): the merged launch's shape and the host's switch
+    const bool short_possible = EARLY && NWA == 8 && a.short_tail != 0 && s_idx == 0 && D == 128 && T == 1 && (C & 3) == 0;
+    if (EARLY) {
+        __builtin_amdgcn_sched_barrier(0);
+        scan_entry();   // (sh_slot is not staged here: nothing reads it, and its index load would wait for the ring rows in front of the reduction)
+        // the waves' maxima go to LDS now; the barrier that publishes the new rows behind the poll publishes them too - no barrier of their own
+        if (!SPLIT || s_idx == 0) { const int v = wave_allmax_i32(last_live); if (lane == 0) sh_i[wave] = v; }
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if (GQKV) {
         // the new rows, from the granules their producers publish (requested behind the ring rows: everything above is in flight while this polls)
 #pragma unroll
@@ -241,25 +381,12 @@ __device__ __forceinline__ void attn_decode_body(const attn_args & a_in, const a
             }
         }
     }
-    int last_live = -1;
-    if (scan_fast) {
-        const int row4 = C / 4, n4 = T * row4;
-#pragma unroll
-        for (int u = 0; u < 3; u++) {
-            const int e = tid + u * ATTN_THREADS;
-            if (e < n4) {
-                ((float4 *) msk)[e] = m4pre[u];
-                const int i4 = e % row4;
-                const int hi = m4pre[u].w > -INFINITY ? 3 : m4pre[u].z > -INFINITY ? 2 : m4pre[u].y > -INFINITY ? 1 : m4pre[u].x > -INFINITY ? 0 : -1;
-                if (hi >= 0) last_live = max(last_live, i4 * 4 + hi);
-            }
-        }
-    } else if (!SPLIT || s_idx == 0) last_live = scan_last_live(0);
+    if (!EARLY) scan_entry();
     __builtin_amdgcn_sched_barrier(0);
-    AT_STAMP(1);
+    AT_STAMP(1);   // (EARLY: the granules are in - the wait ends, the dependent chain starts)
 
     // ---- 1. RoPE + cache write for all T new rows (the reference's set_rows precede the attention of every row) ----------------
-    if (tid < T) sh_slot[tid] = a.index[tid];
+    if (!EARLY && tid < T) sh_slot[tid] = a.index[tid];
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         const int e = tid + u * ATTN_THREADS;
@@ -282,7 +409,29 @@ __device__ __forceinline__ void attn_decode_body(const attn_args & a_in, const a
         }
     }
     if (!SPLIT && a.write_only) return;
-    if (!SPLIT || s_idx == 0) { n_end = block_max_i32(last_live) + 1; if (SPLIT && n_end > w.big_min) SLOTS *= 2; }
+    (void) at_log_id;
+    if (EARLY) {   // the scan ran before the poll: one barrier publishes qf / knew / vnew, the staged mask row and the waves' maxima
+        if (!SPLIT || s_idx == 0) {
+            if (short_possible) lds_barrier(); else __syncthreads();   // (LDS only: the form must not wait for the ring store, and the general body does not need to)
+            int r_ = sh_i[0];
+#pragma unroll
+            for (int w_ = 1; w_ < ATTN_NW; w_++) r_ = max(r_, sh_i[w_]);
+            n_end = __builtin_amdgcn_readfirstlane(r_) + 1;   // (the same in every thread)
+            if (SPLIT && n_end > w.big_min) SLOTS *= 2;
+            if constexpr (NWA == 8) {
+                if (short_possible && n_end <= ATTN_SHORT_MAX && !(SPLIT && n_end > w.single_max)) {
+                    float mpre[NPRE];   // mask values of this lane's slots, -inf beyond the live range (read unconditionally, selected afterwards: no LDS read behind a per-lane branch)
+#pragma unroll
+                    for (int pi = 0; pi < NPRE; pi++) { const int c = wave * 4 + pi * NWA * 4 + (lane >> 4); mpre[pi] = msk[c < C ? c : C - 1]; }
+#pragma unroll
+                    for (int pi = 0; pi < NPRE; pi++) { const int c = wave * 4 + pi * NWA * 4 + (lane >> 4); mpre[pi] = c < n_end ? mpre[pi] : -INFINITY; }
+                    AT_STAMP(2);
+                    attn_short_tail<NWA>(a, h, n_end, slot_t[0], kpre, vpre, mpre, sc, qf, knew, vnew, red, at_log_id);
+                    return;
+                }
+            }
+        } else __syncthreads();
+    } else if (!SPLIT || s_idx == 0) { n_end = block_max_i32(last_live) + 1; if (SPLIT && n_end > w.big_min) SLOTS *= 2; }
     else __syncthreads();
     AT_STAMP(2);
     const int P = SPLIT && n_end > w.single_max ? (n_end + SLOTS - 1) / SLOTS : 1;   // participating workgroups of this head

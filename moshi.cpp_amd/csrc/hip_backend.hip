@@ -2517,7 +2517,8 @@ static bool merge_inproj_attention(planner & pl, int i, const mv_group & grp, co
             if (std::find(ag.members.begin(), ag.members.end(), j) == ag.members.end()) private_y = false;
         }
         if (!private_y || !spin_kernels_allowed(c)) continue;
-        const mv_args am = a; const attn_args aa = at;
+        const mv_args am = a; attn_args aa = at;
+        aa.short_tail = k_attn_short_tail_default() && !(c->flags & 2048);
         unsigned * err = c->err_dev;
         const size_t wn = k_inproj_attn_ws_size(a, at);
         void * ws = pl.em.ws(wn);

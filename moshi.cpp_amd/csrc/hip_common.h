@@ -196,7 +196,12 @@ struct attn_args {
     // Every workgroup rotates ALL T new rows (its scores of a later row need the earlier rows' K / V, which it takes from its own LDS, never from the
     // ring); only the workgroup of row 0 writes the ring. The two rows' score -> soft_max -> P x V chains then run side by side instead of back to back.
     int row_split;
+    // the merged in_proj + attention launch only (k_inproj_attn): 1 lets a head whose live range is at most ATTN_SHORT_MAX slots take the short-ring form
+    // of the tail (attn_short_tail, hip_attn_body.h: the general body's numbers in its summation order), 0 keeps the general body at every live length.
+    // Set by the planner from k_attn_short_tail_default() and backend flag 2048; every other launch leaves it 0.
+    int short_tail;
 };
+bool k_attn_short_tail_default();   // MI355X_ATTN_SHORT_TAIL (default 1), read once
 // Long rings (C >= ATTN_SPLIT_MIN_C, T = 1) are split over ceil(C / ATTN_SPLIT_SLOTS) workgroups per head; `ws` (zeroed once,
 // k_attn_decode_ws_size bytes) carries scores, partial outputs and the per-head arrival counters between them. ws may be NULL
 // for short rings.

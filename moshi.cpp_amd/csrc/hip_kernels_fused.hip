@@ -2044,6 +2044,8 @@ extern "C" __attribute__((visibility("default"))) int mi355x_fold_log_read(unsig
 #define FD_STAMP(i) do {} while (0)
 #endif
 
+// A/B switch of the short-ring form of the merged launch's attention tail (attn_short_tail): MI355X_ATTN_SHORT_TAIL=0 keeps the general body everywhere
+bool k_attn_short_tail_default() { static const int on = env_int("MI355X_ATTN_SHORT_TAIL", 1); return on != 0; }
 static int fold_split_S(const attn_args & at) { return FOLD_GRID / at.H; }
 // may the attention stage split a head over its S parts? (the 8-wave split geometry: ranges of `slots` up to big_min live slots, twice that beyond)
 static bool fold_use_split(const attn_args & at) {
