@@ -131,6 +131,8 @@ struct ggml_mi355x_stats {
     int64_t cross_block_jobs_in_last_plan;      // ... and the jobs they hold
     int64_t float_batched_mms_in_last_plan;     // k_mm_f_batched launches of the last plan (BF16 / F16 weights against 2..64 activation rows on f64 MFMA tiles)
     int64_t float_acc_mms_in_last_plan;         // k_mm_f32acc_batched launches of the last plan (the same products on float-accumulating BF16 / F16 MFMA tiles, set_float_accumulate)
+    int64_t pass_input_launches_in_last_plan;   // k_pass_input launches of the last plan (persona passes: the voice rows and embedding sums of a [dim, T] input in one launch) ...
+    int64_t pass_input_rows_in_last_plan;       // ... and the rows they write
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -159,6 +161,7 @@ GGML_API void ggml_backend_mi355x_get_kernel_profile(ggml_backend_t backend, str
 // 1024 = chain launches always take the descriptor-driven kernel (default: the Depth transformer's steps run as a compile-time step program),
 // 2048 = the attention tail of inproj_attn_kernel keeps its general body at every live length (default: heads with at most 128 live ring slots take the
 //        short-ring form, which computes the same bits; the MI355X_ATTN_SHORT_TAIL=0 environment switch does the same for every handle)
+// 4096 = the input of a persona pass stays its plain nodes (default: one k_pass_input launch for the whole concat chain; same bits either way)
 GGML_API void ggml_backend_mi355x_set_flags(ggml_backend_t backend, int flags);
 // hipGraph capture of repeated graphs on / off without touching cached plans (off: a repeated graph still reuses its plan, launched eagerly -
 // for sequences of same-shaped one-off graphs such as prompt-prefill chunks, where a capture costs more than it saves). No-op on other backends.

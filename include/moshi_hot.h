@@ -82,6 +82,10 @@ struct moshi_hot_config {
     // before wide batches existed keeps; 1 = up to MOSHI_HOT_MAX_STREAMS (64). A caller opts in because a column is not free: its K / V rings are
     // 2 x num_layers x dim x context BF16 values of device memory (1.57 GB at moshika's widths and context 3000). Nothing else depends on it.
     int32_t wide_streams;
+    // moshi_hot_create_streams / moshi_hot_create_slots with personaplex = 1: 0 = NULL for B > 1, as before PersonaPlex columns existed; 1 = the PersonaPlex
+    // shape of a B > 1 model ("PersonaPlex streams and slots" below). 1 without personaplex = 1, or beside anything the moshika shape excludes: NULL.
+    // Ignored by a single-stream model. (It sits in front of float_accumulate, which tests/test_float_acc_streams_gpu.py pins as the struct's last field.)
+    int32_t persona_columns;
     // 1: moshi_hot_create / _create_streams / _create_slots / _create_from_gguf switch the handle the model is created on (and its codec sibling stream,
     // if one is made) to the float-accumulating mat-mul, ggml_backend_mi355x_set_float_accumulate(backend, 1): every B-column product of BF16 / F16
     // linears - streams and slots steps, moshi_hot_slots_prefill / _long, moshi_hot_slots_replay, the [dim, T] passes of moshi_hot_prefill - sums in
@@ -114,7 +118,7 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 // model and a slots model (below) are this one model and step alike; they differ only in where a column's position comes from. Here every column
 // is open from creation and all B share one stream position, so the mask row, the RoPE phase and the ring slot are common.
 // n_streams == 1 builds exactly moshi_hot_create's model.
-// n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0, tp_world == 0, dep_shard_world <= 1, depth_only == 0,
+// n_streams > 1 takes the LM alone: enable_lm = 1 with both codec halves off, personaplex = 0 (or persona_columns = 1 beside it), tp_world == 0, dep_shard_world <= 1, depth_only == 0,
 // chain_depth == 0, codec_stream == 0, and 1 <= n_streams <= 16 (wide_streams = 1: <= MOSHI_HOT_MAX_STREAMS), in one of three shapes (demux / cross-attention / condition_sum / low-rank embeddings /
 // weight schedule / delay_steps: on the tts shape only, see "tts streams and slots" below):
 //  * the moshika shape: dep_q > 0, n_q > dep_q, extra_heads == 0;
@@ -123,6 +127,8 @@ GGML_API void moshi_hot_free(moshi_hot_model_t * m);
 //    A frame takes n_q codes per column, out_audio is not touched and may be NULL, the frame's only sampler site is 0 (the text head), and the
 //    heads' probabilities of every column are computed by the Temporal graph itself and read back with the tokens (moshi_hot_last_heads).
 //  * the tts shape (moshi-tts): dep_q > 0, n_q == dep_q, extra_heads == 0.
+//  * the PersonaPlex shape (personaplex = 1 AND persona_columns = 1; personaplex = 1 alone keeps returning NULL): dep_q >= 8, n_q >= dep_q, n_q > 8,
+//    extra_heads == 0 - see "PersonaPlex streams and slots" below.
 // Anything else returns NULL, and so does a B > 1 model whose state (chiefly the K / V rings: 2 x layers x dim x context BF16 values per column, 1.57 GB
 // at moshika's widths and context 3000) cannot be allocated on the device: nothing is left behind, the caller may ask for fewer columns.
 // On such a model moshi_hot_read_last("text_logits" | "transformer_out" | "dep_logits<k>") returns B consecutive rows (stream 0 first), and
@@ -266,6 +272,41 @@ GGML_API int     moshi_hot_slot_fork_full(moshi_hot_model_t * m, int src, int ds
 GGML_API int64_t moshi_hot_slot_save_full(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes);
 GGML_API int     moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes);
 
+// ---- PersonaPlex streams and slots: B PersonaPlex conversations, personas admitted in batched passes -----------------------------------------------
+// The PersonaPlex shape of a B > 1 model (personaplex = 1 and persona_columns = 1, the LM alone, no tts flag, no extra heads, no tensor parallelism, Depth
+// shard, chain_depth or codec_stream). The Depth graph chains all dep_q (16) steps per column; the frame protocol is the single-stream one per column
+// (lm.h:802-805): moshi_hot_lm_step_streams / _slots take B x 8 codes of the other speakers (in_audio, stream-major) and write B x 8 codes (out_audio),
+// the delay ring is one row deeper (lm.h:728) and takes all 16 raw samples. moshi_hot_slot_last_raw returns n_q + 1 tokens as on every slots model.
+// moshi_hot_slots_prefill / _long, moshi_hot_slot_hold and moshi_hot_slot_fork / _save / _load work as on the moshika shape (the blob's fingerprint
+// mixes the flag in: a moshika-shaped blob is refused here and the other way round); moshi_hot_slots_replay is the tts shape's and refuses; the _full snapshot calls are the plain calls here, as on every shape but the tts one.
+//
+// A conversation starts with a PERSONA (moshi_lmgen_step_system_prompts, lm.h:1120-1134): n_voice voice-prompt frames whose Temporal input is a
+// precomputed embedding (lm.h:1004-1036), the voice's image of the delay ring (lm.h:1038-1052), `silence` silence frames, the text prompt, `silence`
+// silence frames - a few hundred frames. moshi_hot_slots_persona runs them as batched [dim, T] passes:
+struct moshi_hot_persona {
+    const void * voice; int32_t voice_type; int32_t n_voice;   // n_voice rows of [dim] values, GGML_TYPE_F32 / BF16 / F16 (lm.h:1016 casts to F32); NULL / 0: none
+    const int32_t * prompt_cache;                               // moshi_hot_host_ring's layout, rows x (n_q + 1); NULL: the ring stays as it is (lm.h:1038-1052)
+    const int32_t * text_prompt; int32_t n_text;                // lm.h:1079-1098
+    int32_t silence;                                            // frames of moshi_lmgen_step_audio_silence before and after the text prompt (the tool: 6); 0: none
+};
+// Job j advances open slot slots[j] by n_voice + silence + n_text + silence rows, in that order. A voice row's Temporal input is row t of the voice,
+// exactly converted to F32; on the host it advances the frame count and the stream position only (nothing enters the delay ring). After the last voice
+// row prompt_cache, if given, replaces the delay ring's rows (the frame count stays; a persona without voice rows takes it ahead of its first row, and one
+// with no rows at all still takes it: the call then changes that slot's delay ring and counts 0 rows for it). The other rows are the provided frames that
+// moshi_hot_personaplex_system_prompts steps: PROMPT_TOKENS, the text replaced on the text-prompt rows. No Depth graph runs and no sampler noise is
+// drawn (the single-stream calls compute and discard both). The rows of all jobs go end to end into passes of at most `chunk` rows (< 1 or > 64: 64),
+// cut as moshi_hot_slots_prefill cuts them; a job's piece of a pass is one attention sequence whatever its rows are. Afterwards the slot is what a
+// fresh single-stream PersonaPlex model is after n_voice x moshi_hot_lm_step_embedding, moshi_hot_set_host_ring(prompt_cache) and
+// moshi_hot_personaplex_system_prompts (with `silence` = 6): delay ring, frame count, stream position, its column's rows of every Temporal K / V ring
+// and its row of transformer_out - on the oracle, greedy, the frames that follow are that model's bit for bit, for every chunk and any number of jobs
+// per pass. moshi_hot_slot_hold works between calls as for prefill. Returns the number of rows, or -1 with nothing changed: a model that is not a
+// PersonaPlex-shaped slots model, n_jobs > B, a bad, closed or repeated slot, a bad persona (a negative count, a count without its pointer, a voice
+// type other than the three), or position + rows > context (a persona that passes the ring's end is not supported).
+GGML_API int moshi_hot_slots_persona(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const struct moshi_hot_persona * personas, int chunk);
+GGML_API int moshi_hot_slot_persona(moshi_hot_model_t * m, int b, const struct moshi_hot_persona * persona, int chunk);   // one job
+// Persona caching: a persona costs a few passes once - admit it into a spare slot, moshi_hot_slot_save the slot, and moshi_hot_slot_load the blob into a
+// closed slot for every caller that wants that persona (one copy of the ring rows instead of the passes).
+
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute
 // (src/context.h:456-480, moshi/utils/sampling.h:4-64). By default that noise comes from libc rand() in one sweep over the whole [k, B] tensor, so a
@@ -377,6 +418,9 @@ GGML_API moshi_hot_model_t * moshi_hot_create_from_gguf(ggml_backend_t backend, 
 GGML_API int     moshi_hot_tensor_file_name(const char * checkpoint_name, char * out, int n);
 // test hook: the host-side delay ring (rows x (n_q + 1) int32, row-major) -> dst; returns the value count (dst NULL: just the count)
 GGML_API int     moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max_values);
+// the inverse: the host-side delay ring <- rows (n_values = moshi_hot_host_ring's count), the frame count unchanged: what a single-stream model needs to
+// take a voice's ring image (lm.h:1038-1052). Single-stream only. Returns 0, or -1 (nothing changes) on a B > 1 model or for another count.
+GGML_API int     moshi_hot_set_host_ring(moshi_hot_model_t * m, const int32_t * rows, int n_values);
 // the K (kv = 0) / V (kv = 1) ring of one layer as its bytes (BF16 [D, C, H]), read out (write = 0) or overwritten (write = 1): parity runs that restart every
 // frame from another executor's state. Returns the ring's size in bytes (-1: no such ring); buf may be NULL to ask for the size. which: 0 Temporal, 1 Depth.
 GGML_API int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int layer, int kv, void * buf, int64_t nbytes, int write);

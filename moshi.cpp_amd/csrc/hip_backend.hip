@@ -342,7 +342,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -1567,6 +1567,76 @@ static bool match_embed_sum(const analysis & an, int pos, embed_group & grp) {
     return true;
 }
 
+// C+. the [K, T] input of a persona pass (moshi_hot.cpp persona_pass_input): a left-deep chain of concats along dimension 1 whose pieces are embedding
+// sums over their rows (match_embed_sum) and row gathers from dense F32 / BF16 / F16 tensors, matched at the top-most concat -> one k_pass_input launch.
+// The token pieces must be ONE sum over the rows of the pass: the same tables in the same order, and every term's index / scale pointers those of one
+// array per term with row t of the pass at element t (the pieces take views of it). Anything else is declined and runs as the plain nodes it is.
+struct pass_input_group : group { pass_input_args a; };
+static bool match_pass_input(const analysis & an, int pos, pass_input_group & grp) {
+    const ggml_tensor * top = an.g->nodes[pos];
+    auto is_cat = [](const ggml_tensor * t) {
+        return t->op == GGML_OP_CONCAT && t->op_params[0] == 1 && t->type == GGML_TYPE_F32 && !t->view_src && ggml_is_contiguous(t) && t->ne[2] == 1 && t->ne[3] == 1;
+    };
+    if (!is_cat(top) || top->ne[1] > PASS_INPUT_ROWS_MAX) return false;
+    std::vector<const ggml_tensor *> pieces;   // right to left
+    std::vector<int> members;
+    const ggml_tensor * cur = top;
+    while (is_cat(cur) && (cur == top || uses_of(an, cur) == 1) && pos_of(an, cur) >= 0 && !an.skip[(size_t) pos_of(an, cur)]) {
+        pieces.push_back(cur->src[1]);
+        members.push_back(pos_of(an, cur));
+        cur = cur->src[0];
+    }
+    pieces.push_back(cur);
+    const int64_t K = top->ne[0], T = top->ne[1];
+    pass_input_args & a = grp.a;
+    memset(&a, 0, sizeof(a));
+    bool have_sum = false;
+    int64_t row0 = 0;
+    for (size_t pi = pieces.size(); pi-- > 0; ) {   // left to right: rows [row0, row0 + n)
+        const ggml_tensor * p = pieces[pi];
+        const int64_t n = p->ne[1];
+        const int pp = pos_of(an, p);
+        if (pp < 0 || an.skip[(size_t) pp] || uses_of(an, p) != 1 || p->type != GGML_TYPE_F32 || !ggml_is_contiguous(p) || p->ne[0] != K || p->ne[2] != 1 || p->ne[3] != 1) return false;
+        if (p->op == GGML_OP_GET_ROWS) {
+            const ggml_tensor * tab = p->src[0], * idx = p->src[1];
+            if (tab->type != GGML_TYPE_F32 && tab->type != GGML_TYPE_BF16 && tab->type != GGML_TYPE_F16) return false;
+            if (!dense_rows(tab) || tab->ne[0] != K || !tab->data || idx->type != GGML_TYPE_I32 || !ggml_is_contiguous(idx) || ggml_nelements(idx) != n || !idx->data) return false;
+            if (a.n_voices == PASS_INPUT_VOICES_MAX) return false;
+            a.voice[a.n_voices] = { (const char *) tab->data, (int64_t) tab->nb[1], tab->ne[1], (const int32_t *) idx->data, (int) tab->type, (int) row0 };
+            for (int64_t t = 0; t < n; t++) a.kind[row0 + t] = (int8_t) a.n_voices;
+            a.n_voices++;
+            members.push_back(pp);
+        } else {
+            embed_group eg;
+            if (!match_embed_sum(an, pp, eg) || eg.a.n > 24 || eg.a.K != K || eg.a.out != (float *) p->data || (int64_t) (eg.a.B > 1 ? eg.a.B : 1) != n) return false;
+            // this piece's pointers as those of the whole pass: element row0 of the arrays is the piece's first (only rows of the piece itself are ever read through them).
+            // 4 bytes per row on both: the index is a contiguous I32 vector and the scale a contiguous [1, n] F32 tensor (match_embed_term declines anything else at
+            // n > 1; a one-row piece reads element 0 of its own operands whatever their strides)
+            for (int i = 0; i < eg.a.n; i++) {
+                embed_src & e = eg.a.src[i];
+                e.index = (const int32_t *) ((uintptr_t) e.index - (uintptr_t) row0 * 4);
+                if (e.scale) e.scale = (const float *) ((uintptr_t) e.scale - (uintptr_t) row0 * 4);
+            }
+            if (!have_sum) { (embed_sum_args &) a = eg.a; have_sum = true; }
+            else {
+                if (eg.a.n != a.n) return false;
+                for (int i = 0; i < eg.a.n; i++) {
+                    const embed_src & x = eg.a.src[i], & y = a.src[i];
+                    if (x.table != y.table || x.row_bytes != y.row_bytes || x.n_rows != y.n_rows || x.type != y.type || x.index != y.index || x.scale != y.scale) return false;
+                }
+            }
+            for (int64_t t = 0; t < n; t++) a.kind[row0 + t] = -1;
+            members.insert(members.end(), eg.members.begin(), eg.members.end());
+        }
+        row0 += n;
+    }
+    if (row0 != T) return false;
+    a.K = K; a.B = (int) T; a.out = (float *) top->data;
+    grp.members = members;
+    grp.emit_pos = pos;
+    return true;
+}
+
 // C'. one embedding row through a small Q8_0 projection (tts: low-rank Depth embeddings): get_rows -> mul_mat [-> cast] as one launch, matched at the mul_mat
 struct lowrank_group : group { lowrank_embed_args a; };
 static bool match_lowrank_embed(const analysis & an, int pos, lowrank_group & grp) {
@@ -2405,6 +2475,19 @@ static void pass_lowrank_embed(planner & pl) {
     }
 }
 
+// the input of a persona pass: the whole concat chain with its embedding sums and row gathers as one launch (top-most concat first)
+static void pass_pass_inputs(planner & pl) {
+    if (pl.c->flags & 4096) return;   // (the chain stays its plain nodes: an embedding-sum launch per token piece, a row gather per voice piece, the concat copies)
+    for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CONCAT) continue;
+        pass_input_group grp;
+        if (!match_pass_input(pl.an, i, grp) || !claim_group(pl, grp)) continue;   // (claim: the matcher tests position and an.skip of every concat and piece; a sum's terms as pass_embed_sums)
+        const pass_input_args a = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_pass_input(s, a); });
+        pl.p->n_pass_input_launches++; pl.p->n_pass_input_rows += a.B;
+    }
+}
+
 // embedding sums (top-most add first)
 static void pass_embed_sums(planner & pl) {
     for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
@@ -2913,6 +2996,7 @@ static void merge_chains(planner & pl) {
 //   pass_sampler_streams   the B-column form of the same samplers, same direction
 //   pass_cross_attention_blocks   the per-job cross-attention of a tts replay pass: before the row copies and the mat-vec pass, which would take a job's
 //                          copy and its F32 mul_mats one by one
+//   pass_pass_inputs       before pass_embed_sums, which would take the sums of a persona pass's token pieces one by one; bottom-up (the top-most concat)
 //   pass_embed_sums        bottom-up (a left-deep sum is matched at its last add); before the row copies
 //   pass_row_copies        one launch for all rows instead of one per row: before pass_cpy_of_cont, whose pattern every single row is
 //   pass_matvecs           after the attention pass (see there); every remaining mul_mat of a supported shape
@@ -2920,7 +3004,7 @@ static void merge_chains(planner & pl) {
 // (pass_ring_copies, pass_codec_convs, pass_cross_attention, pass_lowrank_embed, pass_cpy_of_cont, pass_timestep_of_add: no reason on record but their place)
 static void (* const fusion_passes[])(planner &) = {
     pass_heads_streams, pass_ring_copies, pass_attention, pass_codec_convs, pass_scalar_gathers, pass_samplers, pass_sampler_streams, pass_cross_attention,
-    pass_cross_attention_blocks, pass_lowrank_embed, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
+    pass_cross_attention_blocks, pass_lowrank_embed, pass_pass_inputs, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
 };
 
 static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
@@ -2984,7 +3068,7 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
-// the sixteen *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+// the twenty *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
 static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
     c->stats.nodes_in_last_plan = p->n_nodes;
@@ -2996,6 +3080,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
+    c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

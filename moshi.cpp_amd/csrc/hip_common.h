@@ -283,6 +283,14 @@ void k_cross_attn_blocks(hipStream_t s, const xattn_blocks_args & a);
 // B > 1 (lockstep streams / prompt blocks): B columns - column b takes index[b] and scale[b] of every term and writes out[b * K ..] (0 = 1 column)
 struct embed_sum_args { embed_src src[EMBED_SUM_MAX]; int n; int64_t K; float * out; int B; };
 void k_embed_sum(hipStream_t s, const embed_sum_args & a);
+// The [K, T] input of a persona pass (moshi_hot.cpp persona_pass_input) as ONE launch: an embedding sum of B = T columns whose index and scale pointers
+// span the whole pass (term i of row t takes index[t] and scale[t]) and whose row t is either a TOKEN row - column t of the sum, written exactly as
+// k_embed_sum writes it - or a VOICE row: row index[t - row0] of voice piece kind[t], a dense [K, n_rows] F32 / BF16 / F16 tensor, converted exactly to F32.
+#define PASS_INPUT_ROWS_MAX 64
+#define PASS_INPUT_VOICES_MAX 16
+struct pass_voice { const char * table; int64_t row_bytes, n_rows; const int32_t * index; int type, row0; };
+struct pass_input_args : embed_sum_args { pass_voice voice[PASS_INPUT_VOICES_MAX]; int n_voices; int8_t kind[PASS_INPUT_ROWS_MAX]; };   // kind[t]: -1 a token row, else its voice piece
+void k_pass_input(hipStream_t s, const pass_input_args & a);
 // one residual-VQ encode level (core_vq.h:27-56, 171-194): nearest centroid of `resid`, its index, and resid - centroid
 struct vq_level_args {
     const char * emb; int64_t emb_row_bytes; int D, NC;      // F32 codebook [D, NC]

@@ -2408,11 +2408,28 @@ void k_cross_attn_blocks(hipStream_t s, const xattn_blocks_args & ba) {
 // choice of a Q4_0 byte) made hipcc wait for each term's loads before it issued the next (24 x s_waitcnt vmcnt(0) in a row: 21 us at the head of every
 // Temporal graph, profiles/r03_bench_kernel_trace_summary.txt). With the type a template parameter the element of every term is ONE scale load + ONE
 // quant load whose addresses are plain arithmetic, all requested before the first is looked at. 64-thread workgroups: 64 of them for a 4096-wide row.
-template <int TYPE, int NMAX>
-__global__ void __launch_bounds__(64) embed_sum_kernel(embed_sum_args a) {
+// ARGS = pass_input_args: the input of a persona pass (hip_common.h) - the same kernel over the T rows of the pass, of which the VOICE rows leave early
+// (the row's kind is uniform per workgroup: one scalar read of the by-value table; one index load, one element load, an exact conversion). A token row runs
+// the instructions below, column b = its row: the bits of k_embed_sum on the same terms. The two are instantiations of ONE kernel and not two kernels
+// around a device function because the argument struct handed to a function - by reference or by value - is no longer read from the kernel arguments
+// where it is needed: hipcc loaded all of it into scalar registers up front and spilled them to vector lanes (the 24-term Q4_0 instance: 1 597 -> 2 555
+// instructions, 812 lane moves). With ARGS = embed_sum_args the code is instruction for instruction what it was before ARGS existed.
+template <int TYPE, int NMAX, class ARGS = embed_sum_args>
+__global__ void __launch_bounds__(64) embed_sum_kernel(ARGS a) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.K) return;
     const int b = (int) blockIdx.y;   // column (stream) b: index[b], scale[b], out[b * K ..]
+    if constexpr (std::is_same<ARGS, pass_input_args>::value) {
+        const int kd = a.kind[b];
+        if (kd >= 0) {
+            const pass_voice & pv = a.voice[kd];
+            int64_t row = pv.index[b - pv.row0];
+            if (row < 0 || row >= pv.n_rows) row = 0;   // (as the embedding rows: an index outside the table reads row 0, never memory outside it)
+            const char * src = pv.table + row * pv.row_bytes;
+            a.out[(int64_t) b * a.K + i] = pv.type == GGML_TYPE_F32 ? ((const float *) src)[i] : pv.type == GGML_TYPE_BF16 ? bf2f(((const uint16_t *) src)[i]) : h2f(((const uint16_t *) src)[i]);
+            return;
+        }
+    }
     int64_t r[NMAX];
     float sc[NMAX], v[NMAX];
 #pragma unroll
@@ -2474,6 +2491,25 @@ void k_embed_sum(hipStream_t s, const embed_sum_args & a) {
         default:             EMBED_LAUNCH(-1); break;
     }
 #undef EMBED_LAUNCH
+}
+
+// The input of a persona pass: embed_sum_kernel over pass_input_args - workgroup (x, t) writes elements 64 x .. 64 x + 63 of row t; no workgroup waits for
+// another, every store is a vector store of the lane's own element.
+void k_pass_input(hipStream_t s, const pass_input_args & a) {
+    const embed_sum_args & e = a;
+    GGML_ASSERT(e.B >= 1 && e.B <= PASS_INPUT_ROWS_MAX && e.n >= 0 && e.n <= 24 && a.n_voices >= 0 && a.n_voices <= PASS_INPUT_VOICES_MAX);
+    for (int t = 0; t < e.B; t++) GGML_ASSERT(a.kind[t] < a.n_voices && (a.kind[t] >= 0 || e.n > 0));
+    int type = e.n > 0 ? e.src[0].type : GGML_TYPE_F32;
+    for (int t = 1; t < e.n; t++) if (e.src[t].type != type) type = -1;
+    const dim3 grid((unsigned) ((e.K + 63) / 64), (unsigned) e.B);
+    switch (type) {   // (the instantiations of k_embed_sum's 24-term kernel: a pass sums a frame's 17 embeddings)
+        case GGML_TYPE_Q4_0: embed_sum_kernel<GGML_TYPE_Q4_0, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+        case GGML_TYPE_Q8_0: embed_sum_kernel<GGML_TYPE_Q8_0, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+        case GGML_TYPE_F32:  embed_sum_kernel<GGML_TYPE_F32, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+        case GGML_TYPE_BF16: embed_sum_kernel<GGML_TYPE_BF16, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+        case GGML_TYPE_F16:  embed_sum_kernel<GGML_TYPE_F16, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+        default:             embed_sum_kernel<-1, 24, pass_input_args><<<grid, 64, 0, s>>>(a); break;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

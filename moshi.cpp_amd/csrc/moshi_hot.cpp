@@ -141,13 +141,30 @@ struct Builder {
     // scratch protocol: alloc -> upload -> compute -> free -> reset (src/context.h:628-653)
     void expand_read(T t, void * dst) { expand(t); readbacks.push_back({ t, dst, ggml_nbytes(t) }); }
     void compute_scratch() {
-        alloc();
+        // MOSHI_HOT_TIME_SCRATCH (diagnosis): where the host spends a scratch graph that takes more than 50 ms - its buffer, its uploads, the enqueue, the
+        // read-backs, the buffer's release - one line on stderr per such graph
+        static const bool timed = getenv("MOSHI_HOT_TIME_SCRATCH") != nullptr;
+        int64_t t[6] = { 0, 0, 0, 0, 0, 0 };
+        auto stamp = [&](int i) { if (timed) t[i] = ggml_time_us(); };
+        const int n_nodes = gf ? ggml_graph_n_nodes(gf) : 0;
+        stamp(0);
+        buf = ggml_backend_alloc_ctx_tensors(ctx, be);
+        GGML_ASSERT(buf);
+        stamp(1);
+        for (auto & c : consts) ggml_backend_tensor_set(c.t, c.data.data(), 0, c.data.size());
+        stamp(2);
         compute();
+        stamp(3);
         for (auto & r : readbacks) ggml_backend_tensor_get(r.t, r.dst, 0, r.n);
+        stamp(4);
         readbacks.clear();
         consts.clear();
         exponentials.clear();
         ggml_backend_buffer_free(buf);
+        stamp(5);
+        if (timed && t[5] - t[0] > 50000)
+            fprintf(stderr, "scratch graph of %d nodes: buffer %.1f ms, uploads %.1f, compute %.1f, read-backs %.1f, release %.1f\n", n_nodes,
+                    (t[1] - t[0]) / 1e3, (t[2] - t[1]) / 1e3, (t[3] - t[2]) / 1e3, (t[4] - t[3]) / 1e3, (t[5] - t[4]) / 1e3);
         buf = nullptr;
         ggml_reset(ctx);
         gf = nullptr;
@@ -1246,7 +1263,7 @@ extern "C" moshi_hot_model_t * moshi_hot_create(ggml_backend_t backend, const st
 static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int B, ModelKind kind) {
     if (!cfg || B < 2 || B > (cfg->wide_streams ? MOSHI_HOT_MAX_STREAMS : MOSHI_HOT_DEFAULT_MAX_STREAMS)) return nullptr;
     const moshi_hot_config & c = *cfg;
-    const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && !c.personaplex && c.tp_world == 0 &&
+    const bool common = c.enable_lm && !c.enable_mimi_encoder && !c.enable_mimi_decoder && c.tp_world == 0 &&
                         c.dep_shard_world <= 1 && !c.depth_only && !c.chain_depth && !c.codec_stream;
     // the tts branches: on the tts shape alone, in any combination
     const bool no_tts = !c.demux_second_stream && !c.depformer_low_rank && !c.delay_steps && !c.cross_attention && !c.condition_sum && !c.dep_schedule_len;
@@ -1256,6 +1273,10 @@ static moshi_hot_model_t * create_columns(ggml_backend_t backend, const struct m
     const bool tts_shape = c.dep_q > 0 && c.n_q == c.dep_q && !c.extra_heads && c.delay_steps >= 0 && c.depformer_low_rank >= 0 &&
                            (!c.cross_attention || c.cross_len >= 1) && c.dep_schedule_len >= 0 && c.dep_schedule_len <= MOSHI_HOT_MAX_CODEBOOKS &&
                            (c.dep_schedule_len == 0 || c.dep_schedule_len >= c.dep_q);
+    // the PersonaPlex shape (opt-in: persona_columns): the moshika shape's conditions around 16 sampled codebooks of which 8 are handed back (lm.h:802-805),
+    // the other speaker's 8 being inputs; the flag is valid on this shape alone, and PersonaPlex without it keeps being refused
+    const bool persona_shape = c.personaplex && c.dep_q >= 8 && c.n_q >= c.dep_q && c.n_q > 8 && !c.extra_heads && no_tts;
+    if (c.personaplex || c.persona_columns) return common && c.persona_columns && persona_shape ? create_model(backend, cfg, seed, nullptr, B, kind) : nullptr;
     if (!common || !(moshika_shape || stt_shape || tts_shape)) return nullptr;
     return create_model(backend, cfg, seed, nullptr, B, kind);
 }
@@ -1269,7 +1290,10 @@ extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, co
 }
 // the tts shape of a B > 1 model (no codebook is an input): a conversation's conditions travel with its history or snapshot, so prefill and the plain
 // snapshot calls refuse it (moshi_hot_slots_replay, moshi_hot_slot_fork_full / _save_full / _load_full take it)
-static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m->cfg.n_q == m->cfg.dep_q; }
+// (PersonaPlex's 16 / 16 is not it: 8 of its codebooks are inputs, it has provided frames and no conditions - prefill and the plain snapshot calls take it)
+static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m->cfg.n_q == m->cfg.dep_q && !m->cfg.personaplex; }
+// the PersonaPlex shape of a B > 1 model (create_columns admits it with persona_columns alone)
+static bool persona_shape(const moshi_hot_model * m) { return m->n_streams > 1 && m->cfg.personaplex; }
 // slot b of a slots model, or NULL (a bad index or a model of another kind)
 static moshi_hot_model::Column * slot(moshi_hot_model_t * m, int b) {
     return m->kind == ModelKind::slots && b >= 0 && b < m->n_streams ? &m->cols[(size_t) b] : nullptr;
@@ -2027,6 +2051,12 @@ extern "C" int moshi_hot_host_ring(moshi_hot_model_t * m, int32_t * dst, int max
     if (dst && n <= max_values) m->ring.export_rows(dst);
     return !dst || n <= max_values ? n : 0;
 }
+extern "C" int moshi_hot_set_host_ring(moshi_hot_model_t * m, const int32_t * rows, int n_values) { STREAMS_REFUSE(-1);
+    // a voice's image of the delay ring (lm.h:1038-1052): the rows are replaced, the frame count stays
+    if (!rows || n_values != (int) m->ring.rows.size()) return -1;
+    m->ring.import_rows(rows, m->ring.frames);
+    return 0;
+}
 extern "C" void moshi_hot_set_depth_hook(moshi_hot_model_t * m, moshi_hot_depth_hook_t fn, void * user) { STREAMS_REFUSE(); m->depth_hook = fn; m->depth_hook_user = user; }
 
 namespace {
@@ -2284,7 +2314,7 @@ T causal_mask_block(Builder & s, int C, int64_t pos, int n) {
 // columns and the replaced ones' results are dropped (the Depth rings start afresh every frame).
 void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, const int32_t * text_in, int32_t * text_token_out, int32_t * out_audio, int32_t * status) {
     const moshi_hot_config & c = m->cfg;
-    const int B = m->n_streams, ncb = c.n_q + 1, dep_q = c.dep_q, needed = m->proto.needed();
+    const int B = m->n_streams, ncb = c.n_q + 1, dep_q = c.dep_q, io_dep_q = m->proto.io_dep_q, needed = m->proto.needed();   // (PersonaPlex: 16 sampled, 8 handed back)
     int n_open = 0;
     for (int b = 0; b < B; b++) {
         const auto & col = m->cols[(size_t) b];
@@ -2352,7 +2382,7 @@ void lm_step_columns(moshi_hot_model * m, const int32_t * in_audio, const int32_
         col.ring.commit(text[(size_t) b], audio.data(), false);
         const DelayRing::ReadOut r = replace[(size_t) b] ? DelayRing::ReadOut::filling : col.ring.read_out(&text_token_out[b], audio.data());
         if (r == DelayRing::ReadOut::filling) continue;
-        if (dep_q > 0) memcpy(out_audio + (size_t) b * dep_q, audio.data(), (size_t) dep_q * sizeof(int32_t));
+        if (dep_q > 0) memcpy(out_audio + (size_t) b * io_dep_q, audio.data(), (size_t) io_dep_q * sizeof(int32_t));
         status[b] = r == DelayRing::ReadOut::valid ? 1 : 0;
         if (status[b] == 1 && heads_row) memcpy(m->last_heads.data() + (size_t) b * heads_row, heads.data() + (size_t) b * heads_row, heads_row * sizeof(float));
     }
@@ -2384,7 +2414,7 @@ extern "C" int moshi_hot_lm_step_slots_text(moshi_hot_model_t * m, const int32_t
     for (int b = 0; b < m->n_streams; b++) {
         if (status[b] == 1) { n_valid++; continue; }
         text_token_out[b] = -1;
-        for (int q = 0; q < m->cfg.dep_q; q++) out_audio[(size_t) b * m->cfg.dep_q + q] = -1;
+        for (int q = 0; q < m->proto.io_dep_q; q++) out_audio[(size_t) b * m->proto.io_dep_q + q] = -1;
     }
     return n_valid;
 }
@@ -2598,21 +2628,12 @@ Builder & ring_ordered_scratch(moshi_hot_model * m) {
     }
     return *m->scratch_rows;
 }
-// one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
-void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames, bool replay) {
+bool any_ordered_piece(const std::vector<PassJob> & jobs) { for (const PassJob & j : jobs) if (j.ordered) return true; return false; }
+Builder & pass_scratch(moshi_hot_model * m, const std::vector<PassJob> & jobs) { return any_ordered_piece(jobs) ? ring_ordered_scratch(m) : *m->scratch; }
+// a pass from its input on: the Temporal stack over the [dim, T] rows `input` built on `s`, every job's row of transformer_out, the stream positions
+void slots_pass_stack(moshi_hot_model * m, Builder & s, std::vector<PassJob> & jobs, T input) {
     const int C = m->temporal.capacity;
-    int Tn = 0;
-    bool any_ordered = false;
-    for (const PassJob & j : jobs) { Tn += j.n; any_ordered = any_ordered || j.ordered; }
-    PassInputs in(m->cfg.n_q + 1, Tn);
-    for (size_t ji = 0; ji < jobs.size(); ji++) {
-        DelayRing & ring = m->cols[(size_t) jobs[ji].b].ring;
-        if (replay) replayed_frames(m->cfg, ring, jobs[ji].b, frames[ji], jobs[ji].n, jobs[ji].row, in);
-        else provided_frames(ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
-    }
-    PhaseTimer pt(m, 1);
-    Builder & s = any_ordered ? ring_ordered_scratch(m) : *m->scratch;
-    T input = embedding_sum_rows(m, s, in, Tn);
+    const bool any_ordered = any_ordered_piece(jobs);
     // the attention sequences of the pass: a block piece is one (causal from its position: it ends at or before the ring's end); a ring-ordered piece is
     // one per row - the job of one row at position p: ring slot p % C, the RoPE row of offset p and the mask row of a live step at p (slot cc is open
     // iff cc <= p, the whole ring from p = C - 1 on; bias_pattern_index(T = 1, p)). All uploaded constants: passes of one shape reuse one plan.
@@ -2641,11 +2662,60 @@ void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
     }
     s.compute_scratch();
 }
+// one pass: the host half of moshi_hot_prefill on each job's own column, then one scratch graph over the concatenated rows
+void slots_prefill_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<const int32_t *> & frames, bool replay) {
+    int Tn = 0;
+    for (const PassJob & j : jobs) Tn += j.n;
+    PassInputs in(m->cfg.n_q + 1, Tn);
+    for (size_t ji = 0; ji < jobs.size(); ji++) {
+        DelayRing & ring = m->cols[(size_t) jobs[ji].b].ring;
+        if (replay) replayed_frames(m->cfg, ring, jobs[ji].b, frames[ji], jobs[ji].n, jobs[ji].row, in);
+        else provided_frames(ring, frames[ji], jobs[ji].n, jobs[ji].row, in);
+    }
+    PhaseTimer pt(m, 1);
+    Builder & s = pass_scratch(m, jobs);
+    slots_pass_stack(m, s, jobs, embedding_sum_rows(m, s, in, Tn));
+}
 
-// moshi_hot_slots_prefill (past_end == false: a job that would pass the ring's end is refused) and moshi_hot_slots_prefill_long (true). The cutter:
-// pieces in job order, a pass of at most `chunk` rows; a piece that would cross the ring's end stops there (everything before the wrap stays in block
-// form) and closes its pass, so that no pass holds two pieces of one slot; a piece at or past the ring's end is ring-ordered, and a pass holds at most
-// RING_ORDERED_ROWS_MAX such rows. With no job past the ring's end none of the three rules ever applies: the passes are those of the refusing call.
+// THE CUTTER of the slot passes: job j's n_rows[j] rows, laid end to end in job order, become pieces of passes of at most `chunk` rows; run_pass(pieces,
+// first) runs one pass, first[i] = piece i's job and the index of its first row within that job. A piece that
+// would cross the ring's end stops there (everything before the wrap stays in block form) and closes its pass, so that no pass holds two pieces of one
+// slot; a piece at or past the ring's end is ring-ordered, and a pass holds at most RING_ORDERED_ROWS_MAX such rows. With no job past the ring's end none
+// of the three rules ever applies. The caller has checked the jobs; run_pass advances the slots' positions.
+struct PieceStart { int job, row; };
+template <class F>
+void cut_passes(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * n_rows, int chunk, F && run_pass) {
+    if (chunk < 1 || chunk > 64) chunk = 64;   // the device's batched kernels take up to 64 rows per pass
+    const int64_t C = m->temporal.capacity;
+    ggml_backend_mi355x_set_capture(m->be, 0);   // same-shaped pass graphs reuse one plan; none is replayed often enough to pay for a hipGraph capture
+    std::vector<PassJob> jobs;
+    std::vector<PieceStart> first;
+    int rows = 0, ordered_rows = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        int done = 0;
+        while (done < n_rows[j]) {
+            int Tj = n_rows[j] - done < chunk - rows ? n_rows[j] - done : chunk - rows;
+            PassJob pj; pj.b = slots[j]; pj.row = rows; pj.pos = m->cols[(size_t) slots[j]].pos;
+            pj.ordered = pj.pos >= C;
+            if (pj.ordered) { if (Tj > RING_ORDERED_ROWS_MAX - ordered_rows) Tj = RING_ORDERED_ROWS_MAX - ordered_rows; ordered_rows += Tj; }
+            else if (pj.pos + Tj > C) Tj = (int) (C - pj.pos);
+            pj.n = Tj;
+            jobs.push_back(pj);
+            first.push_back({ j, done });
+            rows += Tj; done += Tj;
+            const bool at_ring_end = !pj.ordered && pj.pos + Tj == C && done < n_rows[j];   // the job goes on ring-ordered: in a pass of its own
+            if (rows == chunk || ordered_rows == RING_ORDERED_ROWS_MAX || at_ring_end || (j == n_jobs - 1 && done == n_rows[j])) {
+                run_pass(jobs, first);
+                jobs.clear(); first.clear(); rows = 0; ordered_rows = 0;
+            }
+        }
+    }
+    if (!jobs.empty()) run_pass(jobs, first);   // (the last jobs had no rows)
+    ggml_backend_mi355x_set_capture(m->be, 1);
+}
+
+// moshi_hot_slots_prefill (past_end == false: a job that would pass the ring's end is refused) and moshi_hot_slots_prefill_long (true), cut by
+// cut_passes: with no job past the ring's end the passes are those of the refusing call.
 // replay: moshi_hot_slots_replay - the same passes over history frames of a tts-shaped model (which has no provided frames: needed_tokens == 0,
 // lm.h:807-809), and of no other; the prefill calls keep refusing that shape.
 int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end, bool replay = false) {
@@ -2660,36 +2730,124 @@ int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const 
         total += n_frames[j];
     }
     if (!total) return 0;
-    if (chunk < 1 || chunk > 64) chunk = 64;   // the device's batched kernels take up to 64 rows per pass
-    ggml_backend_mi355x_set_capture(m->be, 0);   // same-shaped pass graphs reuse one plan; none is replayed often enough to pay for a hipGraph capture
-    std::vector<PassJob> jobs;
     std::vector<const int32_t *> frames;
-    int rows = 0, ordered_rows = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        int done = 0;
-        while (done < n_frames[j]) {
-            int Tj = n_frames[j] - done < chunk - rows ? n_frames[j] - done : chunk - rows;
-            PassJob pj; pj.b = slots[j]; pj.row = rows; pj.pos = m->cols[(size_t) slots[j]].pos;
-            pj.ordered = pj.pos >= C;
-            if (pj.ordered) { if (Tj > RING_ORDERED_ROWS_MAX - ordered_rows) Tj = RING_ORDERED_ROWS_MAX - ordered_rows; ordered_rows += Tj; }
-            else if (pj.pos + Tj > C) Tj = (int) (C - pj.pos);
-            pj.n = Tj;
-            jobs.push_back(pj);
-            frames.push_back(tokens[j] + (size_t) done * ncb);
-            rows += Tj; done += Tj;
-            const bool at_ring_end = !pj.ordered && pj.pos + Tj == C && done < n_frames[j];   // the job goes on ring-ordered: in a pass of its own
-            if (rows == chunk || ordered_rows == RING_ORDERED_ROWS_MAX || at_ring_end || (j == n_jobs - 1 && done == n_frames[j])) {
-                slots_prefill_pass(m, jobs, frames, replay);
-                jobs.clear(); frames.clear(); rows = 0; ordered_rows = 0;
+    cut_passes(m, n_jobs, slots, n_frames, chunk, [&](std::vector<PassJob> & jobs, const std::vector<PieceStart> & first) {
+        frames.clear();
+        for (const PieceStart & f : first) frames.push_back(tokens[f.job] + (size_t) f.row * ncb);
+        slots_prefill_pass(m, jobs, frames, replay);
+    });
+    return total;
+}
+
+// ---- persona admission (moshi_hot.h "PersonaPlex streams and slots") -------------------------------------------------------------------------------
+constexpr int PERSONAPLEX_PROMPT_COLUMNS = 17;   // PROMPT_TOKENS (lm.h:983-987): the text and 16 codebooks - a persona's prompt frames exist for n_q = 16 alone
+// rows [row, row + n) of a pass whose Temporal input is of one kind: rows first .. first + n - 1 of a persona's voice (voice != NULL), or token rows
+struct InputPiece { int row, n; const moshi_hot_persona * voice; int first; };
+
+// The [dim, T] input of a persona pass from plain nodes: a voice piece is get_rows of its rows of the voice, uploaded in the voice's own type (the
+// exact conversion to F32 of lm.h:1016); a token piece is the embedding sum of embedding_sum_rows over its rows, its indices and scales being views
+// of ONE index and ONE scale tensor per embedding for the whole pass (row t of the pass at element t, whatever piece holds it); the pieces are joined
+// by concat along dimension 1 in row order. The device plan turns the whole chain into one launch (hip_backend.hip match_pass_input). A pass of token
+// rows only is the input of a prefill pass, node for node.
+T persona_pass_input(moshi_hot_model * m, Builder & s, const PassInputs & in, const std::vector<InputPiece> & pieces, int Tn) {
+    if (pieces.size() == 1 && !pieces[0].voice) return embedding_sum_rows(m, s, in, Tn);
+    const int64_t dim = m->cfg.dim;
+    std::vector<T> idx, sc;
+    T input = nullptr;
+    for (const InputPiece & p : pieces) {
+        T x = nullptr;
+        if (p.voice) {
+            const enum ggml_type vt = (enum ggml_type) p.voice->voice_type;
+            T v = s.constant(s.tensor(vt, dim, p.n), (const char *) p.voice->voice + (size_t) p.first * ggml_row_size(vt, dim));
+            std::vector<int32_t> r((size_t) p.n);
+            for (int t = 0; t < p.n; t++) r[(size_t) t] = t;
+            x = ggml_get_rows(s, v, s.i32s(r));
+        } else {
+            if (idx.empty()) for (size_t i = 0; i < in.ids.size(); i++) {
+                idx.push_back(s.i32s(in.ids[i]));
+                sc.push_back(s.constant(s.tensor(GGML_TYPE_F32, 1, Tn), in.scales[i].data()));
+            }
+            for (size_t i = 0; i < in.ids.size(); i++) {
+                T rows = ggml_get_rows(s, i == 0 ? m->text_emb : m->emb[i - 1], ggml_view_1d(s, idx[i], p.n, (size_t) p.row * 4));
+                T e = ggml_mul(s, rows, ggml_view_2d(s, sc[i], 1, p.n, sc[i]->nb[1], (size_t) p.row * sc[i]->nb[1]));
+                x = x ? ggml_add(s, x, e) : e;
             }
         }
+        input = input ? ggml_concat(s, input, x, 1) : x;
     }
-    if (!jobs.empty()) slots_prefill_pass(m, jobs, frames, replay);   // (the last jobs had no frames)
-    ggml_backend_mi355x_set_capture(m->be, 1);
+    return input;
+}
+
+// one pass: the host half of every row on its job's own column, in row order - a voice row advances the frame count alone (ring.commit(.., true) of
+// moshi_hot_lm_step_embedding), the voice's ring image replaces the ring's rows behind the last voice row (lm.h:1038-1052), every other row is a
+// provided frame of moshi_hot_personaplex_system_prompts - then one scratch graph over the rows. A job's piece is one attention sequence whatever
+// its rows are; neighbouring token rows are one piece of the input whatever jobs they belong to.
+void slots_persona_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const std::vector<PieceStart> & first, const moshi_hot_persona * personas) {
+    const int ncb = m->cfg.n_q + 1;
+    int Tn = 0;
+    for (const PassJob & j : jobs) Tn += j.n;
+    PassInputs in(ncb, Tn);   // (the entries of voice rows stay 0: nothing reads them)
+    std::vector<InputPiece> pieces;
+    std::vector<int32_t> tokens(moshi_hot_personaplex_prompt_tokens(), moshi_hot_personaplex_prompt_tokens() + ncb);
+    for (size_t ji = 0; ji < jobs.size(); ji++) {
+        const moshi_hot_persona & p = personas[first[ji].job];
+        DelayRing & ring = m->cols[(size_t) jobs[ji].b].ring;
+        for (int t = 0; t < jobs[ji].n; t++) {
+            const int r = first[ji].row + t, row = jobs[ji].row + t;
+            const bool voice = r < p.n_voice;
+            if (voice) {
+                ring.commit(0, nullptr, true);
+                if (r == p.n_voice - 1 && p.prompt_cache) ring.import_rows(p.prompt_cache, ring.frames);
+            } else {
+                const int k = r - p.n_voice - p.silence;   // the text-prompt rows sit between the two runs of silence frames
+                tokens[0] = k >= 0 && k < p.n_text ? p.text_prompt[k] : moshi_hot_personaplex_prompt_tokens()[0];
+                provided_frames(ring, tokens.data(), 1, row, in);
+            }
+            const bool joins = !pieces.empty() && (voice ? pieces.back().voice == &p && t > 0 : !pieces.back().voice);
+            if (joins) pieces.back().n++;
+            else pieces.push_back({ row, 1, voice ? &p : nullptr, r });
+        }
+    }
+    PhaseTimer pt(m, 1);
+    Builder & s = pass_scratch(m, jobs);
+    slots_pass_stack(m, s, jobs, persona_pass_input(m, s, in, pieces, Tn));
+}
+
+int slots_persona(moshi_hot_model * m, int n_jobs, const int32_t * slots, const moshi_hot_persona * personas, int chunk) {
+    if (m->kind != ModelKind::slots || !persona_shape(m) || m->cfg.n_q + 1 != PERSONAPLEX_PROMPT_COLUMNS || n_jobs < 0 || n_jobs > m->n_streams || (n_jobs > 0 && (!slots || !personas))) return -1;
+    const int64_t C = m->temporal.capacity;
+    std::vector<int32_t> n_rows((size_t) n_jobs);
+    int total = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const moshi_hot_model::Column * s = slot(m, slots[j]);
+        const moshi_hot_persona & p = personas[j];
+        if (!s || !s->open || p.n_voice < 0 || p.n_text < 0 || p.silence < 0 || (p.n_text > 0 && !p.text_prompt)) return -1;
+        if (p.n_voice > 0 && (!p.voice || (p.voice_type != GGML_TYPE_F32 && p.voice_type != GGML_TYPE_BF16 && p.voice_type != GGML_TYPE_F16))) return -1;
+        const int64_t rows = (int64_t) p.n_voice + 2 * (int64_t) p.silence + p.n_text;
+        if (s->pos + rows > C) return -1;   // (a persona that passes the ring's end: not supported)
+        for (int i = 0; i < j; i++) if (slots[i] == slots[j]) return -1;
+        n_rows[(size_t) j] = (int32_t) rows;
+        total += (int) rows;
+    }
+    // a persona without voice rows: its ring image goes in ahead of its first row - and also where it has no row at all (a job of a ring image alone
+    // replaces the slot's delay ring and counts 0 rows: moshi_hot.h says so)
+    for (int j = 0; j < n_jobs; j++) {
+        DelayRing & ring = m->cols[(size_t) slots[j]].ring;
+        if (personas[j].n_voice == 0 && personas[j].prompt_cache) ring.import_rows(personas[j].prompt_cache, ring.frames);
+    }
+    if (!total) return 0;
+    cut_passes(m, n_jobs, slots, n_rows.data(), chunk, [&](std::vector<PassJob> & jobs, const std::vector<PieceStart> & first) { slots_persona_pass(m, jobs, first, personas); });
     return total;
 }
 }  // namespace
 
+extern "C" int moshi_hot_slots_persona(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const struct moshi_hot_persona * personas, int chunk) {
+    return slots_persona(m, n_jobs, slots, personas, chunk);
+}
+extern "C" int moshi_hot_slot_persona(moshi_hot_model_t * m, int b, const struct moshi_hot_persona * persona, int chunk) {
+    const int32_t sb = b;
+    return moshi_hot_slots_persona(m, 1, &sb, persona, chunk);
+}
 extern "C" int moshi_hot_slots_prefill(moshi_hot_model_t * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk) {
     return slots_prefill(m, n_jobs, slots, tokens, n_frames, chunk, false);
 }
@@ -2752,6 +2910,7 @@ uint64_t slot_fingerprint(const moshi_hot_model * m) {
     for (int i = 0; i <= c.n_q; i++) mix(c.delays[i]);
     mix(m->temporal.layers[0].kcache->type);
     mix(sampled_model(m) ? 1 : 0);
+    if (persona_shape(m)) { mix(c.persona_columns); mix(m->proto.io_dep_q); }   // (no other shape mixes anything here: their fingerprints are what they were)
     if (tts_shape(m)) { mix(c.cross_attention); mix(c.cross_attention ? c.cross_len : 0); mix(c.condition_sum); mix(c.demux_second_stream); mix(c.delay_steps); }   // (version 2)
     return h;
 }
@@ -2889,7 +3048,7 @@ extern "C" int moshi_hot_slot_fork_full(moshi_hot_model_t * m, int src, int dst)
 extern "C" int64_t moshi_hot_slot_save_full(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) { return slot_save(m, b, buf, nbytes, true); }
 extern "C" int moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) { return slot_load(m, b, buf, nbytes, true); }
 
-static const int32_t PERSONAPLEX_PROMPT_TOKENS[17] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
+static const int32_t PERSONAPLEX_PROMPT_TOKENS[PERSONAPLEX_PROMPT_COLUMNS] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }
 
 // the same prompt frames through moshi_hot_prefill: identical state afterwards, a fraction of the time

@@ -20,7 +20,7 @@ class Config(C.Structure):
                [("dep_schedule", C.c_int32 * MAX_CB), ("update_scale", C.c_float),
                 ("dep_shard_rank", C.c_int32), ("dep_shard_world", C.c_int32), ("depth_only", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_world", C.c_int32), ("codec_stream", C.c_int32), ("chain_depth", C.c_int32),
-                ("wide_streams", C.c_int32), ("float_accumulate", C.c_int32)]
+                ("wide_streams", C.c_int32), ("persona_columns", C.c_int32), ("float_accumulate", C.c_int32)]
 
     @property
     def io_dep_q(self):
@@ -45,6 +45,34 @@ def get_sampling(lib, model, b):
     if lib.moshi_hot_get_sampling(model, b, C.byref(s), C.byref(seeded)) != 0:
         return None
     return (s.seed, s.temp, s.temp_text, s.top_k, s.top_k_text, bool(seeded.value))
+
+
+class Persona(C.Structure):
+    """struct moshi_hot_persona: one conversation's persona (moshi_hot_slots_persona)"""
+    _fields_ = [("voice", C.c_void_p), ("voice_type", C.c_int32), ("n_voice", C.c_int32), ("prompt_cache", C.c_void_p),
+                ("text_prompt", C.c_void_p), ("n_text", C.c_int32), ("silence", C.c_int32)]
+
+
+def persona(voice=None, voice_type=0, prompt_cache=None, text_prompt=(), silence=6):
+    """-> (Persona, the numpy arrays it points into: keep them alive while the struct is in use). voice: [n_voice, dim] array of the dtype that
+    voice_type names (float32 for GGML_TYPE_F32 = 0, uint16 bit patterns for F16 = 1 / BF16 = 30); prompt_cache: int32 [rows, n_q + 1] or None"""
+    import numpy as np
+    keep = []
+    p = Persona()
+    if voice is not None and len(voice):
+        v = np.ascontiguousarray(voice)
+        keep.append(v)
+        p.voice, p.voice_type, p.n_voice = v.ctypes.data, voice_type, v.shape[0]
+    if prompt_cache is not None:
+        c = np.ascontiguousarray(prompt_cache, np.int32)
+        keep.append(c)
+        p.prompt_cache = c.ctypes.data
+    if len(text_prompt):
+        t = np.ascontiguousarray(text_prompt, np.int32)
+        keep.append(t)
+        p.text_prompt, p.n_text = t.ctypes.data, t.size
+    p.silence = silence
+    return p, keep
 
 
 TEXT_KEEP = -2 ** 31   # MOSHI_HOT_TEXT_KEEP
@@ -97,6 +125,9 @@ SIGNATURES = {
     "moshi_hot_slots_replay": (C.c_int, [P, C.c_int, P, P, P, C.c_int]),
     "moshi_hot_slot_replay": (C.c_int, [P, C.c_int, P, C.c_int, C.c_int]),
     "moshi_hot_slot_last_raw": (C.c_int, [P, C.c_int, P]),
+    "moshi_hot_slots_persona": (C.c_int, [P, C.c_int, P, P, C.c_int]),
+    "moshi_hot_slot_persona": (C.c_int, [P, C.c_int, P, C.c_int]),
+    "moshi_hot_set_host_ring": (C.c_int, [P, P, C.c_int]),
     "moshi_hot_slot_fork_full": (C.c_int, [P, C.c_int, C.c_int]),
     "moshi_hot_slot_save_full": (C.c_int64, [P, C.c_int, P, C.c_int64]),
     "moshi_hot_slot_load_full": (C.c_int, [P, C.c_int, P, C.c_int64]),
