@@ -879,14 +879,17 @@ static bool match_norm_affine(const analysis & an, int pos, norm_affine_group & 
     return true;
 }
 
-// B. single-token attention block
+// B. the self-attention block of one Temporal / Depth layer (moshi_hot.cpp), matched at its soft_max. One block walk, four forms:
+//      single column  q / k / v [D, T, H], whole rings [D, C, H], T <= 64 new rows, output a dense [D, H, T] of its own (match_attention; T > 4 is batched prompt prefill)
+//      ring column    the same over [D, C, H] views of ONE column of [D, C, H, B] rings (slot prefill): `column`, a job of a k_attn_blocks launch pair or, as a run of
+//                     ring-ordered one-row groups, of a k_attn_rows launch; its output may be a copy into the block's row range of a wider [D, H, T] tensor
+//      lockstep       one row of B > 1 columns (moshi_hot_create_streams): q / k / v [D, 1, H, B], rings [D, C, H, B] written at one shared slot, one shared mask row and
+//                     RoPE phase, output [D, H, 1, B] - one launch of B x H workgroups, k_attn_streams (match_attention_streams)
+//      slots          the same with every column at its own position (moshi_hot_create_slots): a mask [C, 1, 1, B] (one contiguous row per stream), an index [1, 1, B]
+//                     (one ring slot per stream), RoPE halves [D/2, 1, 1, B] (one timestep-table row per stream) - the same launch with per-stream strides
+//      Refused today: several rows of several columns at once, and a copy into rows from anything but a ring column.
 struct attn_group : group { attn_args a; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
                           bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
-
-static const ggml_tensor * strip_views(const ggml_tensor * t) {
-    while (t && is_layout_op(t->op)) t = t->src[0];
-    return t;
-}
 
 // rotated = concat(sub(mul(r, rotr), mul(i, roti)), add(mul(r, roti), mul(i, rotr))); returns the un-rotated source
 static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out, const ggml_tensor ** rotr_out, const ggml_tensor ** roti_out) {
@@ -913,58 +916,57 @@ static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out
     return true;
 }
 
-static bool match_attention(const analysis & an, int pos, attn_group & grp) {
-    const ggml_tensor * sm = an.g->nodes[pos];
-    if (sm->op != GGML_OP_SOFT_MAX || !sm->src[1]) return false;
-    const ggml_tensor * kq = sm->src[0], * mask = sm->src[1];
-    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1 || uses_of(an, sm) != 1) return false;
-    const ggml_tensor * kc = kq->src[0], * qo = kq->src[1];
-    if (kc->op != GGML_OP_SET_ROWS || kc->type != GGML_TYPE_BF16) return false;
-    const ggml_tensor * pv = sole_consumer(an, sm);
-    if (!pv || pv->op != GGML_OP_MUL_MAT || pv->src[1] != sm) return false;
-    const ggml_tensor * vt = pv->src[0];
+// THE CHAIN, from the soft_max at `pos`: x2 = sole consumer of x1 = permute(pv), pv = mul_mat(cont(transpose(vc)), sm), sm = soft_max(kq, mask),
+// kq = mul_mat(kc, qo), kc / vc = set_rows(ring, ko / vrow, idx). Guaranteed on return: kq, sm, pv and x1 have one consumer each; the rings are BF16 with
+// dense rows, of one shape [D, C, H] in their first three dimensions, written at one shared contiguous I32 index; D fits the kernels' lane layout; the mask
+// is contiguous F32 rows of C. What x2 is (cont, or a copy into rows) and every size beyond D, C, H is the caller's to check.
+struct attn_chain { const ggml_tensor * sm, * kq, * pv, * kc, * vc, * qo, * ko, * vrow, * x1, * x2, * mask, * idx; };
+static bool match_attention_chain(const analysis & an, int pos, attn_chain & c) {
+    c.sm = an.g->nodes[pos];
+    if (c.sm->op != GGML_OP_SOFT_MAX || !c.sm->src[1]) return false;
+    c.kq = c.sm->src[0]; c.mask = c.sm->src[1];
+    if (c.kq->op != GGML_OP_MUL_MAT || uses_of(an, c.kq) != 1 || uses_of(an, c.sm) != 1) return false;
+    c.kc = c.kq->src[0]; c.qo = c.kq->src[1];
+    if (c.kc->op != GGML_OP_SET_ROWS || c.kc->type != GGML_TYPE_BF16) return false;
+    c.pv = sole_consumer(an, c.sm);
+    if (!c.pv || c.pv->op != GGML_OP_MUL_MAT || c.pv->src[1] != c.sm) return false;
+    const ggml_tensor * vt = c.pv->src[0];
     if (vt->op != GGML_OP_CONT || vt->src[0]->op != GGML_OP_TRANSPOSE) return false;
-    const ggml_tensor * vc = vt->src[0]->src[0];
-    if (vc->op != GGML_OP_SET_ROWS || vc->type != GGML_TYPE_BF16) return false;
-    const ggml_tensor * x1 = sole_consumer(an, pv);
-    if (!x1 || x1->op != GGML_OP_PERMUTE) return false;
-    const ggml_tensor * x2 = sole_consumer(an, x1);
-    // the block's output: a dense copy of its own, or (slot prefill) a copy into the block's row range of a wider [D, H, T] tensor
-    const bool into_rows = x2 && x2->op == GGML_OP_CPY && x2->src[0] == x1 && x2->type == GGML_TYPE_F32;
-    if (!x2 || (x2->op != GGML_OP_CONT && !into_rows)) return false;
-    // the rings: whole [D, C, H] tensors, or (slot prefill) [D, C, H] views of one column of [D, C, H, B] rings
-    const bool column = kc->ne[3] == 1 && kc->view_src && kc->view_src->ne[3] > 1;
-    if (column != (vc->ne[3] == 1 && vc->view_src && vc->view_src->ne[3] > 1) || (into_rows && !column)) return false;
-
-    const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], Tn = qo->ne[1];
-    if (qo->ne[0] != D || Tn < 1 || Tn > 64 || qo->ne[2] != H || qo->ne[3] != 1) return false;   // B == 1; blocks longer than 4 rows (prompt prefill) run as consecutive launches of 4
-    if (vc->ne[0] != D || vc->ne[1] != C || vc->ne[2] != H) return false;
-    if (mask->type != GGML_TYPE_F32 || mask->ne[0] != C || mask->ne[1] != Tn || !ggml_is_contiguous(mask)) return false;
+    c.vc = vt->src[0]->src[0];
+    if (c.vc->op != GGML_OP_SET_ROWS || c.vc->type != GGML_TYPE_BF16) return false;
+    c.x1 = sole_consumer(an, c.pv);
+    if (!c.x1 || c.x1->op != GGML_OP_PERMUTE) return false;
+    c.x2 = sole_consumer(an, c.x1);
+    if (!c.x2) return false;
+    const int64_t D = c.kc->ne[0];
+    if (c.vc->ne[0] != D || c.vc->ne[1] != c.kc->ne[1] || c.vc->ne[2] != c.kc->ne[2] || c.kc->nb[0] != 2 || c.vc->nb[0] != 2) return false;
     if (D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
-    if (kc->src[1] != vc->src[1]) return false;
-    const ggml_tensor * idx = kc->src[1];
-    if (idx->type != GGML_TYPE_I32 || ggml_nelements(idx) != Tn || !ggml_is_contiguous(idx)) return false;
-    if (kc->nb[0] != 2 || vc->nb[0] != 2) return false;
+    if (c.mask->type != GGML_TYPE_F32 || c.mask->ne[0] != c.kc->ne[1] || !ggml_is_contiguous(c.mask)) return false;
+    c.idx = c.kc->src[1];
+    if (c.vc->src[1] != c.idx || c.idx->type != GGML_TYPE_I32 || !ggml_is_contiguous(c.idx)) return false;
+    c.ko = c.kc->src[0]; c.vrow = c.vc->src[0];
+    return true;
+}
 
-    const ggml_tensor * ko = kc->src[0], * vrow = vc->src[0];
-    const ggml_tensor * qsrc = qo, * ksrc = ko, * rotr = nullptr, * roti = nullptr;
-    if (qo->op == GGML_OP_CONCAT) {
-        const ggml_tensor * rotr2, * roti2;
-        if (!match_rope(qo, &qsrc, &rotr, &roti) || !match_rope(ko, &ksrc, &rotr2, &roti2) || rotr != rotr2 || roti != roti2) return false;
-        if (rotr->type != GGML_TYPE_F32 || rotr->ne[0] != D / 2 || rotr->ne[1] != Tn || (const char *) roti->data != (const char *) rotr->data + D / 2 * 4) return false;
-        if (rotr->nb[0] != 4 || (Tn > 1 && (int64_t) rotr->nb[1] != D * 4)) return false;
-    }
-    if (qsrc->type != GGML_TYPE_F32 || ksrc->type != GGML_TYPE_F32 || vrow->type != GGML_TYPE_F32) return false;
-    for (const ggml_tensor * t : { qsrc, ksrc, vrow }) if (t->ne[0] != D || t->ne[1] != Tn || t->ne[2] != H || t->ne[3] != 1) return false;
-    sview qs, ks, vs;
-    if (!strided_resolve(qsrc, qs) || !strided_resolve(ksrc, ks) || !strided_resolve(vrow, vs)) return false;
-    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[0] != 4 || v->nb[1] % 4 != 0 || v->nb[2] % 4 != 0) return false;
-    const ggml_tensor * out_t = x2;
-    if (out_t->ne[0] != D || out_t->ne[1] != H || out_t->ne[2] != Tn || !ggml_is_contiguous(out_t)) return false;
+// THE ROPE PAIR: q and k un-rotated, or both rotated (match_rope) by the same F32 table halves of D / 2 dense values, roti directly behind rotr.
+// rotr == nullptr: no RoPE. How many table rows there are and how they are strided differs by form: the caller's check.
+struct rope_pair { const ggml_tensor * qsrc, * ksrc, * rotr, * roti; };
+static bool match_rope_pair(const attn_chain & c, rope_pair & r) {
+    r = { c.qo, c.ko, nullptr, nullptr };
+    if (c.qo->op != GGML_OP_CONCAT) return true;
+    const ggml_tensor * rotr2, * roti2;
+    const int64_t D = c.kc->ne[0];
+    if (!match_rope(c.qo, &r.qsrc, &r.rotr, &r.roti) || !match_rope(c.ko, &r.ksrc, &rotr2, &roti2) || r.rotr != rotr2 || r.roti != roti2) return false;
+    return r.rotr->type == GGML_TYPE_F32 && r.rotr->ne[0] == D / 2 && r.rotr->nb[0] == 4 && (const char *) r.roti->data == (const char *) r.rotr->data + D / 2 * 4;
+}
 
-    // collect the interior of the block: everything reachable from x2 down to the block inputs
-    std::vector<const ggml_tensor *> stack = { x2 };
-    std::vector<int> members;
+// THE INTERIOR: everything reachable from x2 down to the block's inputs - the projections' mul_mats and timestep tables, the mask, the index, the RoPE
+// table and leaves (rings, weights) - as graph positions. into_rows: x2 is a cpy into rows of a wider tensor, whose destination is not followed (it leads
+// to the previous job). Guaranteed: every member is one of the listed ops and stands at most 200 nodes before the soft_max; the block holds exactly two
+// mul_mats, one soft_max and two set_rows; and no interior value is consumed outside the block (x2 is its output): every consumer of a member is a
+// member - counted from the members' side (the analysis holds every tensor's number of consuming nodes), so a graph of many blocks is not walked once per block.
+static bool collect_attention_interior(const analysis & an, int pos, const attn_chain & c, const rope_pair & r, bool into_rows, std::vector<int> & members) {
+    std::vector<const ggml_tensor *> stack = { c.x2 };
     std::unordered_map<const ggml_tensor *, bool> seen;
     int n_mm = 0, n_sm = 0, n_sr = 0;
     const int lo = pos - 200 > 0 ? pos - 200 : 0;
@@ -974,10 +976,10 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
         seen[t] = true;
         const int p = pos_of(an, t);
         if (p < 0) continue;                                  // leaf: cache, mask, indices, weights
-        if (t == mask || t == idx || t == rotr || t == roti) continue;
+        if (t == c.mask || t == c.idx || t == r.rotr || t == r.roti) continue;
         if ((const char *) t->data == nullptr) return false;
         // the projection output (and anything before it) is an input of the block, not part of it
-        const bool is_input = (t->op == GGML_OP_MUL_MAT && t != kq && t != pv) || t->op == GGML_OP_TIMESTEP_EMBEDDING;
+        const bool is_input = (t->op == GGML_OP_MUL_MAT && t != c.kq && t != c.pv) || t->op == GGML_OP_TIMESTEP_EMBEDDING;
         if (is_input) continue;
         if (p < lo) return false;                              // wandered out of the layer: refuse
         switch (t->op) {
@@ -986,174 +988,128 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
             case GGML_OP_SET_ROWS: n_sr++; break;
             case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: case GGML_OP_CONT:
             case GGML_OP_MUL: case GGML_OP_SUB: case GGML_OP_ADD: case GGML_OP_CONCAT: break;
-            case GGML_OP_CPY: if (t != x2) return false; break;
+            case GGML_OP_CPY: if (t != c.x2 || !into_rows) return false; break;
             default: return false;
         }
         members.push_back(p);
-        if (t == x2 && into_rows) { stack.push_back(t->src[0]); continue; }   // (the destination rows are not the block's: they lead to the previous job)
+        if (t == c.x2 && into_rows) { stack.push_back(t->src[0]); continue; }
         for (int s = 0; s < GGML_MAX_SRC; s++) if (t->src[s]) stack.push_back(t->src[s]);
     }
     if (n_mm != 2 || n_sm != 1 || n_sr != 2) return false;
-    // no interior value may be consumed outside the block (x2 is the block's output): every consumer of a member is a member - counted from the
-    // members' side (the analysis holds every tensor's number of consuming nodes), so a graph of many blocks is not walked once per block
     std::unordered_map<int, int> consumed;   // member position -> consuming nodes inside the block
     for (int p : members) consumed[p] = 0;
     for (int p : members) {
-        const ggml_tensor * c = an.g->nodes[p];
+        const ggml_tensor * n = an.g->nodes[p];
         for (int s = 0; s < GGML_MAX_SRC; s++) {
-            const ggml_tensor * t = c->src[s];
-            if (!t || t == c) continue;
+            const ggml_tensor * t = n->src[s];
+            if (!t || t == n) continue;
             bool dup = false;
-            for (int s2 = 0; s2 < s; s2++) if (c->src[s2] == t) dup = true;
+            for (int s2 = 0; s2 < s; s2++) if (n->src[s2] == t) dup = true;
             if (dup) continue;
             auto it = consumed.find(pos_of(an, t));
             if (it != consumed.end()) it->second++;
         }
     }
-    for (auto & kv : consumed) if (an.g->nodes[kv.first] != x2 && kv.second != uses_of(an, an.g->nodes[kv.first])) return false;
-    attn_args & a = grp.a;
-    memset(&a, 0, sizeof(a));
-    a.q = (const float *) qs.base; a.k = (const float *) ks.base; a.v = (const float *) vs.base;
-    a.q_ts = qs.nb[1] / 4; a.q_hs = qs.nb[2] / 4; a.k_ts = ks.nb[1] / 4; a.k_hs = ks.nb[2] / 4; a.v_ts = vs.nb[1] / 4; a.v_hs = vs.nb[2] / 4;
-    a.rot = rotr ? (const float *) rotr->data : nullptr;
-    a.mask = (const float *) mask->data;
-    grp.mask_node = nullptr;
-    if (mask->op == GGML_OP_CONT && pos_of(an, mask) >= 0) {   // a dense copy of an already dense row: read the source
-        const char * base = resolve_dense(mask);
-        if (base && base != (const char *) mask->data) { a.mask = (const float *) base; grp.mask_node = mask; }
-    }
-    a.index = (const int32_t *) idx->data;
-    a.kcache = (char *) kc->data; a.vcache = (char *) vc->data;
-    a.k_nb1 = (int64_t) kc->nb[1]; a.k_nb2 = (int64_t) kc->nb[2];
-    a.v_nb1 = (int64_t) vc->nb[1]; a.v_nb2 = (int64_t) vc->nb[2];
-    a.H = (int) H; a.D = (int) D; a.C = (int) C; a.T = (int) Tn;
-    a.scale = ggml_get_op_params_f32(sm, 0);
-    a.out = (float *) x2->data;
-    a.out_ts = H * D;
-    grp.column = column;
-    grp.members = members;
-    grp.emit_pos = pos_of(an, x2);
+    for (auto & kv : consumed) if (an.g->nodes[kv.first] != c.x2 && kv.second != uses_of(an, an.g->nodes[kv.first])) return false;
     return true;
 }
 
-// B''. the same single-token attention block over B > 1 lockstep streams (moshi_hot_create_streams): q / k / v [D, 1, H, B], rings [D, C, H, B] written
-//      at one shared slot, one shared mask row and RoPE phase, output [D, H, 1, B]. One launch of B x H workgroups (k_attn_streams).
-//      Stream slots (moshi_hot_create_slots) give every stream its own position: a mask [C, 1, 1, B] (one contiguous row per stream), an index [1, 1, B]
-//      (one ring slot per stream) and RoPE halves [D/2, 1, 1, B] (one timestep-table row per stream) - the same launch with per-stream strides.
-static bool match_attention_streams(const analysis & an, int pos, attn_group & grp) {
-    const ggml_tensor * sm = an.g->nodes[pos];
-    if (sm->op != GGML_OP_SOFT_MAX || !sm->src[1]) return false;
-    const ggml_tensor * kq = sm->src[0], * mask = sm->src[1];
-    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1 || uses_of(an, sm) != 1) return false;
-    const ggml_tensor * kc = kq->src[0], * qo = kq->src[1];
-    if (kc->op != GGML_OP_SET_ROWS || kc->type != GGML_TYPE_BF16) return false;
-    const ggml_tensor * pv = sole_consumer(an, sm);
-    if (!pv || pv->op != GGML_OP_MUL_MAT || pv->src[1] != sm) return false;
-    const ggml_tensor * vt = pv->src[0];
-    if (vt->op != GGML_OP_CONT || vt->src[0]->op != GGML_OP_TRANSPOSE) return false;
-    const ggml_tensor * vc = vt->src[0]->src[0];
-    if (vc->op != GGML_OP_SET_ROWS || vc->type != GGML_TYPE_BF16) return false;
-    const ggml_tensor * x1 = sole_consumer(an, pv);
-    if (!x1 || x1->op != GGML_OP_PERMUTE) return false;
-    const ggml_tensor * x2 = sole_consumer(an, x1);
-    if (!x2 || x2->op != GGML_OP_CONT) return false;
+// q / k / v as the projection left them: F32 [D, n1, H, n3], their first dimension dense (strided_resolve looks through the layout nodes and copies)
+static bool resolve_qkv(const attn_chain & c, const rope_pair & r, int64_t n1, int64_t n3, sview & qs, sview & ks, sview & vs) {
+    for (const ggml_tensor * t : { r.qsrc, r.ksrc, c.vrow })
+        if (t->type != GGML_TYPE_F32 || t->ne[0] != c.kc->ne[0] || t->ne[1] != n1 || t->ne[2] != c.kc->ne[2] || t->ne[3] != n3) return false;
+    return strided_resolve(r.qsrc, qs) && strided_resolve(r.ksrc, ks) && strided_resolve(c.vrow, vs) && qs.nb[0] == 4 && ks.nb[0] == 4 && vs.nb[0] == 4;
+}
 
+// THE COMMON ARGUMENTS of every form: bases, head strides, ring strides, H D C, scale, out and its row stride, members and emit position. A mask that is a
+// dense copy, made in this graph, of an already dense row is bypassed (the source is read) and named in mask_node: pass_attention drops the copy when
+// every consumer bypasses it. T, the row strides of q / k / v and everything per stream are the caller's.
+static void fill_attention_group(const analysis & an, const attn_chain & c, const rope_pair & r, const sview & qs, const sview & ks, const sview & vs,
+                                 const std::vector<int> & members, attn_group & grp) {
+    attn_args & a = grp.a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float *) qs.base; a.k = (const float *) ks.base; a.v = (const float *) vs.base;
+    a.q_hs = qs.nb[2] / 4; a.k_hs = ks.nb[2] / 4; a.v_hs = vs.nb[2] / 4;
+    a.rot = r.rotr ? (const float *) r.rotr->data : nullptr;
+    a.mask = (const float *) c.mask->data;
+    grp.mask_node = nullptr;
+    if (c.mask->op == GGML_OP_CONT && pos_of(an, c.mask) >= 0) {
+        const char * base = resolve_dense(c.mask);
+        if (base && base != (const char *) c.mask->data) { a.mask = (const float *) base; grp.mask_node = c.mask; }
+    }
+    a.index = (const int32_t *) c.idx->data;
+    a.kcache = (char *) c.kc->data; a.vcache = (char *) c.vc->data;
+    a.k_nb1 = (int64_t) c.kc->nb[1]; a.k_nb2 = (int64_t) c.kc->nb[2];
+    a.v_nb1 = (int64_t) c.vc->nb[1]; a.v_nb2 = (int64_t) c.vc->nb[2];
+    a.H = (int) c.kc->ne[2]; a.D = (int) c.kc->ne[0]; a.C = (int) c.kc->ne[1];
+    a.scale = ggml_get_op_params_f32(c.sm, 0);
+    a.out = (float *) c.x2->data;
+    a.out_ts = c.kc->ne[2] * c.kc->ne[0];
+    grp.members = members;
+    grp.emit_pos = pos_of(an, c.x2);
+}
+
+// the single-column and ring-column forms: T rows of one column
+static bool match_attention(const analysis & an, int pos, attn_group & grp) {
+    attn_chain c; rope_pair r;
+    if (!match_attention_chain(an, pos, c)) return false;
+    const ggml_tensor * kc = c.kc, * vc = c.vc, * x2 = c.x2;
+    // the block's output: a dense copy of its own, or (slot prefill) a copy into the block's row range of a wider [D, H, T] tensor
+    const bool into_rows = x2->op == GGML_OP_CPY && x2->src[0] == c.x1 && x2->type == GGML_TYPE_F32;
+    if (x2->op != GGML_OP_CONT && !into_rows) return false;
+    // the rings: whole [D, C, H] tensors, or (slot prefill) [D, C, H] views of one column of [D, C, H, B] rings
+    const bool column = kc->ne[3] == 1 && kc->view_src && kc->view_src->ne[3] > 1;
+    if (column != (vc->ne[3] == 1 && vc->view_src && vc->view_src->ne[3] > 1) || (into_rows && !column)) return false;
+
+    const int64_t D = kc->ne[0], H = kc->ne[2], Tn = c.qo->ne[1];
+    if (c.qo->ne[0] != D || Tn < 1 || Tn > 64 || c.qo->ne[2] != H || c.qo->ne[3] != 1) return false;   // B == 1; blocks longer than 4 rows (prompt prefill) run as consecutive launches of 4
+    if (c.mask->ne[1] != Tn || ggml_nelements(c.idx) != Tn) return false;
+    if (!match_rope_pair(c, r)) return false;
+    if (r.rotr && (r.rotr->ne[1] != Tn || (Tn > 1 && (int64_t) r.rotr->nb[1] != D * 4))) return false;   // one table row per block row
+    sview qs, ks, vs;
+    if (!resolve_qkv(c, r, Tn, 1, qs, ks, vs)) return false;
+    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[1] % 4 != 0 || v->nb[2] % 4 != 0) return false;
+    if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != Tn || !ggml_is_contiguous(x2)) return false;
+    std::vector<int> members;
+    if (!collect_attention_interior(an, pos, c, r, into_rows, members)) return false;
+    fill_attention_group(an, c, r, qs, ks, vs, members, grp);
+    grp.a.T = (int) Tn;
+    grp.a.q_ts = qs.nb[1] / 4; grp.a.k_ts = ks.nb[1] / 4; grp.a.v_ts = vs.nb[1] / 4;
+    grp.column = column;
+    return true;
+}
+
+// the lockstep and slots forms: one row of B > 1 columns; what is per stream (mask row, ring slot, RoPE row) gets a stride, what is shared gets 0
+static bool match_attention_streams(const analysis & an, int pos, attn_group & grp) {
+    attn_chain c; rope_pair r;
+    if (!match_attention_chain(an, pos, c) || c.x2->op != GGML_OP_CONT) return false;
+    const ggml_tensor * kc = c.kc, * vc = c.vc, * mask = c.mask, * idx = c.idx, * x2 = c.x2;
     const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], B = kc->ne[3];
-    if (B < 2 || qo->ne[0] != D || qo->ne[1] != 1 || qo->ne[2] != H || qo->ne[3] != B) return false;
-    if (vc->ne[0] != D || vc->ne[1] != C || vc->ne[2] != H || vc->ne[3] != B) return false;
-    if (mask->type != GGML_TYPE_F32 || mask->ne[0] != C || mask->ne[1] != 1 || !ggml_is_contiguous(mask)) return false;
+    if (B < 2 || c.qo->ne[0] != D || c.qo->ne[1] != 1 || c.qo->ne[2] != H || c.qo->ne[3] != B || vc->ne[3] != B || mask->ne[1] != 1) return false;
     const bool mask_per_stream = mask->ne[2] == 1 && mask->ne[3] == B && ggml_nelements(mask) == C * B;   // one row per stream (slots)
     if (!mask_per_stream && ggml_nelements(mask) != C) return false;                                      // or one shared row
-    if (D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
-    if (kc->src[1] != vc->src[1]) return false;
-    const ggml_tensor * idx = kc->src[1];
-    if (idx->type != GGML_TYPE_I32 || !ggml_is_contiguous(idx)) return false;
     const bool index_per_stream = idx->ne[0] == 1 && idx->ne[1] == 1 && idx->ne[2] == B && ggml_nelements(idx) == B;   // one ring slot per stream (slots)
     if (!index_per_stream && ggml_nelements(idx) != 1) return false;                                                    // or one shared slot
-    if (kc->nb[0] != 2 || vc->nb[0] != 2) return false;
-
-    const ggml_tensor * ko = kc->src[0], * vrow = vc->src[0];
-    const ggml_tensor * qsrc = qo, * ksrc = ko, * rotr = nullptr, * roti = nullptr;
+    if (!match_rope_pair(c, r)) return false;
     int64_t rot_bs = 0;
-    if (qo->op == GGML_OP_CONCAT) {
-        const ggml_tensor * rotr2, * roti2;
-        if (!match_rope(qo, &qsrc, &rotr, &roti) || !match_rope(ko, &ksrc, &rotr2, &roti2) || rotr != rotr2 || roti != roti2) return false;
-        if (rotr->type != GGML_TYPE_F32 || rotr->ne[0] != D / 2 || rotr->ne[1] != 1 || (const char *) roti->data != (const char *) rotr->data + D / 2 * 4) return false;
-        if (rotr->nb[0] != 4) return false;
+    if (r.rotr) {
+        const ggml_tensor * rotr = r.rotr, * roti = r.roti;
+        if (rotr->ne[1] != 1) return false;
         if (ggml_nelements(rotr) == D / 2) rot_bs = 0;                                                            // one shared RoPE row
         else if (rotr->ne[2] == 1 && rotr->ne[3] == B && roti->type == GGML_TYPE_F32 && ggml_are_same_shape(rotr, roti) && roti->nb[3] == rotr->nb[3] &&
                  (int64_t) rotr->nb[3] == D * 4) rot_bs = D;                                                       // one row of the [D, B] table per stream
         else return false;
     }
-    if (qsrc->type != GGML_TYPE_F32 || ksrc->type != GGML_TYPE_F32 || vrow->type != GGML_TYPE_F32) return false;
-    for (const ggml_tensor * t : { qsrc, ksrc, vrow }) if (t->ne[0] != D || t->ne[1] != 1 || t->ne[2] != H || t->ne[3] != B) return false;
     sview qs, ks, vs;
-    if (!strided_resolve(qsrc, qs) || !strided_resolve(ksrc, ks) || !strided_resolve(vrow, vs)) return false;
-    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[0] != 4 || v->nb[2] % 4 != 0 || v->nb[3] % 4 != 0) return false;
+    if (!resolve_qkv(c, r, 1, B, qs, ks, vs)) return false;
+    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[2] % 4 != 0 || v->nb[3] % 4 != 0) return false;
     if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != 1 || x2->ne[3] != B || !ggml_is_contiguous(x2)) return false;
-
-    // the interior of the block, as match_attention collects it
-    std::vector<const ggml_tensor *> stack = { x2 };
     std::vector<int> members;
-    std::unordered_map<const ggml_tensor *, bool> seen;
-    int n_mm = 0, n_sm = 0, n_sr = 0;
-    const int lo = pos - 200 > 0 ? pos - 200 : 0;
-    while (!stack.empty()) {
-        const ggml_tensor * t = stack.back(); stack.pop_back();
-        if (seen[t]) continue;
-        seen[t] = true;
-        const int p = pos_of(an, t);
-        if (p < 0) continue;
-        if (t == mask || t == idx || t == rotr || t == roti) continue;
-        if ((const char *) t->data == nullptr) return false;
-        const bool is_input = (t->op == GGML_OP_MUL_MAT && t != kq && t != pv) || t->op == GGML_OP_TIMESTEP_EMBEDDING;
-        if (is_input) continue;
-        if (p < lo) return false;
-        switch (t->op) {
-            case GGML_OP_MUL_MAT: n_mm++; break;
-            case GGML_OP_SOFT_MAX: n_sm++; break;
-            case GGML_OP_SET_ROWS: n_sr++; break;
-            case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: case GGML_OP_CONT:
-            case GGML_OP_MUL: case GGML_OP_SUB: case GGML_OP_ADD: case GGML_OP_CONCAT: break;
-            default: return false;
-        }
-        members.push_back(p);
-        for (int s = 0; s < GGML_MAX_SRC; s++) if (t->src[s]) stack.push_back(t->src[s]);
-    }
-    if (n_mm != 2 || n_sm != 1 || n_sr != 2) return false;
-    std::unordered_map<int, bool> inside;
-    for (int p : members) inside[p] = true;
-    for (int i = 0; i < an.g->n_nodes; i++) {
-        if (inside.count(i)) continue;
-        const ggml_tensor * c = an.g->nodes[i];
-        for (int s = 0; s < GGML_MAX_SRC; s++) {
-            const ggml_tensor * t = c->src[s];
-            if (!t || t == x2) continue;
-            const int tp = pos_of(an, t);
-            if (tp >= 0 && inside.count(tp)) return false;
-        }
-    }
-    attn_args & a = grp.a;
-    memset(&a, 0, sizeof(a));
-    a.q = (const float *) qs.base; a.k = (const float *) ks.base; a.v = (const float *) vs.base;
-    a.q_hs = qs.nb[2] / 4; a.k_hs = ks.nb[2] / 4; a.v_hs = vs.nb[2] / 4;   // (T = 1: the row strides are never used)
-    a.rot = rotr ? (const float *) rotr->data : nullptr;
-    a.mask = (const float *) mask->data;
-    grp.mask_node = nullptr;
-    if (mask->op == GGML_OP_CONT && pos_of(an, mask) >= 0) {
-        const char * base = resolve_dense(mask);
-        if (base && base != (const char *) mask->data) { a.mask = (const float *) base; grp.mask_node = mask; }
-    }
-    a.index = (const int32_t *) idx->data;
-    a.kcache = (char *) kc->data; a.vcache = (char *) vc->data;
-    a.k_nb1 = (int64_t) kc->nb[1]; a.k_nb2 = (int64_t) kc->nb[2];
-    a.v_nb1 = (int64_t) vc->nb[1]; a.v_nb2 = (int64_t) vc->nb[2];
-    a.H = (int) H; a.D = (int) D; a.C = (int) C; a.T = 1;
-    a.scale = ggml_get_op_params_f32(sm, 0);
-    a.out = (float *) x2->data;
-    a.out_ts = H * D;
+    if (!collect_attention_interior(an, pos, c, r, false, members)) return false;
+    fill_attention_group(an, c, r, qs, ks, vs, members, grp);
+    grp.a.T = 1;   // (the row strides are never used)
     grp.B = (int) B;
-    grp.sa.a = a;
+    grp.sa.a = grp.a;
     grp.sa.B = (int) B;
     grp.sa.q_bs = qs.nb[3] / 4; grp.sa.k_bs = ks.nb[3] / 4; grp.sa.v_bs = vs.nb[3] / 4;
     grp.sa.kc_bs = (int64_t) kc->nb[3]; grp.sa.vc_bs = (int64_t) vc->nb[3];
@@ -1161,8 +1117,6 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     grp.sa.mask_bs = mask_per_stream ? C : 0;
     grp.sa.rot_bs = rot_bs;
     grp.sa.index_bs = index_per_stream ? 1 : 0;
-    grp.members = members;
-    grp.emit_pos = pos_of(an, x2);
     return true;
 }
 
@@ -1383,22 +1337,39 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
     return true;
 }
 
-// B'. cross-attention over a cached condition, ending at x2 = cont(permute(mul_mat(cont(transpose(V)), soft_max(mul_mat(K, q)))))
+// B'. cross-attention over a cached condition. THE CHAIN, walked once for both forms from the output node x2 at `pos`, an F32 `out_op` (cont or cpy) of
+//     x1 = permute(pv), pv = mul_mat(vt = cont(transpose(vx)), sm), sm = soft_max(kq = mul_mat(kx, qp)) without a mask and with max_bias 0. Guaranteed:
+//     x1, pv, vt, its transpose, sm and kq have one consumer each; the five members (x2, pv, vt, sm, kq) are nodes of the graph. What kx / vx / qp / x2 may be
+//     is the caller's.
+struct xattn_chain { const ggml_tensor * x2, * vx, * sm, * kx, * qp; };
+static bool match_cross_attention_chain(const analysis & an, int pos, enum ggml_op out_op, xattn_chain & c, std::vector<int> & members) {
+    c.x2 = an.g->nodes[pos];
+    if (c.x2->op != out_op || c.x2->type != GGML_TYPE_F32) return false;
+    const ggml_tensor * x1 = c.x2->src[0];
+    if (x1->op != GGML_OP_PERMUTE || uses_of(an, x1) != 1) return false;
+    const ggml_tensor * pv = x1->src[0];
+    if (pv->op != GGML_OP_MUL_MAT || uses_of(an, pv) != 1) return false;
+    const ggml_tensor * vt = pv->src[0];
+    c.sm = pv->src[1];
+    if (vt->op != GGML_OP_CONT || uses_of(an, vt) != 1 || vt->src[0]->op != GGML_OP_TRANSPOSE || uses_of(an, vt->src[0]) != 1) return false;
+    c.vx = vt->src[0]->src[0];
+    if (c.sm->op != GGML_OP_SOFT_MAX || uses_of(an, c.sm) != 1 || c.sm->src[1] != NULL || ggml_get_op_params_f32(c.sm, 1) != 0.0f) return false;
+    const ggml_tensor * kq = c.sm->src[0];
+    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1) return false;
+    c.kx = kq->src[0]; c.qp = kq->src[1];
+    members = { pos, pos_of(an, pv), pos_of(an, vt), pos_of(an, c.sm), pos_of(an, kq) };
+    for (int m : members) if (m < 0) return false;
+    return true;
+}
+
+//     B columns of cached state (B-column LM steps; B = 1: the single stream), ending at x2 = cont(..): K / V [D, Tc, H, B], q [D, 1, H, B] over a dense
+//     [D * H, B], x2 [D, H, 1, B] - one (head, column) workgroup each
 struct xattn_group : group { xattn_args a; };
 static bool match_cross_attention(const analysis & an, int pos, xattn_group & grp) {
-    const ggml_tensor * x2 = an.g->nodes[pos];
-    if (x2->op != GGML_OP_CONT || x2->type != GGML_TYPE_F32 || x2->src[0]->op != GGML_OP_PERMUTE || uses_of(an, x2->src[0]) != 1) return false;
-    const ggml_tensor * x1 = x2->src[0], * pv = x1->src[0];
-    if (pv->op != GGML_OP_MUL_MAT || uses_of(an, pv) != 1) return false;
-    const ggml_tensor * vt = pv->src[0], * sm = pv->src[1];
-    if (vt->op != GGML_OP_CONT || uses_of(an, vt) != 1 || vt->src[0]->op != GGML_OP_TRANSPOSE || uses_of(an, vt->src[0]) != 1) return false;
-    const ggml_tensor * vx = vt->src[0]->src[0];
-    if (sm->op != GGML_OP_SOFT_MAX || uses_of(an, sm) != 1 || sm->src[1] != NULL || ggml_get_op_params_f32(sm, 1) != 0.0f) return false;
-    const ggml_tensor * kq = sm->src[0];
-    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1) return false;
-    const ggml_tensor * kx = kq->src[0], * qp = kq->src[1];
+    xattn_chain c;
+    if (!match_cross_attention_chain(an, pos, GGML_OP_CONT, c, grp.members)) return false;
+    const ggml_tensor * x2 = c.x2, * kx = c.kx, * vx = c.vx, * qp = c.qp;
     if (kx->type != GGML_TYPE_F32 || vx->type != GGML_TYPE_F32 || !kx->data || !vx->data || pos_of(an, kx) >= 0 || pos_of(an, vx) >= 0) return false;   // cached state, not graph values
-    // B columns (B-column LM steps): K / V [D, Tc, H, B], q [D, 1, H, B] over a dense [D * H, B], x2 [D, H, 1, B] - one (head, column) workgroup each
     const int64_t D = kx->ne[0], Tc = kx->ne[1], H = kx->ne[2], B = kx->ne[3];
     if (D < 1 || D > 256 || Tc < 1 || H < 1 || B < 1 || B > 65535) return false;
     if (vx->ne[0] != D || vx->ne[1] != Tc || vx->ne[2] != H || vx->ne[3] != B || kx->nb[0] != 4 || vx->nb[0] != 4) return false;
@@ -1414,33 +1385,22 @@ static bool match_cross_attention(const analysis & an, int pos, xattn_group & gr
     a.k = (const char *) kx->data; a.v = (const char *) vx->data;
     a.k_nb1 = (int64_t) kx->nb[1]; a.k_nb2 = (int64_t) kx->nb[2]; a.v_nb1 = (int64_t) vx->nb[1]; a.v_nb2 = (int64_t) vx->nb[2];
     a.H = (int) H; a.D = (int) D; a.Tc = (int) Tc;
-    a.scale = ggml_get_op_params_f32(sm, 0);
+    a.scale = ggml_get_op_params_f32(c.sm, 0);
     a.out = (float *) x2->data;
     a.B = (int) B; a.q_cs = D * H; a.out_cs = D * H; a.k_nb3 = (int64_t) kx->nb[3]; a.v_nb3 = (int64_t) vx->nb[3];
-    grp.members = { pos, pos_of(an, pv), pos_of(an, vt), pos_of(an, sm), pos_of(an, kq) };
-    for (int m : grp.members) if (m < 0) return false;
     grp.emit_pos = pos;
     return true;
 }
 
-// B''. one job of a replay pass's cross-attention (moshi_hot.cpp cross_attention_jobs), ending at the copy into the job's rows of the layer's shared
-//      [D, H, T] tensor: x2 = cpy(permute(mul_mat(cont(transpose(V_b)), soft_max(mul_mat(K_b, q_j)))), rows), K_b / V_b = [D, Tc, H] views of one
-//      column of the cached [D, Tc, H, B] states, q_j = the job's rows of the layer's query projection [D * H, T] seen as [D, T_j, H]
+//     one job of a replay pass's cross-attention (moshi_hot.cpp cross_attention_jobs), ending at x2 = cpy(.., rows), the copy into the job's rows of the
+//     layer's shared [D, H, T] tensor: K_b / V_b = [D, Tc, H] views of one column of the cached [D, Tc, H, B] states, q_j = the job's rows of the layer's
+//     query projection [D * H, T] seen as [D, T_j, H]
 struct xattn_job_group : group { xattn_args a; xattn_block_job job; int64_t q_rs, out_rs; };
 static bool match_cross_attention_job(const analysis & an, int pos, xattn_job_group & grp) {
-    const ggml_tensor * x2 = an.g->nodes[pos];
-    if (x2->op != GGML_OP_CPY || x2->type != GGML_TYPE_F32 || !x2->data || !ggml_is_contiguous(x2)) return false;
-    const ggml_tensor * x1 = x2->src[0];
-    if (x1->op != GGML_OP_PERMUTE || uses_of(an, x1) != 1) return false;
-    const ggml_tensor * pv = x1->src[0];
-    if (pv->op != GGML_OP_MUL_MAT || uses_of(an, pv) != 1) return false;
-    const ggml_tensor * vt = pv->src[0], * sm = pv->src[1];
-    if (vt->op != GGML_OP_CONT || uses_of(an, vt) != 1 || vt->src[0]->op != GGML_OP_TRANSPOSE || uses_of(an, vt->src[0]) != 1) return false;
-    const ggml_tensor * vx = vt->src[0]->src[0];
-    if (sm->op != GGML_OP_SOFT_MAX || uses_of(an, sm) != 1 || sm->src[1] != NULL || ggml_get_op_params_f32(sm, 1) != 0.0f) return false;
-    const ggml_tensor * kq = sm->src[0];
-    if (kq->op != GGML_OP_MUL_MAT || uses_of(an, kq) != 1) return false;
-    const ggml_tensor * kx = kq->src[0], * qp = kq->src[1];
+    xattn_chain c;
+    if (!match_cross_attention_chain(an, pos, GGML_OP_CPY, c, grp.members)) return false;
+    const ggml_tensor * x2 = c.x2, * kx = c.kx, * vx = c.vx, * qp = c.qp;
+    if (!x2->data || !ggml_is_contiguous(x2)) return false;
     // K / V: whole-column views of cached states (leaves of the graph), F32 [D, Tc, H]
     for (const ggml_tensor * t : { kx, vx }) {
         if (t->op != GGML_OP_VIEW || !t->view_src || !t->data || t->type != GGML_TYPE_F32 || uses_of(an, t) != 1) return false;
@@ -1471,10 +1431,9 @@ static bool match_cross_attention_job(const analysis & an, int pos, xattn_job_gr
     a.q = nullptr; a.k = nullptr; a.v = nullptr; a.out = nullptr;
     a.k_nb1 = (int64_t) kx->nb[1]; a.k_nb2 = (int64_t) kx->nb[2]; a.v_nb1 = (int64_t) vx->nb[1]; a.v_nb2 = (int64_t) vx->nb[2];
     a.H = (int) H; a.D = (int) D; a.Tc = (int) Tc;
-    a.scale = ggml_get_op_params_f32(sm, 0);
+    a.scale = ggml_get_op_params_f32(c.sm, 0);
     grp.job = { (const float *) qp->data, (const char *) kx->data, (const char *) vx->data, (float *) x2->data, (int) Tn };
     grp.q_rs = D * H; grp.out_rs = D * H;
-    grp.members = { pos, pos_of(an, pv), pos_of(an, vt), pos_of(an, sm), pos_of(an, kq) };
     grp.emit_pos = pos;
     return true;
 }
@@ -2316,6 +2275,18 @@ static bool claim_group(planner & pl, const group & grp, int self = -1) {
     return true;
 }
 
+// What the run-packers share (pass_cross_attention_blocks, pass_column_attention_rows, merge_column_attention_blocks): groups may share a launch emitted
+// at the last of them only if nothing but layout nodes and members of `inside` stands strictly between positions lo and hi ...
+static bool clean_between(const planner & pl, int lo, int hi, const std::set<int> & inside) {
+    for (int i = lo + 1; i < hi; i++) if (!is_view_op(pl.g->nodes[i]->op) && !inside.count(i)) return false;
+    return true;
+}
+// ... and, for attention groups, only if they agree on everything a launch holds once for all its jobs
+static bool same_attention_shape(const attn_args & a, const attn_args & b) {
+    return b.H == a.H && b.D == a.D && b.C == a.C && b.scale == a.scale && b.out_ts == a.out_ts && (b.rot != nullptr) == (a.rot != nullptr) &&
+           b.q_hs == a.q_hs && b.k_hs == a.k_hs && b.v_hs == a.v_hs && b.k_nb1 == a.k_nb1 && b.k_nb2 == a.k_nb2 && b.v_nb1 == a.v_nb1 && b.v_nb2 == a.v_nb2;
+}
+
 // the extra heads of a B-column stt step: every head's mul_mat -> soft_max -> cpy in one launch
 static void pass_heads_streams(planner & pl) {
     static const bool no_heads = getenv("MI355X_NO_HEADS_FUSION") != nullptr;
@@ -2450,9 +2421,7 @@ static void pass_cross_attention_blocks(planner & pl) {
             const xattn_args & a = ba.a, & b = grp.a;
             bool joins = ba.n_jobs < XATTN_BLOCKS_MAX && b.H == a.H && b.D == a.D && b.Tc == a.Tc && b.scale == a.scale && b.k_nb1 == a.k_nb1 && b.k_nb2 == a.k_nb2 &&
                          b.v_nb1 == a.v_nb1 && b.v_nb2 == a.v_nb2 && grp.q_rs == ba.q_rs && grp.out_rs == ba.out_rs;
-            const std::set<int> inside(grp.members.begin(), grp.members.end());
-            for (int k = hi + 1; k < i && joins; k++) if (!is_view_op(pl.g->nodes[k]->op) && !inside.count(k)) joins = false;
-            if (!joins) flush();
+            if (!joins || !clean_between(pl, hi, i, std::set<int>(grp.members.begin(), grp.members.end()))) flush();
         }
         claim_group(pl, grp);
         if (!ba.n_jobs) { ba.a = grp.a; ba.q_rs = grp.q_rs; ba.out_rs = grp.out_rs; }
@@ -2728,15 +2697,7 @@ static void pass_column_attention_rows(planner & pl) {
     std::vector<size_t> order;   // the column groups in emit order (the order their outputs stand in the graph)
     for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1) order.push_back(i);
     std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return groups[x].emit_pos < groups[y].emit_pos; });
-    auto same_shape = [](const attn_args & a, const attn_args & b) {
-        return b.T == 1 && b.H == a.H && b.D == a.D && b.C == a.C && b.scale == a.scale && b.out_ts == a.out_ts && (b.rot != nullptr) == (a.rot != nullptr) &&
-               b.q_hs == a.q_hs && b.k_hs == a.k_hs && b.v_hs == a.v_hs && b.k_nb1 == a.k_nb1 && b.k_nb2 == a.k_nb2 && b.v_nb1 == a.v_nb1 && b.v_nb2 == a.v_nb2;
-    };
-    // only layout nodes and members of `inside` between two emit positions
-    auto clean_between = [&](int lo, int hi, const std::set<int> & inside) {
-        for (int i = lo + 1; i < hi; i++) if (!is_view_op(pl.g->nodes[i]->op) && !inside.count(i)) return false;
-        return true;
-    };
+    auto same_shape = [](const attn_args & a, const attn_args & b) { return b.T == 1 && same_attention_shape(a, b); };   // rows: one-row groups only
     auto stride = [](const void * a, const void * b) { return (int64_t) ((const char *) b - (const char *) a); };
     attn_rows_args ra;
     int launch_hi = -1;           // emit position of the launch being filled (ra.n_jobs > 0)
@@ -2772,7 +2733,7 @@ static void pass_column_attention_rows(planner & pl) {
                 if (d[0] % 4 || d[1] % 4 || d[2] % 4 || d[3] % 4 || d[4] % 4 || d[5] % 4 || d[6] % 4) break;
                 std::set<int> both = inside;
                 both.insert(gn.members.begin(), gn.members.end());
-                if (!clean_between(hi, gn.emit_pos, both)) break;
+                if (!clean_between(pl, hi, gn.emit_pos, both)) break;
                 inside.swap(both); hi = gn.emit_pos;
                 oe++;
             }
@@ -2786,7 +2747,7 @@ static void pass_column_attention_rows(planner & pl) {
             if (joins) {
                 std::set<int> both = inside;
                 both.insert(rows_inside.begin(), rows_inside.end());
-                joins = clean_between(launch_hi, g0.emit_pos, both);
+                joins = clean_between(pl, launch_hi, g0.emit_pos, both);
             }
             if (!joins) flush();
         }
@@ -2817,9 +2778,7 @@ static void merge_column_attention_blocks(planner & pl) {
         while (ge < attn_groups.size() && ge - gi < ATTN_BLOCKS_MAX) {
             const attn_group & n = attn_groups[ge];
             const attn_args & b = n.a;
-            if (!n.column || n.emit_pos < 0 || b.H != a0.H || b.D != a0.D || b.C != a0.C || b.scale != a0.scale || b.out_ts != a0.out_ts || (b.rot != nullptr) != (a0.rot != nullptr) ||
-                (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts)) || b.q_hs != a0.q_hs || b.k_hs != a0.k_hs || b.v_hs != a0.v_hs ||
-                b.k_nb1 != a0.k_nb1 || b.k_nb2 != a0.k_nb2 || b.v_nb1 != a0.v_nb1 || b.v_nb2 != a0.v_nb2) break;
+            if (!n.column || n.emit_pos < 0 || !same_attention_shape(a0, b) || (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts))) break;
             // a launch pair never holds two groups of one ring column: it writes every job's rows before any job attends, so a second group of a column
             // (a ring-ordered row after its predecessor, where pass_column_attention_rows is off or has declined the run) must start a launch of its own
             bool column_taken = false;
@@ -2828,9 +2787,7 @@ static void merge_column_attention_blocks(planner & pl) {
             std::set<int> both = inside;
             both.insert(n.members.begin(), n.members.end());
             const int nlo = n.emit_pos < lo ? n.emit_pos : lo, nhi = n.emit_pos > hi ? n.emit_pos : hi;
-            bool clean = true;
-            for (int i = nlo + 1; i < nhi && clean; i++) if (!is_view_op(pl.g->nodes[i]->op) && !both.count(i)) clean = false;
-            if (!clean) break;
+            if (!clean_between(pl, nlo, nhi, both)) break;
             inside.swap(both); lo = nlo; hi = nhi;
             if (b.T > 1 && !rows) rows = &b;
             ge++;
