@@ -64,7 +64,7 @@ def quant_q80(x):
     d = (amax / np.float32(127.0)).astype(np.float32)
     idv = np.where(d != 0, np.float32(1.0) / np.where(d != 0, d, 1), 0).astype(np.float32)
     p = (xb * idv[:, None]).astype(np.float32)
-    q = (np.sign(p) * np.floor(np.abs(p) + np.float32(0.5))).astype(np.int32)
+    q = (np.sign(p) * np.floor(np.abs(p).astype(np.float64) + 0.5)).astype(np.int32)   # roundf: |p| + 0.5 in float32 would round 0.5 - 2^-25 up to 1
     return q, d.astype(np.float16).astype(np.float32)
 
 
