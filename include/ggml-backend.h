@@ -133,6 +133,8 @@ struct ggml_mi355x_stats {
     int64_t float_acc_mms_in_last_plan;         // k_mm_f32acc_batched launches of the last plan (the same products on float-accumulating BF16 / F16 MFMA tiles, set_float_accumulate)
     int64_t pass_input_launches_in_last_plan;   // k_pass_input launches of the last plan (persona passes: the voice rows and embedding sums of a [dim, T] input in one launch) ...
     int64_t pass_input_rows_in_last_plan;       // ... and the rows they write
+    int64_t convtr_column_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan (decoder slots: the B convtr + copy nodes of a SEANet layer and their shared streaming tail as one partial and one finish launch)
+    int64_t codec_attn_launches_in_last_plan;   // k_attn_codec_slots launches of the last plan (decoder slots: the 2-row attention of every (column, head) pair of a layer in one launch)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

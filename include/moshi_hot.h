@@ -307,6 +307,31 @@ GGML_API int moshi_hot_slot_persona(moshi_hot_model_t * m, int b, const struct m
 // Persona caching: a persona costs a few passes once - admit it into a spare slot, moshi_hot_slot_save the slot, and moshi_hot_slot_load the blob into a
 // closed slot for every caller that wants that persona (one copy of the ring rows instead of the passes).
 
+// ---- decoder slots: the Mimi decode of B conversations in one pass ---------------------------------------------------------------------------------
+// The codec's counterpart of a slots model: one set of decoder weights, B columns, each a conversation's streaming decoder state - conv tails and
+// transposed-conv partials [len, C, B], the decoder transformer's K / V rings [D, 250, H, B] and a position of its own. The graph is mimi_decode's
+// (compression.h:156-187) with the reference's batch dimension made real; the four SEANet transposed convolutions, which ggml takes as matrices only,
+// are B matrix nodes on the column views. On the oracle slot b's PCM is bit-identical to a fresh single-stream codec-only model (moshi_hot_create with
+// enable_lm = 0) fed the same codes frame by frame, whatever the other slots do.
+// Requires enable_lm = 0, enable_mimi_decoder = 1, enable_mimi_encoder = 0, codec_stream = 0 and 2 <= n_slots <= 16 (wide_streams = 1:
+// <= MOSHI_HOT_MAX_STREAMS); anything else, or a state that does not fit the device, returns NULL. The weights are those moshi_hot_create makes for
+// the same cfg and seed, under the same names. All slots start closed. moshi_hot_n_streams returns B. Every other frame call (moshi_hot_mimi_decode /
+// _encode, moshi_hot_lm_step*, moshi_hot_sts_*, the LM slot calls) refuses as on a B > 1 LM model; the calls below return -1 (or do nothing) on any other model.
+GGML_API moshi_hot_model_t * moshi_hot_create_codec_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots);
+// slot b starts a new conversation: column b of every conv tail and transposed-conv partial is zeroed, its decoder-transformer position is 0. Its
+// ring rows are not cleared (the mask admits only rows the new conversation has written). Returns 0, or -1 for a bad index or another kind of model.
+GGML_API int moshi_hot_codec_slot_open(moshi_hot_model_t * m, int b);
+GGML_API int moshi_hot_codec_slot_close(moshi_hot_model_t * m, int b);   // 0, or -1 as moshi_hot_codec_slot_open
+// frames decoded since slot b was opened (unless moshi_hot_codec_slot_set_fill moved it), -1 if it is closed or b is bad
+GGML_API int64_t moshi_hot_codec_slot_position(moshi_hot_model_t * m, int b);
+// moves slot b's decoder-transformer position only, in frames (2 ring rows each), not its conv states (tests and benchmarks)
+GGML_API void moshi_hot_codec_slot_set_fill(moshi_hot_model_t * m, int b, int64_t frames);
+// one frame of every open slot: codes = B x mimi_n_q (slot-major), pcm = B x 1920, status = B entries: 1 for a decoded slot, -1 for a closed one, whose
+// codes are ignored and whose pcm row is written as zeros (it is computed frozen on code 0; the next open resets its state). Returns the number of
+// slots decoded; 0 with no device work when none is open; -1 with nothing changed on another kind of model or when an open slot has a code outside
+// [0, mimi_codebook_size).
+GGML_API int moshi_hot_mimi_decode_slots(moshi_hot_model_t * m, const int32_t * codes, float * pcm, int32_t * status);
+
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute
 // (src/context.h:456-480, moshi/utils/sampling.h:4-64). By default that noise comes from libc rand() in one sweep over the whole [k, B] tensor, so a

@@ -342,7 +342,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -887,7 +887,9 @@ static bool match_norm_affine(const analysis & an, int pos, norm_affine_group & 
 //                     RoPE phase, output [D, H, 1, B] - one launch of B x H workgroups, k_attn_streams (match_attention_streams)
 //      slots          the same with every column at its own position (moshi_hot_create_slots): a mask [C, 1, 1, B] (one contiguous row per stream), an index [1, 1, B]
 //                     (one ring slot per stream), RoPE halves [D/2, 1, 1, B] (one timestep-table row per stream) - the same launch with per-stream strides
-//      Refused today: several rows of several columns at once, and a copy into rows from anything but a ring column.
+//      decoder slots  T = 2 rows of B > 1 columns, every column at its own position (moshi_hot_create_codec_slots): mask [C, T, 1, B], index [T, 1, B], RoPE halves
+//                     [D/2, T, 1, B] - one launch of H x T x B workgroups, k_attn_codec_slots (match_attention_codec_slots; the codec transformers' shape only)
+//      Refused today: several rows of several columns at once in any other shape, and a copy into rows from anything but a ring column.
 struct attn_group : group { attn_args a; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
                           bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
 
@@ -1117,6 +1119,44 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     grp.sa.mask_bs = mask_per_stream ? C : 0;
     grp.sa.rot_bs = rot_bs;
     grp.sa.index_bs = index_per_stream ? 1 : 0;
+    return true;
+}
+
+// the decoder-slots form: Tn = 2 rows of B > 1 columns (moshi_hot.cpp transformer_graph_build_codec_slots) - mask [C, Tn, 1, B], index [Tn, 1, B] and the
+// RoPE table [D, Tn * B] viewed as [D/2, Tn, 1, B] halves, each column's block dense and one behind the other
+static bool match_attention_codec_slots(const analysis & an, int pos, attn_group & grp) {
+    attn_chain c; rope_pair r;
+    if (!match_attention_chain(an, pos, c) || c.x2->op != GGML_OP_CONT) return false;
+    const ggml_tensor * kc = c.kc, * vc = c.vc, * mask = c.mask, * idx = c.idx, * x2 = c.x2;
+    const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], B = kc->ne[3], Tn = c.qo->ne[1];
+    if (B < 2 || Tn < 2 || c.qo->ne[0] != D || c.qo->ne[2] != H || c.qo->ne[3] != B || vc->ne[3] != B) return false;
+    if (mask->ne[1] != Tn || mask->ne[2] != 1 || mask->ne[3] != B || ggml_nelements(mask) != C * Tn * B) return false;
+    if (idx->ne[0] != Tn || idx->ne[1] != 1 || idx->ne[2] != B || ggml_nelements(idx) != Tn * B) return false;
+    if (!match_rope_pair(c, r)) return false;
+    if (r.rotr) {
+        const ggml_tensor * rotr = r.rotr, * roti = r.roti;
+        if (rotr->ne[1] != Tn || rotr->ne[2] != 1 || rotr->ne[3] != B || roti->type != GGML_TYPE_F32 || !ggml_are_same_shape(rotr, roti) || roti->nb[3] != rotr->nb[3] ||
+            roti->nb[1] != rotr->nb[1] || (int64_t) rotr->nb[1] != D * 4 || (int64_t) rotr->nb[3] != D * 4 * Tn) return false;
+    }
+    sview qs, ks, vs;
+    if (!resolve_qkv(c, r, Tn, B, qs, ks, vs)) return false;
+    for (const sview * v : { &qs, &ks, &vs }) if (v->nb[1] % 4 != 0 || v->nb[2] % 4 != 0 || v->nb[3] % 4 != 0) return false;
+    if (x2->ne[0] != D || x2->ne[1] != H || x2->ne[2] != Tn || x2->ne[3] != B || !ggml_is_contiguous(x2)) return false;
+    std::vector<int> members;
+    if (!collect_attention_interior(an, pos, c, r, false, members)) return false;
+    fill_attention_group(an, c, r, qs, ks, vs, members, grp);
+    grp.a.T = (int) Tn;
+    grp.a.q_ts = qs.nb[1] / 4; grp.a.k_ts = ks.nb[1] / 4; grp.a.v_ts = vs.nb[1] / 4;
+    if (grp.mask_node || !k_attn_codec_slots_supported(grp.a)) return false;   // (the mask is a graph input, never a copy made in this graph)
+    grp.B = (int) B;
+    grp.sa.a = grp.a;
+    grp.sa.B = (int) B;
+    grp.sa.q_bs = qs.nb[3] / 4; grp.sa.k_bs = ks.nb[3] / 4; grp.sa.v_bs = vs.nb[3] / 4;
+    grp.sa.kc_bs = (int64_t) kc->nb[3]; grp.sa.vc_bs = (int64_t) vc->nb[3];
+    grp.sa.out_bs = Tn * H * D;
+    grp.sa.mask_bs = C * Tn;
+    grp.sa.rot_bs = D * Tn;
+    grp.sa.index_bs = Tn;
     return true;
 }
 
@@ -1740,26 +1780,63 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
     return true;
 }
 
+// D'. a codec convolution at B > 1 columns (decoder slots, moshi_hot.cpp conv_1d_bias): im2col [K, OW, B] F16 -> reshape -> mul_mat(., reshape(w)) ->
+//     the strided [OW, OC, B] view of the [OW * B, OC] product -> + bias (or cont). The im2col node keeps its own launch (it carries the batch dimension
+//     as it is); the product, the view and the add / cont become one launch that stores in the final layout (k_conv_cols).
+static bool match_conv_columns(const analysis & an, int pos, step_group & grp) {
+    const ggml_tensor * mm = an.g->nodes[pos];
+    if (mm->op != GGML_OP_MUL_MAT || mm->type != GGML_TYPE_F32 || uses_of(an, mm) != 1) return false;
+    const ggml_tensor * ra = mm->src[0], * rw = mm->src[1];
+    if (ra->op != GGML_OP_RESHAPE || rw->op != GGML_OP_RESHAPE || uses_of(an, ra) != 1 || uses_of(an, rw) != 1) return false;
+    const ggml_tensor * im = ra->src[0], * w = rw->src[0];
+    if (im->op != GGML_OP_IM2COL || im->src[0] != w || im->type != GGML_TYPE_F16 || w->type != GGML_TYPE_F16 || !ggml_is_contiguous(w) || !ggml_is_contiguous(im)) return false;
+    const int64_t K = im->ne[0], OW = im->ne[1], B = im->ne[2], OC = w->ne[2];
+    if (B < 2 || im->ne[3] != 1 || w->ne[3] != 1 || w->ne[0] * w->ne[1] != K || uses_of(an, im) != 1 || !im->data || !w->data) return false;
+    if (ra->ne[0] != K || ra->ne[1] != OW * B || rw->ne[0] != K || rw->ne[1] != OC || ra->data != im->data || rw->data != w->data) return false;
+    const ggml_tensor * vw = sole_consumer(an, mm);
+    if (!vw || vw->op != GGML_OP_VIEW || vw->data != mm->data || vw->ne[0] != OW || vw->ne[1] != OC || vw->ne[2] != B || vw->ne[3] != 1 || vw->nb[0] != 4 ||
+        (int64_t) vw->nb[1] != OW * B * 4 || (int64_t) vw->nb[2] != OW * 4 || uses_of(an, vw) != 1) return false;
+    const ggml_tensor * out = sole_consumer(an, vw);
+    const float * bias = nullptr;
+    if (!out) return false;
+    if (out->op == GGML_OP_ADD && !out->view_src && out->src[0] == vw && out->src[1]->op == GGML_OP_NONE && out->src[1]->type == GGML_TYPE_F32 && out->src[1]->ne[0] == 1 &&
+        out->src[1]->ne[1] == OC && ggml_nelements(out->src[1]) == OC && ggml_is_contiguous(out->src[1]) && out->src[1]->data) bias = (const float *) out->src[1]->data;
+    else if (out->op != GGML_OP_CONT) return false;
+    if (out->type != GGML_TYPE_F32 || !ggml_is_contiguous(out) || !out->data || out->ne[0] != OW || out->ne[1] != OC || out->ne[2] != B || out->ne[3] != 1) return false;
+    if (K > INT32_MAX || OW * B > INT32_MAX || OC > INT32_MAX) return false;
+    grp.members = { pos_of(an, ra), pos_of(an, rw), pos, pos_of(an, vw), pos_of(an, out) };
+    for (int m : grp.members) if (m < 0 || an.skip[(size_t) m]) return false;
+    float * dst = (float *) out->data; const void * ap = im->data, * wp = w->data;
+    const int Kn = (int) K, OWn = (int) OW, OCn = (int) OC, Bn = (int) B;
+    grp.steps.clear();
+    grp.steps.push_back([=](hipStream_t s) { k_conv_cols(s, dst, ap, wp, bias, Kn, OWn, OCn, Bn); });
+    grp.emit_pos = pos_of(an, out);
+    return true;
+}
+
 // E. streaming conv_transpose_1d (conv.h:240-310): [elu] -> conv_transpose_1d -> add_inplace(view lower, view prev tail) -> view full
 //    -> cpy(., prev) [-> + bias] -> view(window) -> cont  becomes the partial products + one finishing kernel.
 struct convtr_tail { const ggml_tensor * prev, * out; const float * bias; int PT; std::vector<int> members; };
 
-// the streaming tail shared by the dense and the depthwise transposed conv: y is the freshly computed [OLf, OC] block
-static bool match_convtr_tail(const analysis & an, const ggml_tensor * y, convtr_tail & t) {
-    if (uses_of(an, y) != 1) return false;
-    const int64_t OLf = y->ne[0], OC = y->ne[1];
-    const ggml_tensor * lower = sole_consumer(an, y);
-    if (!lower || lower->op != GGML_OP_VIEW || lower->data != y->data || lower->ne[1] != OC) return false;
+// the streaming tail shared by the dense and the depthwise transposed conv: y is the freshly computed [OLf, OC] block - or, decoder slots, the
+// [OLf, OC, B] tensor the B column products were copied into, `lower` then being the one consumer of y that is not a copy's destination
+static bool match_convtr_tail(const analysis & an, const ggml_tensor * y, convtr_tail & t, const ggml_tensor * lower_of_columns = nullptr) {
+    if (!lower_of_columns && uses_of(an, y) != 1) return false;
+    const int64_t OLf = y->ne[0], OC = y->ne[1], B = y->ne[2];
+    if (y->ne[3] != 1 || (B != 1 && !lower_of_columns)) return false;
+    const ggml_tensor * lower = lower_of_columns ? lower_of_columns : sole_consumer(an, y);
+    if (!lower || lower->op != GGML_OP_VIEW || lower->data != y->data || lower->ne[1] != OC || lower->ne[2] != B || lower->nb[1] != y->nb[1] || lower->nb[2] != y->nb[2]) return false;
     const int64_t PT = lower->ne[0];
     const ggml_tensor * ai = sole_consumer(an, lower);
     if (!ai || ai->op != GGML_OP_ADD || ai->src[0] != lower || ai->data != lower->data) return false;
     const ggml_tensor * partial = ai->src[1];
     if (partial->op != GGML_OP_VIEW || partial->src[0]->op != GGML_OP_NONE || uses_of(an, partial) != 1) return false;
     const ggml_tensor * prev = partial->src[0];
-    if (prev->type != GGML_TYPE_F32 || !ggml_is_contiguous(prev) || prev->ne[0] != OLf || prev->ne[1] != OC || ggml_nelements(prev) != OLf * OC) return false;
-    if (partial->ne[0] != PT || partial->ne[1] != OC || (const char *) partial->data - (const char *) prev->data != (OLf - PT) * 4 || partial->nb[1] != prev->nb[1]) return false;
+    if (prev->type != GGML_TYPE_F32 || !ggml_is_contiguous(prev) || prev->ne[0] != OLf || prev->ne[1] != OC || ggml_nelements(prev) != OLf * OC * B) return false;
+    if (partial->ne[0] != PT || partial->ne[1] != OC || partial->ne[2] != B || (const char *) partial->data - (const char *) prev->data != (OLf - PT) * 4 || partial->nb[1] != prev->nb[1] ||
+        partial->nb[2] != prev->nb[2]) return false;
     const ggml_tensor * full = sole_consumer(an, ai);
-    if (!full || full->op != GGML_OP_VIEW || full->data != y->data || full->ne[0] != OLf || full->ne[1] != OC) return false;
+    if (!full || full->op != GGML_OP_VIEW || full->data != y->data || full->ne[0] != OLf || full->ne[1] != OC || full->ne[2] != B) return false;
     const ggml_tensor * cp = sole_consumer(an, full);
     if (!cp || cp->op != GGML_OP_CPY || cp->src[1] != prev) return false;
     const ggml_tensor * cur = sole_consumer(an, cp);
@@ -1771,7 +1848,7 @@ static bool match_convtr_tail(const analysis & an, const ggml_tensor * y, convtr
         t.members.push_back(pos_of(an, cur));
         cur = sole_consumer(an, cur);
     }
-    if (!cur || cur->op != GGML_OP_VIEW || cur->ne[0] != OLf - PT || cur->ne[1] != OC || cur->data != cur->src[0]->data) return false;
+    if (!cur || cur->op != GGML_OP_VIEW || cur->ne[0] != OLf - PT || cur->ne[1] != OC || cur->ne[2] != B || cur->data != cur->src[0]->data) return false;
     const ggml_tensor * out = sole_consumer(an, cur);
     if (!out || out->op != GGML_OP_CONT || !ggml_is_contiguous(out) || !out->data) return false;
     t.members.push_back(pos_of(an, cur)); t.members.push_back(pos_of(an, out));
@@ -1810,6 +1887,68 @@ static bool match_convtr(const analysis & an, int pos, step_group & grp, emitter
     return true;
 }
 
+// E'. the same at B columns (decoder slots, moshi_hot.cpp streaming_conv_transpose): for b = 0 .. B - 1, in graph order, conv_transpose_1d(w, view of
+//     column b of x) copied into column b of one [OLf, OC, B] tensor y that no node computes, then the streaming tail ONCE over the B columns of y and of
+//     prev. Matched at column 0's conv_transpose_1d; all of it becomes one partial launch over the B x L positions and one finish launch (k_convtr_cols).
+static bool match_convtr_columns(const analysis & an, int pos, step_group & grp, emitter & em) {
+    const ggml_cgraph * g = an.g;
+    const ggml_tensor * ct0 = g->nodes[pos];
+    if (ct0->op != GGML_OP_CONV_TRANSPOSE_1D || uses_of(an, ct0) != 1) return false;
+    const ggml_tensor * cp0 = sole_consumer(an, ct0);
+    if (!cp0 || cp0->op != GGML_OP_CPY || cp0->src[0] != ct0 || cp0->src[1]->op != GGML_OP_VIEW) return false;
+    const ggml_tensor * y = cp0->src[1]->src[0];
+    if (y->op != GGML_OP_NONE || pos_of(an, y) >= 0 || y->type != GGML_TYPE_F32 || !ggml_is_contiguous(y) || !y->data || y->ne[3] != 1 || cp0->src[1]->data != y->data) return false;
+    const ggml_tensor * w = ct0->src[0], * xv0 = ct0->src[1];
+    if (xv0->op != GGML_OP_VIEW) return false;
+    const ggml_tensor * x = xv0->src[0];
+    const int64_t B = y->ne[2];
+    const int K = (int) w->ne[0], OC = (int) w->ne[1], s0 = ct0->op_params[0], L = (int) xv0->ne[0], PT = K - s0;
+    if (B < 2 || x->ne[2] != B || x->ne[3] != 1 || x->ne[0] != L || x->ne[1] != w->ne[2] || xv0->data != x->data || xv0->nb[1] != x->nb[1] || x->type != GGML_TYPE_F32 || !x->data) return false;
+    if (PT <= 0 || PT > L * s0 || !(w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_F32) || (int64_t) w->nb[1] != (int64_t) w->nb[0] * K) return false;
+    if (y->ne[0] != (int64_t) (L - 1) * s0 + K || y->ne[1] != OC) return false;
+    // the B products and copies, consecutive in graph order
+    std::vector<int> members;
+    int at = pos;
+    for (int64_t b = 0; b < B; b++) {
+        // (view of x's column, conv_transpose_1d, view of y's column, cpy - the two views in either order)
+        int p_ct = -1;
+        for (int i = at; i < g->n_nodes && i < at + 4; i++) if (g->nodes[i]->op == GGML_OP_CONV_TRANSPOSE_1D) { p_ct = i; break; } else if (g->nodes[i]->op != GGML_OP_VIEW) break;
+        if (p_ct < 0) return false;
+        const ggml_tensor * ct = g->nodes[p_ct];
+        const ggml_tensor * cp = uses_of(an, ct) == 1 ? sole_consumer(an, ct) : nullptr;
+        if (!cp || cp->op != GGML_OP_CPY || cp->src[0] != ct || uses_of(an, cp) != 0 || pos_of(an, cp) > p_ct + 2) return false;
+        const ggml_tensor * xv = ct->src[1], * yv = cp->src[1];
+        if (ct->src[0] != w || ct->op_params[0] != s0 || xv->op != GGML_OP_VIEW || xv->src[0] != x || uses_of(an, xv) != 1 || xv->ne[0] != L || xv->ne[1] != x->ne[1] || xv->nb[1] != x->nb[1] ||
+            (const char *) xv->data - (const char *) x->data != b * (int64_t) x->nb[2]) return false;
+        if (yv->op != GGML_OP_VIEW || yv->src[0] != y || uses_of(an, yv) != 1 || yv->ne[0] != y->ne[0] || yv->ne[1] != OC || yv->nb[1] != y->nb[1] ||
+            (const char *) yv->data - (const char *) y->data != b * (int64_t) y->nb[2]) return false;
+        for (const ggml_tensor * t : { xv, ct, yv, cp }) members.push_back(pos_of(an, t));
+        at = pos_of(an, cp) + 1;
+    }
+    // the tail's first node: the consumer of y behind the copies that is not a copy's destination
+    const ggml_tensor * lower = nullptr;
+    for (int i = at; i < g->n_nodes && i < at + 4 && !lower; i++) if (g->nodes[i]->op == GGML_OP_VIEW && g->nodes[i]->src[0] == y) lower = g->nodes[i];
+    if (!lower || uses_of(an, y) != (int) B + 1) return false;
+    convtr_tail t;
+    if (!match_convtr_tail(an, y, t, lower) || t.PT != PT) return false;
+    for (int m : t.members) members.push_back(m);
+    int pre_elu = 0;
+    const ggml_tensor * xin = x;
+    if (is_elu(xin) && uses_of(an, xin) == (int) B && pos_of(an, xin) >= 0) { pre_elu = 1; members.push_back(pos_of(an, xin)); xin = xin->src[0]; }
+    if (!xin->data || xin->type != GGML_TYPE_F32 || xin->ne[2] != B) return false;
+    if (t.out->type != GGML_TYPE_F32 || t.out->ne[0] != (int64_t) L * s0 || t.out->ne[1] != OC || t.out->ne[2] != B) return false;
+    for (int m : members) if (m < 0 || an.skip[(size_t) m]) return false;
+    void * ws = em.ws(k_convtr_cols_ws_size(w, L, B));
+    const tdesc d_w = make_tdesc(w), d_x = make_tdesc(xin), d_out = make_tdesc(t.out);
+    float * pv = (float *) t.prev->data;
+    const float * bias = t.bias;
+    grp.steps.clear();
+    grp.steps.push_back([=](hipStream_t s) { k_convtr_cols(s, d_out, pv, bias, d_w, d_x, s0, pre_elu, ws); });
+    grp.members = members;
+    grp.emit_pos = pos_of(an, t.out);
+    return true;
+}
+
 // E2. depthwise streaming conv_transpose_1d on a single frame (the 12.5 -> 25 Hz upsampler, conv.h:262-278): one multiply per
 //     kernel tap, concatenated, then the same streaming tail
 static bool match_dw_convtr(const analysis & an, int pos, step_group & grp) {
@@ -1826,7 +1965,7 @@ static bool match_dw_convtr(const analysis & an, int pos, step_group & grp) {
     }
     pieces.insert(pieces.begin(), cur);
     const int K = (int) pieces.size();
-    if (K < 2 || K > 16 || y->ne[0] != K) return false;
+    if (K < 2 || K > 16 || y->ne[0] != K || y->ne[2] != 1 || y->ne[3] != 1) return false;   // (one column: the B-column upsample of decoder slots runs node by node)
     const int64_t C = y->ne[1];
     const ggml_tensor * x = nullptr, * w = nullptr;
     for (int k = 0; k < K; k++) {
@@ -2319,7 +2458,7 @@ static void pass_attention(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
         attn_group grp;
-        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp)) continue;
+        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp) && !match_attention_codec_slots(pl.an, i, grp)) continue;
         if (claim_group(pl, grp)) pl.attn_groups.push_back(grp);
     }
     // mask copies that every consumer now bypasses (NOT the claim rule: the copy is no matcher's member, and it is marked and counted as it always was,
@@ -2334,13 +2473,18 @@ static void pass_codec_convs(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i]) continue;
         step_group grp;
+        bool convtr_columns = false;
         const enum ggml_op op = pl.g->nodes[i]->op;
-        if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em)) continue; }
-        else if (op == GGML_OP_CONV_TRANSPOSE_1D) { if (!match_convtr(pl.an, i, grp, pl.em)) continue; }
+        if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em) && !match_conv_columns(pl.an, i, grp)) continue; }
+        else if (op == GGML_OP_CONV_TRANSPOSE_1D) {
+            if (match_convtr_columns(pl.an, i, grp, pl.em)) convtr_columns = true;
+            else if (!match_convtr(pl.an, i, grp, pl.em)) continue;
+        }
         else if (op == GGML_OP_ARGMAX) { if (!match_vq_level(pl.an, i, grp, pl.em)) continue; }
         else if (op == GGML_OP_CONCAT) { if (!match_dw_convtr(pl.an, i, grp)) continue; }
         else continue;
         if (!claim_group(pl, grp)) continue;
+        if (convtr_columns) pl.p->n_convtr_column_groups++;
         for (auto & f : grp.steps) {
             pl.at_pos[grp.emit_pos].push_back(f);
             if (grp.has_vq) { pl.p->vq_copies.emplace_back(new vq_level_args(grp.vq)); pl.at_pos[grp.emit_pos].back().vq = pl.p->vq_copies.back().get(); }
@@ -2819,6 +2963,12 @@ static void emit_attention_groups(planner & pl) {
         const attn_args a = ag.a;
         unsigned * err = c->err_dev;
         auto & at = pl.at_pos[ag.emit_pos];
+        if (ag.B > 1 && ag.sa.a.T > 1) {   // decoder slots: one launch for every (head, row, column)
+            const attn_streams_args sa = ag.sa;
+            at.insert(at.begin(), [=](hipStream_t s) { k_attn_codec_slots(s, sa); });
+            pl.p->n_codec_attn_launches++;
+            continue;
+        }
         if (ag.B > 1) {   // lockstep streams: one launch for every (head, stream)
             const attn_streams_args sa = ag.sa;
             at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams(s, sa, err); });
@@ -3025,7 +3175,7 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
-// the twenty *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+// the twenty-two *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
 static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
     c->stats.nodes_in_last_plan = p->n_nodes;
@@ -3038,6 +3188,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
+    c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

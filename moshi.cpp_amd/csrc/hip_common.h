@@ -80,6 +80,13 @@ void k_convtr_finish(hipStream_t s, tdesc out, float * prev, const float * bias,
 // depthwise transposed conv of one input frame + streaming tail: y[k, c] = x[c] * w[k, c]
 void k_dw_convtr_frame(hipStream_t s, float * out, float * prev, const float * bias, const char * x, int64_t x_cs, const char * w, int64_t w_cs, int K, int PT, int C, int64_t out_cs = -1, int64_t out_ks = 1);   // out[c * out_cs + k * out_ks] (default: out_cs = K - PT)
 int  k_conv_transpose_1d_partial(hipStream_t s, tdesc w, tdesc x, void * ws, int pre_elu);   // returns the number of ic splits written to ws
+// the streaming transposed convolution at B columns (decoder slots): x [L, IC, B] (any strides), prev [OLf, OC, B] dense, out [L * s0, OC, B] - one
+// partial launch over the B x L positions and one finish launch, the sums of an output element in k_conv_transpose_1d_partial / k_convtr_finish's order
+// a codec convolution at B columns (decoder slots): dst F32 [OW, OC, B] dense <- the F16 im2col rows [K, OW * B] (column-major positions) times the F16
+// kernel [K, OC], + bias[oc] (may be NULL). The order of an output's sums depends on (K, OW, OC) alone
+void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w, const float * bias, int K, int OW, int OC, int B);
+size_t k_convtr_cols_ws_size(const struct ggml_tensor * w, int64_t L, int64_t B);
+void k_convtr_cols(hipStream_t s, tdesc out, float * prev, const float * bias, tdesc w, tdesc x, int s0, int pre_elu, void * ws);
 // scatter of batched small uploads: descs/blob live in pinned host memory mapped into the device
 struct upload_desc { char * dst; uint32_t offset; uint32_t size; };
 void k_scatter_uploads(hipStream_t s, const upload_desc * descs, const char * blob, int n);
@@ -219,6 +226,13 @@ void k_attn_decode(hipStream_t s, const attn_args & a, void * ws = nullptr, unsi
 // stream (stream slots, moshi_hot_create_slots: mask_bs = C, rot_bs = D floats, index_bs = 1), each workgroup then scanning its own stream's mask row.
 struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs, mask_bs, rot_bs, index_bs; };
 void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err = nullptr);
+// Decoder slots (moshi_hot_create_codec_slots): the codec transformer's attention block of B columns, T = 2 new rows each at the column's own position -
+// one workgroup per (head, row, column), each doing exactly what attn_ring256_kernel's workgroup (head, row) does for a single column (attn_ring256_body:
+// it rotates both new rows, workgroup (h, 0, b) writes them into column b's ring, row t attends over the column's own ring under its own mask row). `a`
+// describes column 0 with T rows (the ring256 shape: D = 64, 1 <= T <= 2, 64 < C <= 256); column b's pointers are a's plus b times the *_bs strides
+// (floats for q / k / v / out / mask / rot, elements for index, bytes for the rings). A plain grid: no workgroup waits for another.
+bool k_attn_codec_slots_supported(const attn_args & a);
+void k_attn_codec_slots(hipStream_t s, const attn_streams_args & a);
 // Slot prefill (moshi_hot_slots_prefill): the attention blocks of one layer of one [dim, T] pass - job j = T_j consecutive rows of the pass that belong
 // to one slot: its own rows of q / k / v, its own column of the [D, C, H, B] rings, its own mask block [C, T_j], RoPE rows, ring slots and output rows -
 // as ONE pair of launches (write_only = 1: every row's K / V into its ring; then 0: all rows attend). Workgroup (g, h, j) runs attn_decode_body on rows

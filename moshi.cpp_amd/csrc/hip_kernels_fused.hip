@@ -1864,6 +1864,26 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
     else      attn_streams_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(sa, w);
 }
 
+// Decoder slots: workgroup (h, t, b) is attn_ring256_kernel's workgroup (h, t) over column b - its own q / k / v rows, ring column, mask rows, RoPE rows,
+// ring slots and output rows - so a column's two rows are computed exactly as the single-column launch computes them. Only workgroup (h, 0, b) writes
+// column b's ring rows; nothing of another column is read or written.
+__global__ void __launch_bounds__(512) attn_codec_slots_kernel(attn_streams_args sa) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t b = blockIdx.z;
+    attn_args a = sa.a;
+    a.q += b * sa.q_bs; a.k += b * sa.k_bs; a.v += b * sa.v_bs;
+    a.kcache += b * sa.kc_bs; a.vcache += b * sa.vc_bs;
+    a.out += b * sa.out_bs;
+    a.mask += b * sa.mask_bs; a.index += b * sa.index_bs;
+    if (a.rot) a.rot += b * sa.rot_bs;
+    attn_ring256_body<AT_PLAIN>(a, smem, (int) blockIdx.x, (int) blockIdx.y);
+}
+bool k_attn_codec_slots_supported(const attn_args & a) { return attn_ring256_shape(a); }
+void k_attn_codec_slots(hipStream_t s, const attn_streams_args & sa) {
+    GGML_ASSERT(sa.B >= 1 && sa.B <= 65535 && attn_ring256_shape(sa.a));
+    attn_codec_slots_kernel<<<dim3((unsigned) sa.a.H, (unsigned) sa.a.T, (unsigned) sa.B), 512, ATTN_RING256_SMEM, s>>>(sa);
+}
+
 // Slot prefill: workgroup (g, h, j) runs attn_decode_body for head h on rows 4 g .. 4 g + 3 of job j of the table - what attn_decode_kernel's workgroup
 // (h, g) does in the T > 4 launches of a single ring, on the job's own rows, ring column, mask block, RoPE rows, ring slots and output rows. The job
 // index is uniform over the workgroup: its table entry is read from the kernel arguments by scalar loads.

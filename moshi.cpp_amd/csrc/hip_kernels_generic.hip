@@ -618,16 +618,23 @@ __global__ void convtr_overlap_add_kernel(tdesc dst, const double * P, int N, in
 size_t k_conv_transpose_1d_ws_size(const struct ggml_tensor * w, const struct ggml_tensor * x) {
     return (size_t) 16 * (size_t) x->ne[0] * (size_t) (w->ne[0] * w->ne[1]) * 8 + 256;
 }
+// the number of ic slices of a layer: a function of the layer's own shape (N = OC * K weight columns, L positions of ONE column, IC), which fixes the
+// order in which an output element's products are summed
+static int convtr_nsplit(int N, int L, int IC) {
+    const int nb = (N + 255) / 256, lt = (L + CT_LT - 1) / CT_LT;
+    int nsplit = 512 / (nb * lt);
+    if (nsplit > 16) nsplit = 16;
+    if (nsplit > IC / 32) nsplit = IC / 32;
+    if (nsplit < 1) nsplit = 1;
+    return nsplit;
+}
 int k_conv_transpose_1d_partial(hipStream_t s, tdesc w, tdesc x, void * ws, int pre_elu) {
     GGML_ASSERT(x.type == GGML_TYPE_F32 && (w.type == GGML_TYPE_F32 || w.type == GGML_TYPE_F16));
     const int K = (int) w.ne[0], OC = (int) w.ne[1], IC = (int) w.ne[2], L = (int) x.ne[0];
     GGML_ASSERT(w.nb[1] == w.nb[0] * K && "kernel taps and output channels must be contiguous");
     const int N = OC * K;
     const int nb = (N + 255) / 256, lt = (L + CT_LT - 1) / CT_LT;
-    int nsplit = 512 / (nb * lt);
-    if (nsplit > 16) nsplit = 16;
-    if (nsplit > IC / 32) nsplit = IC / 32;
-    if (nsplit < 1) nsplit = 1;
+    const int nsplit = convtr_nsplit(N, L, IC);
     const int per = (IC + nsplit - 1) / nsplit;
     convtr_partial_kernel<<<dim3(nb, lt, nsplit), 256, (size_t) per * CT_LT * 4, s>>>(w, x, (double *) ws, N, L, IC, per, pre_elu);
     return nsplit;
@@ -747,6 +754,102 @@ void k_convtr_finish(hipStream_t s, tdesc out, float * prev, const float * bias,
         case 16: convtr_finish_kernel<16><<<nb, BLOCK, 0, s>>>(out, prev, bias, (const double *) ws, K, OC, L, s0, nsplit, scv); break;
         default: convtr_finish_kernel<0><<<nb, BLOCK, 0, s>>>(out, prev, bias, (const double *) ws, K, OC, L, s0, nsplit, scv); break;
     }
+}
+
+// ---- the streaming transposed convolution at B columns (decoder slots): x [L, IC, B], prev [OLf, OC, B], out [L * s0, OC, B] ----
+// The partial products are a product over positions, so the B columns are B x L positions p = b * L + l against ONE read of the weight slab:
+// P[s][p][n] as convtr_partial_kernel writes P[s][l][n], the ic slices those of the layer at ONE column (convtr_nsplit of L, not of B x L). An output
+// element's sums therefore run in the order convtr_partial_kernel / convtr_finish_kernel give it - a function of the layer alone, never of b or B.
+__global__ void __launch_bounds__(256) convtr_partial_cols_kernel(tdesc w, tdesc x, double * P, int N, int L, int BL, int IC, int ic_per_split, int pre_elu) {
+    extern __shared__ float ct_xs[];   // [ic in this split][CT_LT]
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    const int p0 = blockIdx.y * CT_LT;
+    const int split = blockIdx.z;
+    const int ic0 = split * ic_per_split, ic1 = min(IC, ic0 + ic_per_split), nic = ic1 - ic0;
+    const bool f16 = w.type == GGML_TYPE_F16;
+    for (int idx = threadIdx.x; idx < nic * CT_LT; idx += blockDim.x) {
+        const int i = idx % CT_LT, icl = idx / CT_LT, p = p0 + i;
+        float xv = 0.f;
+        if (p < BL) {
+            const int b = p / L, l = p - b * L;
+            xv = *(const float *) (x.data + (int64_t) l * x.nb[0] + (int64_t) (ic0 + icl) * x.nb[1] + (int64_t) b * x.nb[2]);
+            if (pre_elu) xv = xv > 0.f ? xv : expm1f(xv);
+            if (f16) xv = h2f(f2h(xv));
+        }
+        ct_xs[idx] = xv;
+    }
+    __syncthreads();
+    if (n >= N) return;
+    double acc[CT_LT];
+#pragma unroll
+    for (int i = 0; i < CT_LT; i++) acc[i] = 0;
+    const char * wp = w.data + (int64_t) n * w.nb[0] + (int64_t) ic0 * w.nb[2];
+    int icl = 0;
+    for (; icl + 8 <= nic; icl += 8) {
+        float wv[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const char * wq = wp + (int64_t) (icl + u) * w.nb[2];
+            wv[u] = f16 ? h2f(*(const uint16_t *) wq) : *(const float *) wq;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+#pragma unroll
+            for (int i = 0; i < CT_LT; i++) acc[i] += (double) (ct_xs[(icl + u) * CT_LT + i] * wv[u]);
+    }
+    for (; icl < nic; icl++) {
+        const char * wq = wp + (int64_t) icl * w.nb[2];
+        const float wv = f16 ? h2f(*(const uint16_t *) wq) : *(const float *) wq;
+#pragma unroll
+        for (int i = 0; i < CT_LT; i++) acc[i] += (double) (ct_xs[icl * CT_LT + i] * wv);
+    }
+#pragma unroll
+    for (int i = 0; i < CT_LT; i++) { const int p = p0 + i; if (p < BL) P[((int64_t) split * BL + p) * N + n] = acc[i]; }
+}
+// the finish of column b = blockIdx.y: convtr_finish_kernel's thread (t, oc) on the column's own partials, carried tail prev[:, :, b] and output column
+__global__ void convtr_finish_cols_kernel(tdesc out, float * prev, const float * bias, const double * P, int K, int OC, int L, int BL, int s0, int nsplit) {
+    const int N = OC * K, OLf = (L - 1) * s0 + K, PT = K - s0, keep = OLf - PT;   // keep == L * s0
+    const int b = blockIdx.y;
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t) keep * OC) return;
+    const int t = (int) (i % keep), oc = (int) (i / keep);
+    auto conv_at = [&](int tt) {
+        float acc = 0.f;
+        int l0 = (tt - (K - 1) + s0 - 1) / s0;
+        if (l0 < 0) l0 = 0;
+        for (int l = l0; l < L && l * s0 <= tt; l++) {
+            const int k = tt - l * s0;
+            if (k >= K) continue;
+            double v = 0;
+            for (int sp = 0; sp < nsplit; sp++) v += P[((int64_t) sp * BL + (int64_t) b * L + l) * N + oc * K + k];
+            acc += (float) v;
+        }
+        return acc;
+    };
+    float * pv = prev + ((int64_t) b * OC + oc) * OLf;
+    const bool has2 = t < PT;               // position t + keep lies in the carried tail
+    float y = conv_at(t), y2 = 0.f;
+    if (has2) { y = y + pv[keep + t]; y2 = conv_at(t + keep); }
+    pv[t] = y;
+    if (has2) pv[t + keep] = y2;
+    *(float *) at(out, t, oc, b, 0) = bias ? y + bias[oc] : y;
+}
+size_t k_convtr_cols_ws_size(const struct ggml_tensor * w, int64_t L, int64_t B) {
+    const int N = (int) (w->ne[0] * w->ne[1]);
+    return (size_t) convtr_nsplit(N, (int) L, (int) w->ne[2]) * (size_t) (B * L) * (size_t) N * 8 + 256;
+}
+void k_convtr_cols(hipStream_t s, tdesc out, float * prev, const float * bias, tdesc w, tdesc x, int s0, int pre_elu, void * ws) {
+    GGML_ASSERT(x.type == GGML_TYPE_F32 && out.type == GGML_TYPE_F32 && (w.type == GGML_TYPE_F32 || w.type == GGML_TYPE_F16));
+    const int K = (int) w.ne[0], OC = (int) w.ne[1], IC = (int) w.ne[2], L = (int) x.ne[0], B = (int) x.ne[2];
+    GGML_ASSERT(w.nb[1] == w.nb[0] * K && x.ne[1] == IC && B >= 1 && B <= 65535 && K - s0 > 0 && K - s0 <= L * s0);
+    GGML_ASSERT(out.ne[0] == (int64_t) L * s0 && out.ne[1] == OC && out.ne[2] == B);
+    const int N = OC * K, BL = B * L;
+    const int nsplit = convtr_nsplit(N, L, IC), per = (IC + nsplit - 1) / nsplit;
+    const int nbx = (N + 255) / 256, pt = (BL + CT_LT - 1) / CT_LT;
+    GGML_ASSERT(pt <= 65535);
+    convtr_partial_cols_kernel<<<dim3(nbx, pt, nsplit), 256, (size_t) per * CT_LT * 4, s>>>(w, x, (double *) ws, N, L, BL, IC, per, pre_elu);
+    const int64_t n = (int64_t) L * s0 * OC;
+    convtr_finish_cols_kernel<<<dim3((unsigned) nblocks(n), (unsigned) B), BLOCK, 0, s>>>(out, prev, bias, (const double *) ws, K, OC, L, BL, s0, nsplit);
 }
 
 // depthwise variant for one input frame: y[k, c] = x[c] * w[k, c]; y[:PT] += prev[K-PT:]; prev = y; out = (y + bias)[:K-PT]
@@ -1258,6 +1361,83 @@ generic_product:
     if (direct) y = b.data;
     else convert_rows_kernel<<<(int) rows, BLOCK, 0, s>>>(b, vt, (char *) ws, row_bytes);
     mul_mat_kernel<<<nblocks(total, 4) + mm_tail_extra(epi), 256, 0, s>>>(dst, a, b, y, row_bytes, vt, total, epi);
+}
+
+// ---- the codec convolutions at B columns (decoder slots) ----
+// dst[ow, oc, b] = sum_k A[b * OW + ow][k] * W[oc][k] (+ bias[oc]): A = the F16 im2col rows of the B columns one behind the other (ggml_im2col's
+// [K, OW, B]), W the F16 kernel [K, OC]. ggml_conv_1d's own product leaves these values as [OW * B, OC]; here they are stored in the [OW, OC, B] layout
+// the graph's strided view and bias add (or cont) would bring them into. Which kernel runs and how the tile kernel slices K are functions of the
+// layer's own shape (OW, OC, K), never of B: a column's sums are those of the same layer in a batch of any other size, beside any neighbours.
+// The tile form (mul_mat_f16_mfma_kernel's tiles: one wave per 16 x 16 outputs, K in SK contiguous slices summed through LDS in slice order); OW % 16 == 0,
+// so the 16 rows of a tile - and the 4 a lane stores - lie in one column.
+__global__ void __launch_bounds__(1024) conv_cols_mfma_kernel(float * dst, int64_t d_nb1, int64_t d_nb2, const char * A, const char * W, const float * bias, int K, int OW, int mt, int nt, int SK, int TPW) {
+    __shared__ f32x4 red[16][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slice = wave % SK, tw = wave / SK;
+    const int tile = blockIdx.x * TPW + tw;
+    const bool live = tile < mt * nt;
+    const int tm = live ? tile % mt : 0, tn = live ? tile / mt : 0;
+    const int r = lane & 15, kq = lane >> 4;
+    const int steps = K / 32, per = (steps + SK - 1) / SK;
+    const int s_begin = slice * per, s_end = min(steps, s_begin + per);
+    const char * ap = A + (int64_t) (tm * 16 + r) * K * 2 + kq * 16;
+    const char * bp = W + (int64_t) (tn * 16 + r) * K * 2 + kq * 16;
+    f32x4 acc = { 0.f, 0.f, 0.f, 0.f };
+    int st = s_begin;
+    for (; st + 4 <= s_end; st += 4) {
+        f16x8 av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) { av[u] = *(const f16x8 *) (ap + (st + u) * 64); bv[u] = *(const f16x8 *) (bp + (st + u) * 64); }
+#pragma unroll
+        for (int u = 0; u < 4; u++) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[u], bv[u], acc, 0, 0, 0);
+    }
+    for (; st < s_end; st++) {
+        const f16x8 av = *(const f16x8 *) (ap + st * 64);
+        const f16x8 bv = *(const f16x8 *) (bp + st * 64);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc, 0, 0, 0);
+    }
+    bool writer = live;
+    if (SK > 1) {
+        if (slice > 0) red[wave][lane] = acc;
+        __syncthreads();
+        if (slice > 0) writer = false;
+        else for (int sl = 1; sl < SK; sl++) { const f32x4 o = red[wave + sl][lane]; acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2]; acc[3] += o[3]; }
+    }
+    if (writer) {
+        const int m0 = tm * 16 + kq * 4, b = m0 / OW, ow = m0 - b * OW, oc = tn * 16 + r;
+        if (bias) { const float bv = bias[oc]; acc[0] = acc[0] + bv; acc[1] = acc[1] + bv; acc[2] = acc[2] + bv; acc[3] = acc[3] + bv; }
+        *(f32x4 *) ((char *) dst + (int64_t) oc * d_nb1 + (int64_t) b * d_nb2 + (int64_t) ow * 4) = acc;
+    }
+}
+// any other shape (few positions per column, one output channel, a short K): one wave per output, mul_mat_kernel's F16 dot (lanes stride K, double)
+__global__ void conv_cols_dot_kernel(float * dst, int64_t d_nb1, int64_t d_nb2, const uint16_t * A, const uint16_t * W, const float * bias, int K, int OW, int64_t M, int64_t total) {
+    const int lane = threadIdx.x & 63;
+    const int64_t o = (int64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (o >= total) return;
+    const int64_t m = o % M, oc = o / M;
+    const uint16_t * a = A + m * K, * w = W + oc * K;
+    double acc = 0;
+    for (int k = lane; k < K; k += 64) acc += (double) (h2f(a[k]) * h2f(w[k]));
+    float result = (float) wave_sum_f64(acc);
+    if (lane == 0) {
+        if (bias) result = result + bias[oc];
+        const int64_t b = m / OW, ow = m - b * OW;
+        *(float *) ((char *) dst + oc * d_nb1 + b * d_nb2 + ow * 4) = result;
+    }
+}
+void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w, const float * bias, int K, int OW, int OC, int B) {
+    GGML_ASSERT(K >= 1 && OW >= 1 && OC >= 1 && B >= 1);
+    const int64_t d_nb1 = (int64_t) OW * 4, d_nb2 = (int64_t) OW * OC * 4, M = (int64_t) OW * B;
+    if (OW % 16 == 0 && OC % 16 == 0 && K % 32 == 0 && (uintptr_t) im2col % 16 == 0 && (uintptr_t) w % 16 == 0 && (uintptr_t) dst % 16 == 0) {
+        const int mt = (int) (M / 16), nt = OC / 16, steps = K / 32;
+        const int SK = mfma_split_k((OW / 16) * nt, steps);   // the slices of this layer at ONE column
+        const int TPW = SK >= 4 ? 1 : 4 / SK;
+        const int64_t tiles = (int64_t) mt * nt;
+        conv_cols_mfma_kernel<<<(unsigned) ((tiles + TPW - 1) / TPW), 64 * SK * TPW, 0, s>>>(dst, d_nb1, d_nb2, (const char *) im2col, (const char *) w, bias, K, OW, mt, nt, SK, TPW);
+        return;
+    }
+    const int64_t total = M * OC;
+    conv_cols_dot_kernel<<<nblocks(total, 4), 256, 0, s>>>(dst, d_nb1, d_nb2, (const uint16_t *) im2col, (const uint16_t *) w, bias, K, OW, M, total);
 }
 
 // ---------------------------------------------------------------------------------------------------

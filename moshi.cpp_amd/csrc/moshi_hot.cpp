@@ -635,6 +635,50 @@ void transformer_graph_step_slots(Builder & scratch, Transformer & tr, const std
     ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
 }
 
+// transformer_graph_build for decoder slots (moshi_hot_create_codec_slots): x = [dim, Tn, B], column b's Tn rows at its own stream position. The slot
+// form above with Tn rows per column: g_bias [C, Tn, 1, B] (column b's Tn mask rows, bias_pattern_index's T = Tn quirk included), g_offset [Tn * B]
+// (the timesteps themselves, pos_b + i: what arange(Tn) + offset gives the single stream, exact in float; the table [D, Tn * B] is viewed as
+// [D/2, Tn, 1, B] halves) and g_indices [Tn, 1, B] (column b's Tn ring rows).
+T transformer_graph_build_codec_slots(Builder & g, Transformer & tr, T x) {
+    const int64_t Tn = x->ne[1], B = x->ne[2], C = tr.capacity, D = tr.dim / tr.heads;
+    tr.g_bias = g.tensor(GGML_TYPE_F32, C, Tn, 1, B);
+    Rot rot;
+    if (tr.max_period) {
+        tr.g_offset = g.tensor(GGML_TYPE_F32, Tn * B);
+        T table = ggml_timestep_embedding(g, tr.g_offset, (int) D, tr.max_period);
+        rot.rotr = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, 0);
+        rot.roti = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, table->nb[0] * (size_t) (D / 2));
+    }
+    tr.g_indices = g.tensor(GGML_TYPE_I32, Tn, 1, B);
+    for (auto & L : tr.layers) x = transformer_layer(g, tr, L, 0, tr.g_indices, x, tr.g_bias, tr.max_period ? &rot : nullptr, false);
+    return x;
+}
+// its per-step inputs: column b's rows start at stream position pos[b] (transformer_graph_step_at per column; tr.offset is not used). The B x Tn mask
+// rows are the windows bias_pattern_index cuts from create_bias_pattern's table, written out on the host and uploaded with the other two inputs: one
+// upload for all columns instead of 2 B copy nodes in a scratch graph (the table holds 0 and -inf only: the same bytes).
+void transformer_graph_step_codec_slots(Transformer & tr, int Tn, const std::vector<int64_t> & pos) {
+    const int B = (int) pos.size(), C = tr.capacity, start = C * 2 - Tn;
+    std::vector<float> ts((size_t) B * (size_t) Tn), mask((size_t) B * (size_t) Tn * (size_t) C);
+    std::vector<int32_t> idx((size_t) B * (size_t) Tn);
+    for (int b = 0; b < B; b++) {
+        const int offset = (int) pos[(size_t) b], col = offset <= C ? start - offset : C - (offset % C);   // bias_pattern_index (torch.h:205-223)
+        for (int j = 0; j < Tn; j++) {
+            float * row = mask.data() + ((size_t) b * (size_t) Tn + (size_t) j) * (size_t) C;
+            for (int i = 0; i < C; i++) {   // table[j][col + i] of create_bias_pattern (torch.h:170-203)
+                const int t = col + i;
+                row[i] = t < start + 1 + j && !(t <= C - 1 && t > C - 1 - (Tn - j - 1)) ? 0.0f : -INFINITY;
+            }
+        }
+        for (int i = 0; i < Tn; i++) {
+            ts[(size_t) (b * Tn + i)] = (float) i + (float) pos[(size_t) b];
+            idx[(size_t) (b * Tn + i)] = (int32_t) ((pos[(size_t) b] + i) % C);
+        }
+    }
+    ggml_backend_tensor_set(tr.g_bias, mask.data(), 0, mask.size() * 4);
+    if (tr.g_offset) ggml_backend_tensor_set(tr.g_offset, ts.data(), 0, ts.size() * 4);
+    ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
+}
+
 // moshi_streaming_transformer_graph_step (transformer.h:1259-1289): refresh mask, rope offset, ring slots for the Tn positions from `offset` on
 void transformer_graph_step_at(Builder & scratch, Transformer & tr, int Tn, int offset) {
     T bias = bias_pattern_index(scratch, tr, Tn, offset);
@@ -711,27 +755,44 @@ struct Conv { int cin, cout, k, stride; T w = nullptr, b = nullptr; T prev = nul
 struct ConvTr { int cin, cout, k, stride, groups; T w = nullptr, b = nullptr; T prev = nullptr; };
 struct ResBlock { Conv block1, block3; };
 
+// ggml_conv_1d + bias. Its reshape of the product to [OW, OC, B] is right for one batch entry only: the product's rows hold the B x OW positions
+// column-major ([OW * B, OC]). At B > 1 columns (decoder slots) the same im2col and the same product are read through the strided [OW, OC, B] view,
+// which the bias add (else a cont) brings into layout: per column the very dots of the single-stream nodes.
+T conv_1d_bias(Builder & g, T w, T x, int stride, T bias) {
+    if (x->ne[2] == 1) {
+        T y = ggml_conv_1d(g, w, x, stride, 0, 1);
+        return bias ? ggml_add(g, y, bias) : y;
+    }
+    T im2col = ggml_im2col(g, w, x, stride, 0, 0, 0, 1, 0, false, GGML_TYPE_F16);
+    const int64_t OW = im2col->ne[1], B = im2col->ne[2];
+    T y = ggml_mul_mat(g, ggml_reshape_2d(g, im2col, im2col->ne[0], OW * B), ggml_reshape_2d(g, w, w->ne[0] * w->ne[1], w->ne[2]));
+    y = ggml_view_3d(g, y, OW, w->ne[2], B, y->nb[1], (size_t) OW * y->nb[0], 0);
+    return bias ? ggml_add(g, y, bias) : ggml_cont(g, y);
+}
 // moshi_streaming_conv_1d (moshi/modules/conv.h:50-96)
 T streaming_conv(Builder & g, Conv & cv, T x) {
     const int TP = cv.k - cv.stride;
     x = ggml_concat(g, cv.prev, x, 0);
     T tail = ggml_view_3d(g, x, TP, x->ne[1], x->ne[2], x->nb[1], x->nb[2], x->nb[0] * (size_t) (x->ne[0] - TP));
     g.expand(ggml_cpy(g, tail, cv.prev));
-    T y = ggml_conv_1d(g, cv.w, x, cv.stride, 0, 1);
-    if (cv.b) y = ggml_add(g, y, cv.b);
-    return y;
+    return conv_1d_bias(g, cv.w, x, cv.stride, cv.b);
 }
 // moshi_stateless_conv_1d (conv.h:137-161)
-T stateless_conv(Builder & g, Conv & cv, T x) {
-    T y = ggml_conv_1d(g, cv.w, x, 1, 0, 1);
-    if (cv.b) y = ggml_add(g, y, cv.b);
-    return y;
-}
+T stateless_conv(Builder & g, Conv & cv, T x) { return conv_1d_bias(g, cv.w, x, 1, cv.b); }
 // moshi_streaming_conv_transpose_1d (conv.h:240-310)
 T streaming_conv_transpose(Builder & g, ConvTr & ct, T x) {
     const int PT = ct.k - ct.stride;
     T y = nullptr;
-    if (ct.groups == 1) y = ggml_conv_transpose_1d(g, ct.w, x, ct.stride, 0, 1);
+    if (ct.groups == 1 && x->ne[2] > 1) {
+        // ggml_conv_transpose_1d takes a matrix: at B columns (decoder slots) one node per contiguous column view x[:, :, b], each copied into column b
+        // of one [OL, OC, B] tensor; the streaming tail below then runs once over the B columns
+        const int64_t B = x->ne[2];
+        y = g.tensor(GGML_TYPE_F32, (x->ne[0] - 1) * ct.stride + ct.k, ct.cout, B);
+        for (int64_t b = 0; b < B; b++) {
+            T yb = ggml_conv_transpose_1d(g, ct.w, ggml_view_2d(g, x, x->ne[0], x->ne[1], x->nb[1], (size_t) b * x->nb[2]), ct.stride, 0, 1);
+            g.expand(ggml_cpy(g, yb, ggml_view_2d(g, y, y->ne[0], y->ne[1], y->nb[1], (size_t) b * y->nb[2])));
+        }
+    } else if (ct.groups == 1) y = ggml_conv_transpose_1d(g, ct.w, x, ct.stride, 0, 1);
     else {
         for (int i = 0; i < ct.w->ne[0]; i++) {   // depthwise: one multiply per kernel tap (conv.h:262-278)
             T sub = ggml_view_3d(g, ct.w, 1, ct.w->ne[2], ct.w->ne[1], ct.w->nb[2], ct.w->nb[2], ct.w->nb[0] * (size_t) i);
@@ -763,6 +824,11 @@ struct Rvq { std::vector<Codebook> layers; T input_proj = nullptr, output_proj =
 
 // moshi_vq_decode (moshi/quantization/core_vq.h:100-109)
 T vq_decode(Builder & g, Codebook & cb, T codes) {
+    if (codes->ne[1] > 1) {   // B columns (decoder slots) of one frame: ggml_get_rows wants its table's ne[2] entries, so the B indices go in as one row
+        GGML_ASSERT(codes->ne[0] == 1);
+        T q = ggml_get_rows(g, cb.embedding, ggml_reshape_1d(g, ggml_cont(g, codes), codes->ne[1]));   // [256, B]
+        return ggml_cont(g, ggml_permute(g, ggml_reshape_3d(g, q, q->ne[0], 1, q->ne[1]), 1, 0, 2, 3));   // [1, 256, B]
+    }
     T q = ggml_get_rows(g, cb.embedding, ggml_cont(g, codes));
     q = ggml_permute(g, q, 1, 0, 2, 3);
     return ggml_cont(g, q);
@@ -777,7 +843,7 @@ T rvq_decode(Builder & g, Rvq & rvq, T codes) {
         T dec = vq_decode(g, rvq.layers[i], lc);
         quantized = quantized ? ggml_add(g, quantized, dec) : dec;
     }
-    if (rvq.output_proj) quantized = ggml_conv_1d(g, rvq.output_proj, quantized, 1, 0, 1);
+    if (rvq.output_proj) quantized = conv_1d_bias(g, rvq.output_proj, quantized, 1, nullptr);
     return quantized;
 }
 // moshi_EuclideanCodebook_encode (core_vq.h:27-56): nearest centroid via the materialised difference
@@ -818,7 +884,7 @@ T rvq_encode(Builder & g, Rvq & rvq, T x, T * latent = nullptr) {
 // ---------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------
-enum class ModelKind { single, lockstep, slots };   // one stream (moshi_hot_create), or B > 1 columns at a shared / an own stream position
+enum class ModelKind { single, lockstep, slots, codec_slots };   // one stream (moshi_hot_create), B > 1 LM columns at a shared / an own stream position, or B > 1 decoder columns (moshi_hot_create_codec_slots)
 struct moshi_hot_model {
     moshi_hot_config cfg;
     ggml_backend_t be;
@@ -896,6 +962,9 @@ struct moshi_hot_model {
     std::vector<Conv> dec_convs; std::vector<ConvTr> dec_convtrs; std::vector<ResBlock> dec_res;
     std::vector<Conv> enc_convs; std::vector<ResBlock> enc_res;
     Builder * g_dec = nullptr; T dec_codes = nullptr, dec_frame = nullptr; int dec_T = 0;
+    // decoder slots (moshi_hot_create_codec_slots): column b's frames decoded since it opened - its decoder-transformer position is pos * dec_T
+    struct CodecColumn { int64_t pos = 0; bool open = false; };
+    std::vector<CodecColumn> codec_cols;
     Builder * g_enc = nullptr; T enc_frame = nullptr, enc_codes = nullptr; int enc_T = 0;
     T enc_latent[2] = { nullptr, nullptr };   // the projected latents the two RVQ stacks quantise (inputs of their first levels), for tie analysis in tests
 
@@ -966,7 +1035,7 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
                 L.gate_out.push_back(W.add(p + "gating" + ws + ".linear_out.weight", wtype, ffn_hidden, dim, 1, qgen(upd / sqrtf((float) ffn_hidden))));
             }
         }
-        if (m->n_streams > 1 && !mimi_style) {   // moshi_kv_cache_state with batch_size = B (transformer.h:155-171)
+        if (m->n_streams > 1) {   // moshi_kv_cache_state with batch_size = B (transformer.h:155-171); decoder slots: the codec transformer's rings too
             L.kcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
             L.vcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
         } else {
@@ -995,7 +1064,7 @@ Conv make_conv(moshi_hot_model * m, const std::string & name, int cin, int cout,
     const float sd = 1.f / sqrtf((float) (cin * k));
     c.w = W.add(name + ".weight", GGML_TYPE_F16, k, cin, cout, [sd](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, sd); });   // loader.h:209: conv weights are F16
     if (bias) c.b = W.add(name + ".bias", GGML_TYPE_F32, 1, cout, 1, [](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, 0.02f); });
-    if (stateful && k - stride > 0) c.prev = state(m, GGML_TYPE_F32, k - stride, cin);
+    if (stateful && k - stride > 0) c.prev = state(m, GGML_TYPE_F32, k - stride, cin, m->n_streams);   // (decoder slots: one tail per column)
     return c;
 }
 ConvTr make_convtr(moshi_hot_model * m, const std::string & name, int cin, int cout, int k, int stride, int groups, bool bias, int64_t in_len) {
@@ -1004,7 +1073,7 @@ ConvTr make_convtr(moshi_hot_model * m, const std::string & name, int cin, int c
     const float sd = 1.f / sqrtf((float) (cin / groups));
     c.w = W.add(name + ".weight", GGML_TYPE_F32, k, cout / groups, cin, [sd](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, sd); });
     if (bias) c.b = W.add(name + ".bias", GGML_TYPE_F32, 1, cout, 1, [](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, 0.02f); });
-    c.prev = state(m, GGML_TYPE_F32, (in_len - 1) * stride + k, cout);   // conv.h:205-217
+    c.prev = state(m, GGML_TYPE_F32, (in_len - 1) * stride + k, cout, m->n_streams);   // conv.h:205-217 (decoder slots: one partial per column)
     return c;
 }
 ResBlock make_res(moshi_hot_model * m, const std::string & name, int dim) {
@@ -1171,7 +1240,8 @@ void build_decode_graph(moshi_hot_model * m) {
     const moshi_hot_config & c = m->cfg;
     m->g_dec = new Builder(m->be_codec, 256);
     Builder & g = *m->g_dec;
-    T codes = ggml_new_tensor_2d(g, GGML_TYPE_I32, 1, c.mimi_n_q);
+    // decoder slots: the reference's batch dimension made real - codes [1, n_q, B], every activation and carried state gains ne[2] = B
+    T codes = m->kind == ModelKind::codec_slots ? ggml_new_tensor_3d(g, GGML_TYPE_I32, 1, c.mimi_n_q, m->n_streams) : ggml_new_tensor_2d(g, GGML_TYPE_I32, 1, c.mimi_n_q);
     m->dec_codes = codes;
     // moshi_split_rvq_decode (vq.h:62-95)
     const int64_t B = codes->ne[2], K = codes->ne[1], Tn = codes->ne[0];
@@ -1185,7 +1255,7 @@ void build_decode_graph(moshi_hot_model * m) {
     m->dec_T = (int) emb->ne[0];
     // moshi_projected_transformer_graph_build (transformer.h:1356-1365)
     T x = ggml_cont(g, ggml_transpose(g, emb));
-    x = transformer_graph_build(g, m->dec_tr, x);
+    x = m->kind == ModelKind::codec_slots ? transformer_graph_build_codec_slots(g, m->dec_tr, x) : transformer_graph_build(g, m->dec_tr, x);
     x = ggml_transpose(g, x);
     // moshi_seanet_decoder (seanet.h:179-211)
     x = streaming_conv(g, m->dec_convs[0], x);
@@ -1641,6 +1711,75 @@ extern "C" void moshi_hot_mimi_encode(moshi_hot_model_t * m, const float * pcm, 
     PhaseTimer pt(m, 0);
     mimi_encode_launch(m, pcm);
     mimi_encode_finish(m, codes);
+}
+
+// ---- decoder slots (moshi_hot.h): B conversations' Mimi decode in one pass ------------------------------------------------------------------------
+extern "C" moshi_hot_model_t * moshi_hot_create_codec_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
+    if (!cfg || n_slots < 2 || n_slots > (cfg->wide_streams ? MOSHI_HOT_MAX_STREAMS : MOSHI_HOT_DEFAULT_MAX_STREAMS)) return nullptr;
+    if (cfg->enable_lm || !cfg->enable_mimi_decoder || cfg->enable_mimi_encoder || cfg->codec_stream || cfg->mimi_n_q < 1 || cfg->mimi_codebook_size < 1) return nullptr;
+    moshi_hot_model_t * m = create_model(backend, cfg, seed, nullptr, n_slots, ModelKind::codec_slots);
+    if (m) m->codec_cols.assign((size_t) n_slots, {});
+    return m;
+}
+static moshi_hot_model::CodecColumn * codec_slot(moshi_hot_model_t * m, int b) {
+    return m->kind == ModelKind::codec_slots && b >= 0 && b < m->n_streams ? &m->codec_cols[(size_t) b] : nullptr;
+}
+extern "C" int moshi_hot_codec_slot_open(moshi_hot_model_t * m, int b) {
+    moshi_hot_model::CodecColumn * s = codec_slot(m, b);
+    if (!s) return -1;
+    // column b of every conv tail and transposed-conv partial starts as zeros (conv.h:112, 205-217); its ring rows stay: the mask admits written rows only
+    auto clear = [b](T t) { if (t) ggml_backend_tensor_memset(t, 0, (size_t) b * t->nb[2], t->nb[2]); };
+    clear(m->upsample.prev);
+    for (auto & cv : m->dec_convs) clear(cv.prev);
+    for (auto & ct : m->dec_convtrs) clear(ct.prev);
+    for (auto & rb : m->dec_res) { clear(rb.block1.prev); clear(rb.block3.prev); }
+    s->pos = 0; s->open = true;
+    return 0;
+}
+extern "C" int moshi_hot_codec_slot_close(moshi_hot_model_t * m, int b) {
+    moshi_hot_model::CodecColumn * s = codec_slot(m, b);
+    if (!s) return -1;
+    s->open = false;
+    return 0;
+}
+extern "C" int64_t moshi_hot_codec_slot_position(moshi_hot_model_t * m, int b) {
+    moshi_hot_model::CodecColumn * s = codec_slot(m, b);
+    return s && s->open ? s->pos : -1;
+}
+extern "C" void moshi_hot_codec_slot_set_fill(moshi_hot_model_t * m, int b, int64_t frames) {
+    moshi_hot_model::CodecColumn * s = codec_slot(m, b);
+    if (s && frames >= 0) s->pos = frames;
+}
+extern "C" int moshi_hot_mimi_decode_slots(moshi_hot_model_t * m, const int32_t * codes, float * pcm, int32_t * status) {
+    if (m->kind != ModelKind::codec_slots || !codes || !pcm || !status) return -1;
+    const int B = m->n_streams, nq = m->cfg.mimi_n_q;
+    int n_open = 0;
+    for (int b = 0; b < B; b++) {
+        if (!m->codec_cols[(size_t) b].open) continue;
+        n_open++;
+        for (int q = 0; q < nq; q++) if (codes[(size_t) b * nq + q] < 0 || codes[(size_t) b * nq + q] >= m->cfg.mimi_codebook_size) return -1;   // nothing has changed
+    }
+    for (int b = 0; b < B; b++) status[b] = m->codec_cols[(size_t) b].open ? 1 : -1;
+    if (n_open == 0) { memset(pcm, 0, (size_t) B * 1920 * sizeof(float)); return 0; }
+    PhaseTimer pt(m, 3);
+    if (!m->g_dec) build_decode_graph(m);
+    GGML_ASSERT(ggml_nelements(m->dec_frame) == (int64_t) B * 1920);
+    // a closed slot is computed frozen: code 0 at its position, which does not advance (its tails drift; the next open resets them)
+    std::vector<int32_t> cd((size_t) B * (size_t) nq, 0);
+    std::vector<int64_t> pos((size_t) B);
+    for (int b = 0; b < B; b++) {
+        if (m->codec_cols[(size_t) b].open) memcpy(cd.data() + (size_t) b * nq, codes + (size_t) b * nq, (size_t) nq * 4);
+        pos[(size_t) b] = m->codec_cols[(size_t) b].pos * m->dec_T;
+    }
+    ggml_backend_tensor_set(m->dec_codes, cd.data(), 0, ggml_nbytes(m->dec_codes));
+    transformer_graph_step_codec_slots(m->dec_tr, m->dec_T, pos);
+    m->g_dec->compute();
+    ggml_backend_tensor_get(m->dec_frame, pcm, 0, ggml_nbytes(m->dec_frame));
+    for (int b = 0; b < B; b++) {
+        if (m->codec_cols[(size_t) b].open) m->codec_cols[(size_t) b].pos++;
+        else memset(pcm + (size_t) b * 1920, 0, 1920 * sizeof(float));
+    }
+    return n_open;
 }
 
 // moshi_lmgen_step (lm.h:778-979) for the plain moshi model: no state machine, no prefixes

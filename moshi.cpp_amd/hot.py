@@ -137,6 +137,12 @@ SIGNATURES = {
     "moshi_hot_save_gguf": (C.c_int, [P, C.c_char_p]),
     "moshi_hot_create_from_gguf": (P, [P, C.POINTER(Config), C.c_char_p]),
     "moshi_hot_tensor_file_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
+    "moshi_hot_create_codec_slots": (P, [P, C.POINTER(Config), C.c_uint64, C.c_int]),
+    "moshi_hot_codec_slot_open": (C.c_int, [P, C.c_int]),
+    "moshi_hot_codec_slot_close": (C.c_int, [P, C.c_int]),
+    "moshi_hot_codec_slot_position": (C.c_int64, [P, C.c_int]),
+    "moshi_hot_codec_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
+    "moshi_hot_mimi_decode_slots": (C.c_int, [P, P, P, P]),
     "moshi_hot_mimi_encode": (None, [P, P, P]),
     "moshi_hot_mimi_decode": (None, [P, P, P]),
     "moshi_hot_lm_step": (C.c_int, [P, P, P, P]),
