@@ -135,6 +135,8 @@ struct ggml_mi355x_stats {
     int64_t pass_input_rows_in_last_plan;       // ... and the rows they write
     int64_t convtr_column_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan (decoder slots: the B convtr + copy nodes of a SEANet layer and their shared streaming tail as one partial and one finish launch)
     int64_t codec_attn_launches_in_last_plan;   // k_attn_codec_slots launches of the last plan (decoder slots: the 2-row attention of every (column, head) pair of a layer in one launch)
+    int64_t vq_column_levels_in_last_plan;      // k_vq_level_cols launches of the last plan (encoder slots: one residual-VQ level of all B columns in one launch)
+    int64_t code_gather_columns_in_last_plan;   // columns written by B-column code gathers of the last plan (encoder slots: the [1, n_q, B] code tensor in one k_gather_scalars launch; 0 = a copy per concat)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -164,6 +166,8 @@ GGML_API void ggml_backend_mi355x_get_kernel_profile(ggml_backend_t backend, str
 // 2048 = the attention tail of inproj_attn_kernel keeps its general body at every live length (default: heads with at most 128 live ring slots take the
 //        short-ring form, which computes the same bits; the MI355X_ATTN_SHORT_TAIL=0 environment switch does the same for every handle)
 // 4096 = the input of a persona pass stays its plain nodes (default: one k_pass_input launch for the whole concat chain; same bits either way)
+// 8192 = the residual-VQ levels and the code vector of a B-column encode (encoder slots) stay their plain nodes (default: one k_vq_level_cols launch per
+//        level for all columns and one gather launch for the codes; same bits either way)
 GGML_API void ggml_backend_mi355x_set_flags(ggml_backend_t backend, int flags);
 // hipGraph capture of repeated graphs on / off without touching cached plans (off: a repeated graph still reuses its plan, launched eagerly -
 // for sequences of same-shaped one-off graphs such as prompt-prefill chunks, where a capture costs more than it saves). No-op on other backends.

@@ -332,6 +332,27 @@ GGML_API void moshi_hot_codec_slot_set_fill(moshi_hot_model_t * m, int b, int64_
 // [0, mimi_codebook_size).
 GGML_API int moshi_hot_mimi_decode_slots(moshi_hot_model_t * m, const int32_t * codes, float * pcm, int32_t * status);
 
+// ---- encoder slots: the Mimi encode of B conversations in one pass ---------------------------------------------------------------------------------
+// The other half of the codec at B columns: one set of encoder weights, B columns, each a conversation's streaming encoder state - the conv tails
+// [len, C, B] of the SEANet encoder and of the downsampler, the encoder transformer's K / V rings [D, 250, H, B] and a position of its own. The graph
+// is mimi_encode's (compression.h:284-308) with the batch dimension made real: the frame is [1920, 1, B], the transformer takes 2 rows per column,
+// and every residual-VQ level searches its codebook for the B residuals at once (distances [NC, B], one code per column). On the oracle slot b's codes
+// and both projected latents are bit-identical to a fresh single-stream codec-only model (moshi_hot_create with enable_lm = 0) fed the same frames one
+// by one, whatever the other slots do.
+// Requires enable_lm = 0, enable_mimi_encoder = 1, enable_mimi_decoder = 0, codec_stream = 0, mimi_n_q >= 1, mimi_codebook_size >= 1 and
+// 2 <= n_slots <= 16 (wide_streams = 1: <= MOSHI_HOT_MAX_STREAMS); anything else, or a state that does not fit the device, returns NULL. The weights
+// are those moshi_hot_create makes for the same cfg and seed, under the same names. All slots start closed. moshi_hot_n_streams returns B.
+// moshi_hot_codec_slot_open / _close / _position / _set_fill take such a model as they take a decoder-slots model: open zeroes column b of every
+// encoder conv tail and sets its encoder-transformer position to 0 (ring rows stay: the mask admits written rows only), set_fill moves the position
+// alone. Every other frame call refuses: moshi_hot_mimi_encode / _decode do nothing, moshi_hot_mimi_decode_slots, moshi_hot_lm_step*, moshi_hot_sts_*
+// and the LM slot calls return -1. moshi_hot_read_last("enc_latent_first" | "enc_latent_rest") returns B consecutive rows of 256, slot 0 first.
+GGML_API moshi_hot_model_t * moshi_hot_create_encoder_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots);
+// one frame of every open slot: pcm = B x 1920 (slot-major), codes = B x mimi_n_q, status = B entries: 1 for an encoded slot, -1 for a closed one, whose
+// pcm is ignored and whose codes row is written as -1 (it is computed frozen on zero PCM at its position, which does not advance; the next open resets
+// its state). Returns the number of slots encoded; 0 with no device work when none is open (codes are then all -1); -1 on any other kind of model,
+// decoder-slots models included, or on a NULL argument.
+GGML_API int moshi_hot_mimi_encode_slots(moshi_hot_model_t * m, const float * pcm, int32_t * codes, int32_t * status);
+
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute
 // (src/context.h:456-480, moshi/utils/sampling.h:4-64). By default that noise comes from libc rand() in one sweep over the whole [k, B] tensor, so a
@@ -429,7 +450,7 @@ GGML_API void    moshi_hot_set_timing(moshi_hot_model_t * m, int on);
 GGML_API void    moshi_hot_get_timing(moshi_hot_model_t * m, double * us_per_call);
 // teacher forcing for parity runs: overwrite the tokens the last moshi_hot_lm_step wrote into the delay ring
 GGML_API void    moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, const int32_t * audio_tokens);
-GGML_API void    moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset); // jump the Temporal ring to a given fill level (bench only)
+GGML_API void    moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset); // jump the Temporal ring to a given fill level (bench only); on a single-stream codec-only model (enable_lm = 0): the codec transformers' positions, in frames (2 ring rows each)
 // write the same pseudo-random BF16 rows (approximately N(0, scale^2), a function of seed / which / layer / position only) into EVERY slot of the K and V
 // rings (transformer.h:156-172) of one layer (layer >= 0) or of all layers (-1) of the Temporal (which = 0) or Depth (1) transformer: two executors
 // filled alike hold identical caches, so attention over hundreds or thousands of live slots can be compared node by node (tests only)

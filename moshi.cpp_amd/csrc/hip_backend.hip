@@ -342,7 +342,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -2095,6 +2095,97 @@ static bool match_vq_level(const analysis & an, int pos, step_group & grp, emitt
     return true;
 }
 
+// F'. the same level at B > 1 columns (encoder slots, moshi_hot.cpp rvq_encode_columns): the B residuals [1, D, B] go through codebook_encode as its
+//     ane1 = B rows - distances [NC, B], argmax [B] - and vq_decode gathers the B centroids as [1, D, B]; one k_vq_level_cols launch for all columns.
+//     has_vq stays unset: the multi-level chain (vq_chain_kernel) takes single-column levels only.
+static bool match_vq_level_columns(const analysis & an, int pos, step_group & grp, emitter & em) {
+    const ggml_tensor * am = an.g->nodes[pos];
+    const int64_t B = am->ne[0];
+    if (am->op != GGML_OP_ARGMAX || B < 2 || B > VQ_COLS_MAX_B || ggml_nelements(am) != B || !am->data) return false;
+    auto one_use = [&](const ggml_tensor * t, enum ggml_op op) { return t && t->op == op && !t->view_src && uses_of(an, t) == 1; };
+    auto reshape_use = [&](const ggml_tensor * t) { return t && t->op == GGML_OP_RESHAPE && uses_of(an, t) == 1; };
+    auto shape = [](const ggml_tensor * t, int64_t n0, int64_t n1, int64_t n2) { return t->ne[0] == n0 && t->ne[1] == n1 && t->ne[2] == n2 && t->ne[3] == 1; };
+    const ggml_tensor * dv = am->src[0];
+    if (!one_use(dv, GGML_OP_DIV)) return false;
+    const ggml_tensor * num = dv->src[0], * ad = dv->src[1];
+    if (!one_use(ad, GGML_OP_ADD)) return false;
+    const ggml_tensor * rs = ad->src[0], * addc = ad->src[1];
+    if (!reshape_use(rs)) return false;
+    const ggml_tensor * sr = rs->src[0];
+    if (!one_use(sr, GGML_OP_SUM_ROWS)) return false;
+    const ggml_tensor * sq = sr->src[0];
+    if (!one_use(sq, GGML_OP_MUL) || sq->src[0] != sq->src[1]) return false;
+    const ggml_tensor * df = sq->src[0];
+    if (!one_use(df, GGML_OP_SUB)) return false;
+    const ggml_tensor * rb = df->src[0], * ra2 = df->src[1];
+    if (!one_use(rb, GGML_OP_REPEAT) || !reshape_use(ra2)) return false;
+    const ggml_tensor * emb = rb->src[0], * ra = ra2->src[0];
+    if (!one_use(ra, GGML_OP_REPEAT)) return false;
+    const ggml_tensor * ra0 = ra->src[0];
+    if (!reshape_use(ra0)) return false;
+    const ggml_tensor * ac = ra0->src[0];
+    if (!one_use(ac, GGML_OP_CONT)) return false;
+    const ggml_tensor * xp = ac->src[0];
+    if (!reshape_use(xp)) return false;
+    const ggml_tensor * resid = xp->src[0];
+    const int64_t D = emb->ne[0], NC = emb->ne[1];
+    if (emb->op != GGML_OP_NONE || emb->type != GGML_TYPE_F32 || !dense_rows(emb) || D != 256 || NC < 1 || NC > 4096 || emb->ne[2] != 1 || emb->ne[3] != 1 || !emb->data) return false;
+    if (resid->type != GGML_TYPE_F32 || !shape(resid, 1, D, B) || !ggml_is_contiguous(resid) || !resid->data || ((uintptr_t) resid->data & 15)) return false;
+    // row b * NC + c of the difference is centroid c against residual b
+    if (!shape(xp, D, B, 1) || !shape(ac, D, B, 1) || !shape(ra0, D, 1, B) || !shape(ra, D, NC, B) || !shape(ra2, D, NC * B, 1) || !shape(rb, D, NC * B, 1) ||
+        !shape(sr, 1, NC * B, 1) || !shape(rs, NC, B, 1) || !shape(dv, NC, B, 1)) return false;
+    if (num->op != GGML_OP_NONE || num->type != GGML_TYPE_F32 || ggml_nelements(num) != NC * B || !ggml_is_contiguous(num) || !num->data) return false;
+    if (addc->op != GGML_OP_NONE || addc->type != GGML_TYPE_F32 || ggml_nelements(addc) != 1 || !addc->data) return false;
+    std::vector<int> members = { pos, pos_of(an, dv), pos_of(an, ad), pos_of(an, rs), pos_of(an, sr), pos_of(an, sq), pos_of(an, df), pos_of(an, rb),
+                                 pos_of(an, ra2), pos_of(an, ra), pos_of(an, ra0), pos_of(an, ac), pos_of(an, xp) };
+    // consumers of the codes: the F32 cast (always) and the centroid gather feeding the next residuals (all but the last level)
+    const ggml_tensor * cs = find_consumer(an, am, GGML_OP_CPY);
+    if (!cs || cs->type != GGML_TYPE_F32 || cs->src[0] != am || cs->view_src || !ggml_is_contiguous(cs) || ggml_nelements(cs) != B || !cs->data) return false;
+    members.push_back(pos_of(an, cs));
+    float * resid_out = nullptr;
+    const ggml_tensor * i2 = find_consumer(an, am, GGML_OP_RESHAPE);
+    if (i2) {
+        if (uses_of(an, am) != 2 || uses_of(an, i2) != 1) return false;
+        const ggml_tensor * ci = sole_consumer(an, i2);
+        if (!one_use(ci, GGML_OP_CONT)) return false;
+        const ggml_tensor * r1 = sole_consumer(an, ci);
+        if (!reshape_use(r1) || r1->ne[0] != B || ggml_nelements(r1) != B) return false;
+        const ggml_tensor * gr = sole_consumer(an, r1);
+        if (!one_use(gr, GGML_OP_GET_ROWS) || gr->src[0] != emb || gr->src[1] != r1) return false;
+        const ggml_tensor * r3 = sole_consumer(an, gr);
+        if (!reshape_use(r3)) return false;
+        const ggml_tensor * pm = sole_consumer(an, r3);
+        if (!pm || pm->op != GGML_OP_PERMUTE || uses_of(an, pm) != 1) return false;
+        const ggml_tensor * qc = sole_consumer(an, pm);
+        if (!one_use(qc, GGML_OP_CONT) || !shape(qc, 1, D, B)) return false;
+        const ggml_tensor * sb = sole_consumer(an, qc);
+        if (!sb || sb->op != GGML_OP_SUB || sb->view_src || sb->src[0] != resid || sb->src[1] != qc || !ggml_is_contiguous(sb) || !sb->data || !shape(sb, 1, D, B) ||
+            ((uintptr_t) sb->data & 15)) return false;
+        if (uses_of(an, resid) != 2) return false;
+        resid_out = (float *) sb->data;
+        for (const ggml_tensor * t : { i2, ci, r1, gr, r3, pm, qc, sb }) members.push_back(pos_of(an, t));
+    } else if (uses_of(an, am) != 1) return false;
+    for (int m : members) if (m < 0) return false;
+    // emitted where the F32 codes are produced, as the single-column level is (match_vq_level)
+    const int last = pos_of(an, cs);
+    if (last < pos) return false;
+    const size_t ws_bytes = k_vq_level_cols_ws_size((int) NC, (int) B);
+    char * ws = (char *) em.ws(ws_bytes);
+    HIP_CHECK(hipMemsetAsync(ws, 0, ws_bytes, em.c->stream));   // stream-ordered behind the block's previous user (plans are built outside capture)
+    const size_t n_cand = (ws_bytes - 256) / 8;
+    vq_level_cols_args a;
+    a.emb = (const char *) emb->data; a.emb_row_bytes = (int64_t) emb->nb[1]; a.D = (int) D; a.NC = (int) NC; a.B = (int) B;
+    a.resid = (const char *) resid->data; a.resid_col_bytes = (int64_t) resid->nb[2];
+    a.add_c = (const float *) addc->data; a.num = (const float *) num->data;
+    a.resid_out = resid_out; a.idx_f = (float *) cs->data; a.idx_i = (int32_t *) am->data;
+    a.counter = (unsigned *) ws; a.cand_val = (float *) (ws + 256); a.cand_idx = (int32_t *) (ws + 256 + n_cand * 4);
+    grp.steps.clear();
+    grp.steps.push_back([=](hipStream_t s) { k_vq_level_cols(s, a); });
+    grp.members = members;
+    grp.emit_pos = last;
+    return true;
+}
+
 // G. a tree of concats / layout nodes over one-element F32 tensors, optionally cast to I32 at the top (the RVQ encoder's code
 //    vector: vq.h:32-45, 97-114): one gather instead of a copy per concat
 static bool vector_like(const ggml_tensor * t) {
@@ -2149,10 +2240,57 @@ static bool match_scalar_gather(const analysis & an, int pos, step_group & grp) 
     for (int i = 0; i < a.n; i++) a.src[i] = (const float *) leaves[(size_t) i]->data;
     a.dst = top->data;
     a.dst_type = top->type;
+    a.B = 1;
     grp.steps.clear();
     grp.steps.push_back([=](hipStream_t s) { k_gather_scalars(s, a); });
     grp.members = members;
     grp.emit_pos = pos;
+    return true;
+}
+// G'. the same tree at B > 1 columns (encoder slots): concats along dim 1 of [1, k, B] tensors whose leaves are reshapes [1, 1, B] of B-element F32
+//     tensors (a level's codes), optionally cast to I32 at the top - dst[b * n + i] = leaf i's element b, one launch.
+static bool collect_column_leaves(const analysis & an, const ggml_tensor * t, bool top, int64_t B, std::vector<const ggml_tensor *> & leaves, std::vector<int> & members) {
+    if (t->type != GGML_TYPE_F32 || t->ne[0] != 1 || t->ne[2] != B || t->ne[3] != 1) return false;
+    if (!top && uses_of(an, t) != 1) return false;
+    if (pos_of(an, t) < 0) return false;
+    if (t->op == GGML_OP_CONCAT) {
+        if (t->view_src || t->op_params[0] != 1) return false;
+        members.push_back(pos_of(an, t));
+        return collect_column_leaves(an, t->src[0], false, B, leaves, members) && collect_column_leaves(an, t->src[1], false, B, leaves, members);
+    }
+    if (t->op != GGML_OP_RESHAPE || t->ne[1] != 1) return false;
+    const ggml_tensor * base = t->src[0];
+    if (base->type != GGML_TYPE_F32 || ggml_nelements(base) != B || !ggml_is_contiguous(base) || !base->data || base->data != t->data) return false;
+    members.push_back(pos_of(an, t));
+    leaves.push_back(base);
+    return true;
+}
+static bool match_column_gather(const analysis & an, int pos, step_group & grp, int & n_cols) {
+    const ggml_tensor * top = an.g->nodes[pos];
+    const ggml_tensor * tree = top;
+    std::vector<int> members;
+    if (top->op == GGML_OP_CPY && top->view_src == NULL && top->type == GGML_TYPE_I32 && top->src[0]->type == GGML_TYPE_F32) {
+        members.push_back(pos);
+        tree = top->src[0];
+        if (uses_of(an, tree) != 1) return false;
+    } else if (top->op != GGML_OP_CONCAT) return false;
+    const int64_t n = top->ne[1], B = top->ne[2];
+    if (!ggml_is_contiguous(top) || !top->data || top->ne[0] != 1 || top->ne[3] != 1 || B < 2 || n < 2 || n > GATHER_MAX || !ggml_are_same_shape(top, tree)) return false;
+    std::vector<const ggml_tensor *> leaves;
+    if (!collect_column_leaves(an, tree, tree == top, B, leaves, members)) return false;
+    if ((int64_t) leaves.size() != n) return false;
+    for (int m : members) if (m < 0) return false;
+    gather_args a;
+    memset(&a, 0, sizeof(a));
+    a.n = (int) n; a.B = (int) B;
+    for (int i = 0; i < a.n; i++) a.src[i] = (const float *) leaves[(size_t) i]->data;
+    a.dst = top->data;
+    a.dst_type = top->type;
+    grp.steps.clear();
+    grp.steps.push_back([=](hipStream_t s) { k_gather_scalars(s, a); });
+    grp.members = members;
+    grp.emit_pos = pos;
+    n_cols = (int) B;
     return true;
 }
 
@@ -2473,18 +2611,24 @@ static void pass_codec_convs(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i]) continue;
         step_group grp;
-        bool convtr_columns = false;
+        bool convtr_columns = false, vq_columns = false;
         const enum ggml_op op = pl.g->nodes[i]->op;
         if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em) && !match_conv_columns(pl.an, i, grp)) continue; }
         else if (op == GGML_OP_CONV_TRANSPOSE_1D) {
             if (match_convtr_columns(pl.an, i, grp, pl.em)) convtr_columns = true;
             else if (!match_convtr(pl.an, i, grp, pl.em)) continue;
         }
-        else if (op == GGML_OP_ARGMAX) { if (!match_vq_level(pl.an, i, grp, pl.em)) continue; }
+        else if (op == GGML_OP_ARGMAX) {
+            if (!match_vq_level(pl.an, i, grp, pl.em)) {
+                if ((pl.c->flags & 8192) || !match_vq_level_columns(pl.an, i, grp, pl.em)) continue;
+                vq_columns = true;
+            }
+        }
         else if (op == GGML_OP_CONCAT) { if (!match_dw_convtr(pl.an, i, grp)) continue; }
         else continue;
         if (!claim_group(pl, grp)) continue;
         if (convtr_columns) pl.p->n_convtr_column_groups++;
+        if (vq_columns) pl.p->n_vq_column_levels++;
         for (auto & f : grp.steps) {
             pl.at_pos[grp.emit_pos].push_back(f);
             if (grp.has_vq) { pl.p->vq_copies.emplace_back(new vq_level_args(grp.vq)); pl.at_pos[grp.emit_pos].back().vq = pl.p->vq_copies.back().get(); }
@@ -2497,7 +2641,10 @@ static void pass_scalar_gathers(planner & pl) {
     for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
         if (pl.an.skip[(size_t) i] || !(pl.g->nodes[i]->op == GGML_OP_CPY || pl.g->nodes[i]->op == GGML_OP_CONCAT)) continue;
         step_group grp;
-        if (!match_scalar_gather(pl.an, i, grp) || !claim_group(pl, grp)) continue;
+        int n_cols = 0;
+        if (!match_scalar_gather(pl.an, i, grp) && ((pl.c->flags & 8192) || !match_column_gather(pl.an, i, grp, n_cols))) continue;
+        if (!claim_group(pl, grp)) continue;
+        pl.p->n_code_gather_columns += n_cols;
         for (auto & f : grp.steps) pl.at_pos[grp.emit_pos].push_back(f);
     }
 }
@@ -3189,6 +3336,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
+    c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

@@ -313,9 +313,10 @@ struct vq_level_args {
     float * resid_out; float * idx_f; int32_t * idx_i;        // resid_out may be NULL (last level)
     float * cand_val; int32_t * cand_idx; unsigned * counter; // workspace: one candidate per workgroup + arrival counter (zeroed once)
 };
-// dst[i] = (dst type) *src[i]: a tree of concats of one-element F32 tensors collapsed into one launch (RVQ code vectors)
+// dst[i] = (dst type) *src[i]: a tree of concats of one-element F32 tensors collapsed into one launch (RVQ code vectors). At B > 1 columns (encoder slots)
+// every source holds B values and dst[b * n + i] = (dst type) src[i][b]: the [1, n, B] code tensor of the B columns.
 #define GATHER_MAX 32
-struct gather_args { const float * src[GATHER_MAX]; int n; void * dst; int dst_type; };
+struct gather_args { const float * src[GATHER_MAX]; int n; void * dst; int dst_type; int B; };   // B: 1 = the one-element form
 void k_gather_scalars(hipStream_t s, const gather_args & a);
 // moshi_sample_token with temp > 0 (sampling.h:4-64): soft_max(logits / temp) -> top-k (descending, ties by lower index) -> p / Exp(1) noise ->
 // argmax -> the chosen index, as one launch (the node chain costs ~12 launches and a full argsort of up to 32 000 values)
@@ -340,6 +341,19 @@ struct heads_streams_args { const char * w[HEADS_MAX]; float * out[HEADS_MAX]; i
 void k_heads_streams(hipStream_t s, const heads_streams_args & a);
 #define VQ_LEVEL_WS_BYTES 4096
 void k_vq_level(hipStream_t s, const vq_level_args & a);
+// The same level for the B residuals of B columns (encoder slots) as one launch: resid / resid_out are [D, B] (column b at + b * col_stride bytes / b * D
+// floats), num [NC, B], idx_f / idx_i [B]. A column's code is what k_vq_level gives for that residual alone, whatever B and b. Workspace: the arrival
+// counter, then one candidate per (column, workgroup) - zeroed once, k_vq_level_cols_ws_size bytes.
+#define VQ_COLS_MAX_B 64
+struct vq_level_cols_args {
+    const char * emb; int64_t emb_row_bytes; int D, NC, B;
+    const char * resid; int64_t resid_col_bytes;              // column b's D contiguous floats at resid + b * resid_col_bytes
+    const float * add_c; const float * num;                   // score = num[b * NC + c] / (dist + add_c[0])
+    float * resid_out; float * idx_f; int32_t * idx_i;         // resid_out [D, B] contiguous, may be NULL (last level)
+    unsigned * counter; float * cand_val; int32_t * cand_idx;  // workspace: candidates [B][workgroups]
+};
+size_t k_vq_level_cols_ws_size(int NC, int B);
+void k_vq_level_cols(hipStream_t s, const vq_level_cols_args & a);
 // Consecutive levels of one RVQ stack (each level's residual is the previous level's output: core_vq.h:27-56 inside vq.h:97-114's loop) as ONE persistent
 // launch (hip_chain.hip, vq_chain_kernel): the workgroups score their centroids of level l, exchange their candidates as tagged granules, every workgroup
 // merges them and subtracts the winning centroid from its own copy of the residual - one hand-off per level instead of a launch per level.

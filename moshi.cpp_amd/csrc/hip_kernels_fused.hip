@@ -2610,6 +2610,101 @@ void k_vq_level(hipStream_t s, const vq_level_args & a) {
     vq_level_kernel<<<grid, 256, 0, s>>>(a);
 }
 
+// The level at B columns (encoder slots): the grid is vq_level_kernel's - 4 waves x VQ_CPW centroids per workgroup - and every wave keeps its centroid
+// rows in registers (read once per level, not once per column) while it walks the B residuals. Per (centroid, column) the arithmetic is vq_level_kernel's
+// to the letter: float difference, float square, the lane's 4 squares added in double in the same order, wave_allsum_f64, num / ((float) acc + add_c),
+// the last maximum wins - so a column's code is a function of its residual alone, never of b or B. A workgroup publishes one candidate per column; the
+// last workgroup to arrive (vq_level_kernel's ticket) merges every column - one wave per column, round robin - writes the codes and the new residuals.
+// No workgroup waits for another.
+__global__ void __launch_bounds__(256) vq_level_cols_kernel(vq_level_cols_args a) {
+    __shared__ float sv[4][VQ_COLS_MAX_B];
+    __shared__ int si[4][VQ_COLS_MAX_B];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int B = a.B, G = (int) gridDim.x;
+    const int c0 = (blockIdx.x * 4 + wave) * VQ_CPW;
+    f32x4 e[VQ_CPW];
+#pragma unroll
+    for (int u = 0; u < VQ_CPW; u++) {
+        const int c = c0 + u < a.NC ? c0 + u : a.NC - 1;
+        e[u] = *(const f32x4 *) (a.emb + (int64_t) c * a.emb_row_bytes + lane * 16);
+    }
+    const float addc = a.add_c[0];
+    f32x4 x = *(const f32x4 *) (a.resid + lane * 16);
+    float num[VQ_CPW];
+#pragma unroll
+    for (int u = 0; u < VQ_CPW; u++) num[u] = a.num[c0 + u < a.NC ? c0 + u : a.NC - 1];
+    for (int b = 0; b < B; b++) {
+        // the next column's residual and numerators, in flight while this column is scored
+        const int bn = b + 1 < B ? b + 1 : b;
+        const f32x4 xn = *(const f32x4 *) (a.resid + (int64_t) bn * a.resid_col_bytes + lane * 16);
+        float numn[VQ_CPW];
+#pragma unroll
+        for (int u = 0; u < VQ_CPW; u++) numn[u] = a.num[(int64_t) bn * a.NC + (c0 + u < a.NC ? c0 + u : a.NC - 1)];
+        float best = -INFINITY; int bi = -1;
+#pragma unroll
+        for (int u = 0; u < VQ_CPW; u++) {
+            double acc = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) { const float d = e[u][j] - x[j]; acc += (double) (d * d); }
+            acc = wave_allsum_f64(acc);
+            const int c = c0 + u;
+            if (c < a.NC) {
+                const float v = num[u] / ((float) acc + addc);
+                if (v >= best) { best = v; bi = c; }   // centroids ascend: '>=' keeps the last maximum (ggml_vec_argmax_f32)
+            }
+        }
+        if (lane == 0) { sv[wave][b] = best; si[wave][b] = bi; }
+        x = xn;
+#pragma unroll
+        for (int u = 0; u < VQ_CPW; u++) num[u] = numn[u];
+    }
+    __syncthreads();
+    if (tid < B) {   // column tid's candidate of this workgroup
+        float best = sv[0][tid]; int bi = si[0][tid];
+        for (int w = 1; w < 4; w++) if (sv[w][tid] > best || (sv[w][tid] == best && si[w][tid] > bi)) { best = sv[w][tid]; bi = si[w][tid]; }
+        xchg_agent_wait(a.cand_val + (int64_t) tid * G + blockIdx.x, best); xchg_agent_wait(a.cand_idx + (int64_t) tid * G + blockIdx.x, bi);   // complete before the counter moves
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned ticket = atomicAdd(a.counter, 1u);
+        s_last = ticket == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    // merge: wave w takes columns w, w + 4, ...; a column's <= 256 candidates are at most 4 per lane
+    for (int b = wave; b < B; b += 4) {
+        float best = -INFINITY; int bi = -1;
+        for (int g = lane; g < G; g += 64) {
+            const float v = ld_agent(a.cand_val + (int64_t) b * G + g); const int j = ld_agent(a.cand_idx + (int64_t) b * G + g);
+            if (v > best || (v == best && j > bi)) { best = v; bi = j; }
+        }
+        for (int st = 32; st > 0; st >>= 1) {
+            const float v = __shfl_xor(best, st, 64); const int j = __shfl_xor(bi, st, 64);
+            if (v > best || (v == best && j > bi)) { best = v; bi = j; }
+        }
+        const int code = bi < 0 ? 0 : bi;
+        if (lane == 0) { a.idx_i[b] = code; a.idx_f[b] = (float) code; }
+        if (a.resid_out) {
+            const f32x4 q = *(const f32x4 *) (a.emb + (int64_t) code * a.emb_row_bytes + lane * 16);
+            const f32x4 r = *(const f32x4 *) (a.resid + (int64_t) b * a.resid_col_bytes + lane * 16);
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; j++) o[j] = r[j] - q[j];
+            *(f32x4 *) (a.resid_out + (int64_t) b * a.D + lane * 4) = o;
+        }
+    }
+    if (tid == 0) *a.counter = 0u;
+}
+static int vq_cols_grid(int NC) { return (NC + 4 * VQ_CPW - 1) / (4 * VQ_CPW); }
+size_t k_vq_level_cols_ws_size(int NC, int B) { return 256 + (size_t) vq_cols_grid(NC) * (size_t) B * 8; }
+void k_vq_level_cols(hipStream_t s, const vq_level_cols_args & a) {
+    GGML_ASSERT(a.D == 256 && a.NC >= 1 && a.B >= 1 && a.B <= VQ_COLS_MAX_B);
+    const int grid = vq_cols_grid(a.NC);
+    GGML_ASSERT(grid <= 256);
+    vq_level_cols_kernel<<<grid, 256, 0, s>>>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // fused sampler (moshi_sample_token, temp > 0; src/moshi/utils/sampling.h:4-64)
 //   p = soft_max(logits * (1 / temp))  [ggml: expf(x - max) summed in double, scaled by float(1 / sum)]
@@ -2857,15 +2952,15 @@ void k_sample_topk(hipStream_t s, const sample_args & a) {
 }
 
 __global__ void gather_scalars_kernel(gather_args a) {
-    const int i = threadIdx.x;
+    const int i = threadIdx.x, b = blockIdx.x;   // (one workgroup per column; the one-element form is column 0 alone)
     if (i >= a.n) return;
-    const float v = *a.src[i];
-    if (a.dst_type == GGML_TYPE_I32) ((int32_t *) a.dst)[i] = (int32_t) v;
-    else ((float *) a.dst)[i] = v;
+    const float v = a.src[i][b];
+    if (a.dst_type == GGML_TYPE_I32) ((int32_t *) a.dst)[b * a.n + i] = (int32_t) v;
+    else ((float *) a.dst)[b * a.n + i] = v;
 }
 void k_gather_scalars(hipStream_t s, const gather_args & a) {
-    GGML_ASSERT(a.n <= GATHER_MAX && (a.dst_type == GGML_TYPE_I32 || a.dst_type == GGML_TYPE_F32));
-    gather_scalars_kernel<<<1, 64, 0, s>>>(a);
+    GGML_ASSERT(a.n <= GATHER_MAX && a.B >= 1 && (a.dst_type == GGML_TYPE_I32 || a.dst_type == GGML_TYPE_F32));
+    gather_scalars_kernel<<<a.B, 64, 0, s>>>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------

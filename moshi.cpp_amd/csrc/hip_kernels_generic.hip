@@ -1425,6 +1425,21 @@ __global__ void conv_cols_dot_kernel(float * dst, int64_t d_nb1, int64_t d_nb2, 
         *(float *) ((char *) dst + oc * d_nb1 + b * d_nb2 + ow * 4) = result;
     }
 }
+// a short K (the encoder's first convolution at B columns: 1 input channel x 7 taps over 1920 positions per column): a wave per output would spend 64
+// lanes on 7 products, so one thread per output adds its K products in double from k = 0 up; consecutive threads take consecutive positions
+#define CONV_COLS_SHORT_K 16
+__global__ void conv_cols_short_kernel(float * dst, int64_t d_nb1, int64_t d_nb2, const uint16_t * A, const uint16_t * W, const float * bias, int K, int OW, int64_t M, int64_t total) {
+    const int64_t o = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= total) return;
+    const int64_t m = o % M, oc = o / M;
+    const uint16_t * a = A + m * K, * w = W + oc * K;
+    double acc = 0;
+    for (int k = 0; k < K; k++) acc += (double) (h2f(a[k]) * h2f(w[k]));
+    float result = (float) acc;
+    if (bias) result = result + bias[oc];
+    const int64_t b = m / OW, ow = m - b * OW;
+    *(float *) ((char *) dst + oc * d_nb1 + b * d_nb2 + ow * 4) = result;
+}
 void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w, const float * bias, int K, int OW, int OC, int B) {
     GGML_ASSERT(K >= 1 && OW >= 1 && OC >= 1 && B >= 1);
     const int64_t d_nb1 = (int64_t) OW * 4, d_nb2 = (int64_t) OW * OC * 4, M = (int64_t) OW * B;
@@ -1437,6 +1452,10 @@ void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w
         return;
     }
     const int64_t total = M * OC;
+    if (K <= CONV_COLS_SHORT_K) {   // (by K alone: no layer of the decoder is this short, the encoder's first is)
+        conv_cols_short_kernel<<<nblocks(total), BLOCK, 0, s>>>(dst, d_nb1, d_nb2, (const uint16_t *) im2col, (const uint16_t *) w, bias, K, OW, M, total);
+        return;
+    }
     conv_cols_dot_kernel<<<nblocks(total, 4), 256, 0, s>>>(dst, d_nb1, d_nb2, (const uint16_t *) im2col, (const uint16_t *) w, bias, K, OW, M, total);
 }
 

@@ -878,13 +878,30 @@ T rvq_encode(Builder & g, Rvq & rvq, T x, T * latent = nullptr) {
     }
     return ggml_permute(g, out, 0, 2, 1, 3);
 }
+// rvq_encode at B > 1 columns (encoder slots): x = [1, 512, B] -> codes F32 [1, n_q, B]. The projection goes through conv_1d_bias (ggml_conv_1d's
+// reshape is right for one batch entry only); the B residuals [1, 256, B] are codebook_encode's ane1 = B rows [256, B]: distances [NC, B], argmax [B],
+// centroids gathered as [1, 256, B] and subtracted per column - per column the very sums and the very comparison of the single-stream level.
+T rvq_encode_columns(Builder & g, Rvq & rvq, T x, T * latent) {
+    const int64_t B = x->ne[2];
+    x = conv_1d_bias(g, rvq.input_proj, x, 1, nullptr);
+    if (latent) *latent = x;
+    T residual = x, out = nullptr;
+    for (int i = 0; i < rvq.n_q; i++) {
+        T idx = codebook_encode(g, rvq.layers[(size_t) i], ggml_reshape_2d(g, residual, residual->ne[1], B));   // I32 [B]
+        T quant = vq_decode(g, rvq.layers[(size_t) i], ggml_reshape_2d(g, idx, 1, B));                       // [1, 256, B]
+        T idf = ggml_reshape_3d(g, ggml_cast(g, idx, GGML_TYPE_F32), 1, 1, B);
+        residual = ggml_sub(g, residual, quant);
+        out = out ? ggml_concat(g, out, idf, 1) : idf;
+    }
+    return out;
+}
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
 // model
 // ---------------------------------------------------------------------------------------------------
-enum class ModelKind { single, lockstep, slots, codec_slots };   // one stream (moshi_hot_create), B > 1 LM columns at a shared / an own stream position, or B > 1 decoder columns (moshi_hot_create_codec_slots)
+enum class ModelKind { single, lockstep, slots, codec_slots, encoder_slots };   // one stream (moshi_hot_create), B > 1 LM columns at a shared / an own stream position, B > 1 decoder columns (moshi_hot_create_codec_slots) or B > 1 encoder columns (moshi_hot_create_encoder_slots)
 struct moshi_hot_model {
     moshi_hot_config cfg;
     ggml_backend_t be;
@@ -962,7 +979,8 @@ struct moshi_hot_model {
     std::vector<Conv> dec_convs; std::vector<ConvTr> dec_convtrs; std::vector<ResBlock> dec_res;
     std::vector<Conv> enc_convs; std::vector<ResBlock> enc_res;
     Builder * g_dec = nullptr; T dec_codes = nullptr, dec_frame = nullptr; int dec_T = 0;
-    // decoder slots (moshi_hot_create_codec_slots): column b's frames decoded since it opened - its decoder-transformer position is pos * dec_T
+    // decoder slots (moshi_hot_create_codec_slots): column b's frames decoded since it opened - its decoder-transformer position is pos * dec_T;
+    // encoder slots (moshi_hot_create_encoder_slots): its frames encoded, the encoder-transformer position is pos * enc_T
     struct CodecColumn { int64_t pos = 0; bool open = false; };
     std::vector<CodecColumn> codec_cols;
     Builder * g_enc = nullptr; T enc_frame = nullptr, enc_codes = nullptr; int enc_T = 0;
@@ -1276,7 +1294,9 @@ void build_encode_graph(moshi_hot_model * m) {
     const moshi_hot_config & c = m->cfg;
     m->g_enc = new Builder(m->be_codec, 256);
     Builder & g = *m->g_enc;
-    T x = ggml_new_tensor_1d(g, GGML_TYPE_F32, 1920);
+    // encoder slots: the reference's batch dimension made real - the frame [1920, 1, B], every activation and carried conv tail gains ne[2] = B
+    const bool cols = m->kind == ModelKind::encoder_slots;
+    T x = cols ? ggml_new_tensor_3d(g, GGML_TYPE_F32, 1920, 1, m->n_streams) : ggml_new_tensor_1d(g, GGML_TYPE_F32, 1920);
     m->enc_frame = x;
     // moshi_seanet_encoder (seanet.h:88-113)
     x = streaming_conv(g, m->enc_convs[0], x);
@@ -1289,12 +1309,18 @@ void build_encode_graph(moshi_hot_model * m) {
     x = streaming_conv(g, m->enc_convs[5], x);
     m->enc_T = (int) x->ne[0];
     x = ggml_cont(g, ggml_transpose(g, x));
-    x = transformer_graph_build(g, m->enc_tr, x);
+    x = cols ? transformer_graph_build_codec_slots(g, m->enc_tr, x) : transformer_graph_build(g, m->enc_tr, x);
     x = ggml_transpose(g, x);
     x = streaming_conv(g, m->downsample, x);
     // moshi_split_rvq_encode (vq.h:97-114)
-    T codes = rvq_encode(g, m->rvq_first, x, &m->enc_latent[0]);
-    if (c.mimi_n_q > 1) codes = ggml_concat(g, codes, rvq_encode(g, m->rvq_rest, x, &m->enc_latent[1]), 1);
+    T codes;
+    if (cols) {   // codes [1, n_q, B]: slot-major rows of n_q
+        codes = rvq_encode_columns(g, m->rvq_first, x, &m->enc_latent[0]);
+        if (c.mimi_n_q > 1) codes = ggml_concat(g, codes, rvq_encode_columns(g, m->rvq_rest, x, &m->enc_latent[1]), 1);
+    } else {
+        codes = rvq_encode(g, m->rvq_first, x, &m->enc_latent[0]);
+        if (c.mimi_n_q > 1) codes = ggml_concat(g, codes, rvq_encode(g, m->rvq_rest, x, &m->enc_latent[1]), 1);
+    }
     codes = ggml_cast(g, codes, GGML_TYPE_I32);
     m->enc_codes = codes;
     g.expand(codes);
@@ -1721,8 +1747,16 @@ extern "C" moshi_hot_model_t * moshi_hot_create_codec_slots(ggml_backend_t backe
     if (m) m->codec_cols.assign((size_t) n_slots, {});
     return m;
 }
+// ---- encoder slots (moshi_hot.h): B conversations' Mimi encode in one pass; the slot calls below serve both kinds --------------------------------------
+extern "C" moshi_hot_model_t * moshi_hot_create_encoder_slots(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, int n_slots) {
+    if (!cfg || n_slots < 2 || n_slots > (cfg->wide_streams ? MOSHI_HOT_MAX_STREAMS : MOSHI_HOT_DEFAULT_MAX_STREAMS)) return nullptr;
+    if (cfg->enable_lm || !cfg->enable_mimi_encoder || cfg->enable_mimi_decoder || cfg->codec_stream || cfg->mimi_n_q < 1 || cfg->mimi_codebook_size < 1) return nullptr;
+    moshi_hot_model_t * m = create_model(backend, cfg, seed, nullptr, n_slots, ModelKind::encoder_slots);
+    if (m) m->codec_cols.assign((size_t) n_slots, {});
+    return m;
+}
 static moshi_hot_model::CodecColumn * codec_slot(moshi_hot_model_t * m, int b) {
-    return m->kind == ModelKind::codec_slots && b >= 0 && b < m->n_streams ? &m->codec_cols[(size_t) b] : nullptr;
+    return (m->kind == ModelKind::codec_slots || m->kind == ModelKind::encoder_slots) && b >= 0 && b < m->n_streams ? &m->codec_cols[(size_t) b] : nullptr;
 }
 extern "C" int moshi_hot_codec_slot_open(moshi_hot_model_t * m, int b) {
     moshi_hot_model::CodecColumn * s = codec_slot(m, b);
@@ -1733,6 +1767,10 @@ extern "C" int moshi_hot_codec_slot_open(moshi_hot_model_t * m, int b) {
     for (auto & cv : m->dec_convs) clear(cv.prev);
     for (auto & ct : m->dec_convtrs) clear(ct.prev);
     for (auto & rb : m->dec_res) { clear(rb.block1.prev); clear(rb.block3.prev); }
+    // (an encoder-slots model holds the encoder's tails instead, a decoder-slots model none of them)
+    for (auto & cv : m->enc_convs) clear(cv.prev);
+    for (auto & rb : m->enc_res) { clear(rb.block1.prev); clear(rb.block3.prev); }
+    clear(m->downsample.prev);
     s->pos = 0; s->open = true;
     return 0;
 }
@@ -1778,6 +1816,33 @@ extern "C" int moshi_hot_mimi_decode_slots(moshi_hot_model_t * m, const int32_t 
     for (int b = 0; b < B; b++) {
         if (m->codec_cols[(size_t) b].open) m->codec_cols[(size_t) b].pos++;
         else memset(pcm + (size_t) b * 1920, 0, 1920 * sizeof(float));
+    }
+    return n_open;
+}
+
+extern "C" int moshi_hot_mimi_encode_slots(moshi_hot_model_t * m, const float * pcm, int32_t * codes, int32_t * status) {
+    if (!m || m->kind != ModelKind::encoder_slots || !pcm || !codes || !status) return -1;
+    const int B = m->n_streams, nq = m->cfg.mimi_n_q;
+    int n_open = 0;
+    for (int b = 0; b < B; b++) { status[b] = m->codec_cols[(size_t) b].open ? 1 : -1; n_open += m->codec_cols[(size_t) b].open; }
+    if (n_open == 0) { for (int i = 0; i < B * nq; i++) codes[i] = -1; return 0; }
+    PhaseTimer pt(m, 0);
+    if (!m->g_enc) build_encode_graph(m);
+    GGML_ASSERT(ggml_nelements(m->enc_codes) == (int64_t) B * nq && ggml_nelements(m->enc_frame) == (int64_t) B * 1920);
+    // a closed slot is computed frozen: zero PCM at its position, which does not advance (its tails drift; the next open resets them)
+    std::vector<float> in((size_t) B * 1920, 0.f);
+    std::vector<int64_t> pos((size_t) B);
+    for (int b = 0; b < B; b++) {
+        if (m->codec_cols[(size_t) b].open) memcpy(in.data() + (size_t) b * 1920, pcm + (size_t) b * 1920, 1920 * sizeof(float));
+        pos[(size_t) b] = m->codec_cols[(size_t) b].pos * m->enc_T;
+    }
+    ggml_backend_tensor_set(m->enc_frame, in.data(), 0, ggml_nbytes(m->enc_frame));
+    transformer_graph_step_codec_slots(m->enc_tr, m->enc_T, pos);
+    m->g_enc->compute();
+    ggml_backend_tensor_get(m->enc_codes, codes, 0, ggml_nbytes(m->enc_codes));
+    for (int b = 0; b < B; b++) {
+        if (m->codec_cols[(size_t) b].open) m->codec_cols[(size_t) b].pos++;
+        else for (int q = 0; q < nq; q++) codes[(size_t) b * nq + q] = -1;
     }
     return n_open;
 }
@@ -3318,6 +3383,11 @@ extern "C" void moshi_hot_force_last(moshi_hot_model_t * m, int32_t text_token, 
 extern "C" void moshi_hot_set_context_fill(moshi_hot_model_t * m, int64_t offset) {
     if (m->kind == ModelKind::slots) return;   // (a position per slot: moshi_hot_slot_set_fill)
     if (m->kind == ModelKind::lockstep) { for (auto & col : m->cols) col.pos = offset; return; }   // (not the frame counts)
+    if (m->kind != ModelKind::single) return;   // (decoder / encoder slots: moshi_hot_codec_slot_set_fill)
+    if (!m->cfg.enable_lm) {   // a codec-only model: the codec transformers' positions, in frames of 2 ring rows (what moshi_hot_codec_slot_set_fill moves per slot)
+        m->enc_tr.offset = m->dec_tr.offset = (int) (offset * 2);
+        return;
+    }
     unstage_temporal(m);
     m->temporal.offset = (int) offset;
     if (m->tp_x) m->temporal_tp.offset = (int) offset;   // tensor-parallel frame mode steps its own stack (head-sliced rings): same stream position

@@ -143,6 +143,8 @@ SIGNATURES = {
     "moshi_hot_codec_slot_position": (C.c_int64, [P, C.c_int]),
     "moshi_hot_codec_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
     "moshi_hot_mimi_decode_slots": (C.c_int, [P, P, P, P]),
+    "moshi_hot_create_encoder_slots": (P, [P, C.POINTER(Config), C.c_uint64, C.c_int]),
+    "moshi_hot_mimi_encode_slots": (C.c_int, [P, P, P, P]),
     "moshi_hot_mimi_encode": (None, [P, P, P]),
     "moshi_hot_mimi_decode": (None, [P, P, P]),
     "moshi_hot_lm_step": (C.c_int, [P, P, P, P]),
