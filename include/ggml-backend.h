@@ -137,6 +137,8 @@ struct ggml_mi355x_stats {
     int64_t codec_attn_launches_in_last_plan;   // k_attn_codec_slots launches of the last plan (decoder slots: the 2-row attention of every (column, head) pair of a layer in one launch)
     int64_t vq_column_levels_in_last_plan;      // k_vq_level_cols launches of the last plan (encoder slots: one residual-VQ level of all B columns in one launch)
     int64_t code_gather_columns_in_last_plan;   // columns written by B-column code gathers of the last plan (encoder slots: the [1, n_q, B] code tensor in one k_gather_scalars launch; 0 = a copy per concat)
+    int64_t state_copy_launches_in_last_plan;   // k_state_copy launches of the last plan (codec slot snapshots: every conv-state column copy of a fork, a save or a load in one launch) ...
+    int64_t state_copy_jobs_in_last_plan;       // ... and the cpy nodes (jobs) they hold
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set

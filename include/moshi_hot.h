@@ -353,6 +353,31 @@ GGML_API moshi_hot_model_t * moshi_hot_create_encoder_slots(ggml_backend_t backe
 // decoder-slots models included, or on a NULL argument.
 GGML_API int moshi_hot_mimi_encode_slots(moshi_hot_model_t * m, const float * pcm, int32_t * codes, int32_t * status);
 
+// ---- codec slot snapshots: fork, save and restore a decoder or an encoder slot -----------------------------------------------------------------------
+// The codec's counterpart of moshi_hot_slot_fork / _save / _load, on a decoder-slots or an encoder-slots model: same signatures, same blocking behaviour,
+// same refusal style. A streaming codec state depends on its whole history and the codec has no prefill call, so a copy is the only way to move or
+// branch it. The state of column b: its position (frames); column b of every carried conv state, the tensors moshi_hot_codec_slot_open clears, in model
+// order (a decoder: upsample.prev, the two conv tails, the four transposed-conv partials, block1.prev of the four residual blocks; an encoder: the six
+// conv tails, block1.prev of the four residual blocks, downsample.prev - eleven each); and ring rows 0 .. n - 1 of every head of column b of every K
+// and V ring of the codec transformer, n = min(position x rows per frame, capacity) = min(2 position, 250). Before the wrap the mask admits only
+// written rows, after it all 250 are live; a column positioned by moshi_hot_codec_slot_set_fill has live rows nobody wrote, copied like any other.
+// No other column's state is touched. Each call returns -1 and changes nothing on any other kind of model (as moshi_hot_slot_fork / _save / _load
+// keep doing on these), for a bad index, and where a slot is not in the state the call requires.
+//  * fork: src open, dst closed and != src. Afterwards dst is open at src's position and, given the same input, yields the same output from then on.
+//  * save: slot b open. Writes a self-describing little-endian blob and returns the bytes written; buf == NULL: the bytes needed now (they grow by
+//    2 x layers x dim x 2 x rows per frame per frame until the ring is full); -1 when nbytes is too small. The slot is unchanged. The blob: magic "MCSL",
+//    format version 1, kind (1 decoder, 2 encoder), a reserved zero, a fingerprint (FNV-1a over the kind, the codec transformer's dim, heads, layers,
+//    capacity, rows per frame and ring type, and the (len, C) of every carried state in model order), total bytes, position, n - 48 bytes - then every
+//    state's column as F32 [len, C], each zero-padded to a multiple of 16 bytes, then per layer K and then V as H x n x D BF16. The same state always
+//    gives the same bytes.
+//  * load: slot b closed; nbytes must be the blob's exact size. A NULL or short header, a truncated or oversized buffer, a wrong magic, version, kind
+//    or fingerprint, a non-zero reserved field, a negative position and an n that does not follow from the position are refused before anything
+//    changes. The blob may come from any column of a model of the same kind of any B on any backend with the same fingerprint. Afterwards the slot is
+//    open at the blob's position and holds that conversation.
+GGML_API int     moshi_hot_codec_slot_fork(moshi_hot_model_t * m, int src, int dst);
+GGML_API int64_t moshi_hot_codec_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes);
+GGML_API int     moshi_hot_codec_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes);
+
 // ---- per-conversation sampling: a seed, temperatures and top-k values per column --------------------------------------------------------------------
 // In sampled mode (config temp > 0 and temp_text > 0) the sampler divides the top-k probabilities by Exp(1) noise that the host uploads per compute
 // (src/context.h:456-480, moshi/utils/sampling.h:4-64). By default that noise comes from libc rand() in one sweep over the whole [k, B] tensor, so a

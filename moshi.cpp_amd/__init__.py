@@ -65,7 +65,8 @@ class Stats(C.Structure):
                                          "float_batched_mms_in_last_plan", "float_acc_mms_in_last_plan",
                                          "pass_input_launches_in_last_plan", "pass_input_rows_in_last_plan",
                                          "convtr_column_groups_in_last_plan", "codec_attn_launches_in_last_plan",
-                                         "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan")]
+                                         "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan",
+                                         "state_copy_launches_in_last_plan", "state_copy_jobs_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

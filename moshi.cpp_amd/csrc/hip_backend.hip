@@ -342,7 +342,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -1299,6 +1299,54 @@ static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & gr
         grp.emit_pos = i;
     }
     return grp.a.n_jobs > 0;
+}
+
+// B'''''. codec slot snapshots (moshi_hot.cpp codec_state_graph): a run of cpy(a, b) of one unquantised type between contiguous tensors - each side
+//      one run of bytes - at least one side exactly ONE column of a [len, C, B] root (B > 1: a carried conv state), with nothing but layout nodes
+//      between the copies: one k_state_copy launch for up to STATE_COPY_MAX of them. The run is taken only if at least two of its jobs are columns of
+//      two or more rows (view ne[1] >= 2): a lone column copy (cond_cross in a tts fork) and 1-D row copies (transformer_out, cond_sum) stay the generic
+//      copies they always were. A copy whose bases or length are no multiples of 4 bytes, a side that leaves its root tensor, a source that overlaps its
+//      destination, or a copy that touches what an earlier job of the run writes (or writes what one reads) ends the run and stays a generic copy.
+struct state_copy_group : group { state_copy_args a; };
+// t as one run of bytes inside its root tensor; column: it is exactly one column of a 3-D root with ne[2] > 1
+static bool state_copy_side(const ggml_tensor * t, byte_range * span, bool * column) {
+    if (!t->data || ggml_is_quantized(t->type) || !ggml_is_contiguous(t)) return false;
+    const ggml_tensor * root = t;
+    while (root->view_src) root = root->view_src;
+    span->lo = (const char *) t->data; span->hi = span->lo + ggml_nbytes(t);
+    if (!root->data || span->hi <= span->lo || span->lo < (const char *) root->data || span->hi > (const char *) root->data + ggml_nbytes(root)) return false;
+    *column = false;
+    if (root != t && root->ne[2] > 1 && root->ne[3] == 1 && ggml_is_contiguous(root)) {
+        const int64_t off = span->lo - (const char *) root->data, col = (int64_t) root->nb[2];
+        *column = off % col == 0 && span->hi - span->lo == col;
+    }
+    return ((uintptr_t) span->lo | (uintptr_t) (span->hi - span->lo)) % 4 == 0;
+}
+static bool match_state_copies(const analysis & an, int pos, state_copy_group & grp) {
+    const ggml_cgraph * g = an.g;
+    memset(&grp.a, 0, sizeof(grp.a));
+    grp.members.clear();
+    std::vector<byte_range> reads, writes;
+    int wide = 0;
+    for (int i = pos; i < g->n_nodes && grp.a.n_jobs < STATE_COPY_MAX; i++) {
+        const ggml_tensor * cp = g->nodes[i];
+        if (is_view_op(cp->op) && !an.skip[(size_t) i]) continue;   // (the views that feed the next copy)
+        if (cp->op != GGML_OP_CPY || an.skip[(size_t) i] || uses_of(an, cp) != 0) break;
+        const ggml_tensor * a = cp->src[0];
+        byte_range ra, rb; bool col_a = false, col_b = false;
+        if (a->type != cp->type || !state_copy_side(a, &ra, &col_a) || !state_copy_side(cp, &rb, &col_b)) break;
+        if (ra.hi - ra.lo != rb.hi - rb.lo || !(col_a || col_b) || ra.overlaps(rb)) break;
+        bool hazard = false;
+        for (const byte_range & w : writes) if (w.overlaps(ra) || w.overlaps(rb)) hazard = true;
+        for (const byte_range & r : reads) if (r.overlaps(rb)) hazard = true;
+        if (hazard) break;
+        grp.a.job[grp.a.n_jobs++] = { ra.lo, (char *) rb.lo, (int64_t) (ra.hi - ra.lo) };
+        if ((col_a && a->ne[1] >= 2) || (col_b && cp->ne[1] >= 2)) wide++;
+        reads.push_back(ra); writes.push_back(rb);
+        grp.members.push_back(i);
+        grp.emit_pos = i;
+    }
+    return grp.a.n_jobs > 0 && wide >= 2;
 }
 
 // A'. several activation rows against Q4_K weights (batched prompt prefill): the int8-MFMA mat-mul with the activation producer
@@ -2590,6 +2638,18 @@ static void pass_ring_copies(planner & pl) {
     }
 }
 
+// codec slot snapshots: the conv-state column copies of a fork, a save or a load (moshi_hot.cpp codec_state_graph) - one launch for the whole run
+static void pass_state_copies(planner & pl) {
+    for (int i = 0; i < pl.g->n_nodes; i++) {
+        state_copy_group grp;
+        if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_CPY || !match_state_copies(pl.an, i, grp)) continue;
+        if (!claim_group(pl, grp)) continue;   // (claim: every member is a position the matcher's own loop stood on and tested an.skip for)
+        const state_copy_args sa = grp.a;
+        pl.at_pos[grp.emit_pos].push_back([=](hipStream_t s) { k_state_copy(s, sa); });
+        pl.p->n_state_copy_launches++; pl.p->n_state_copy_jobs += sa.n_jobs;
+    }
+}
+
 // attention blocks (they swallow set_rows / soft_max / two mul_mats): collected here, emitted after the mat-vec pass, which may absorb a short-ring
 // attention into the projection that consumes it
 static void pass_attention(planner & pl) {
@@ -3255,10 +3315,11 @@ static void merge_chains(planner & pl) {
 //   pass_row_copies        one launch for all rows instead of one per row: before pass_cpy_of_cont, whose pattern every single row is
 //   pass_matvecs           after the attention pass (see there); every remaining mul_mat of a supported shape
 //   pass_norm_affine       after the mat-vec pass: only a norm that no mat-vec prologue took
+//   pass_state_copies      last: it takes only column copies that no other pass wanted, so no plan that existed before it loses a node to it
 // (pass_ring_copies, pass_codec_convs, pass_cross_attention, pass_lowrank_embed, pass_cpy_of_cont, pass_timestep_of_add: no reason on record but their place)
 static void (* const fusion_passes[])(planner &) = {
     pass_heads_streams, pass_ring_copies, pass_attention, pass_codec_convs, pass_scalar_gathers, pass_samplers, pass_sampler_streams, pass_cross_attention,
-    pass_cross_attention_blocks, pass_lowrank_embed, pass_pass_inputs, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine,
+    pass_cross_attention_blocks, pass_lowrank_embed, pass_pass_inputs, pass_embed_sums, pass_row_copies, pass_cpy_of_cont, pass_timestep_of_add, pass_matvecs, pass_norm_affine, pass_state_copies,
 };
 
 static plan_t * build_plan(hip_ctx * c, ggml_cgraph * g, bool keep = true) {
@@ -3322,7 +3383,7 @@ static void run_steps_profiled(hip_ctx * c, plan_t * p) {
     }
 }
 
-// the twenty-two *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
+// the *_in_last_plan counters of ggml_mi355x_stats: what the plan of the graph computed last holds
 static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.kernels_in_last_plan = (int64_t) p->steps.size();
     c->stats.nodes_in_last_plan = p->n_nodes;
@@ -3337,6 +3398,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
+    c->stats.state_copy_launches_in_last_plan = p->n_state_copy_launches; c->stats.state_copy_jobs_in_last_plan = p->n_state_copy_jobs;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {

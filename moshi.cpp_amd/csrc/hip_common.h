@@ -267,6 +267,18 @@ void k_copy_rows(hipStream_t s, const copy_rows_args & a);
 struct ring_copy_job { const char * src; char * dst; int64_t src_hs, dst_hs; };
 struct ring_copy_args { int n_jobs, H; int64_t run_bytes; int blocks_per_run; ring_copy_job job[RING_COPY_MAX]; };
 void k_ring_copy(hipStream_t s, const ring_copy_args & a, int usable_cus);
+// Codec slot snapshots (moshi_hot_codec_slot_fork / _save / _load): a run of flat copies - one column of a [len, C, B] conv state, or a slice of a
+// contiguous staging tensor, each one run of bytes - as ONE launch. Job j = one cpy node: bytes contiguous bytes from src to dst. Unlike the ring copies
+// the jobs differ in length (24 bytes to 492 544 bytes in one run), so each is cut into pieces of STATE_COPY_PIECE bytes, one workgroup per piece:
+// first_piece[j] is the index of job j's first piece (first_piece[n_jobs] the grid), filled in by k_state_copy. Every base and length is a multiple of 4
+// bytes; a job whose bases and length are all multiples of 16 moves 16-byte vectors, any other job dwords. No job's destination overlaps another job's
+// source or destination (match_state_copies declines anything else). The table goes by value in the kernel arguments (32 x 24 bytes + 33 indices); a
+// longer run takes several launches.
+#define STATE_COPY_MAX 32
+#define STATE_COPY_PIECE 16384
+struct state_copy_job { const char * src; char * dst; int64_t bytes; };
+struct state_copy_args { int n_jobs; int first_piece[STATE_COPY_MAX + 1]; state_copy_job job[STATE_COPY_MAX]; };
+void k_state_copy(hipStream_t s, const state_copy_args & a);
 
 // in_proj + the attention that consumes it as ONE launch of 256 resident workgroups (inproj_attn_kernel): `a` is the RMS-normed Q4_K mat-vec whose output
 // holds `at`'s q | k | v. supported(): shapes, and whether the whole grid fits the compute units the stream may use (the parts of a head wait for each

@@ -2041,6 +2041,53 @@ void k_ring_copy(hipStream_t s, const ring_copy_args & in, int usable_cus) {
     ring_copy_kernel<<<(unsigned) (runs * bpr), 256, 0, s>>>(a);
 }
 
+// Codec slot snapshots (moshi_hot_codec_slot_fork / _save / _load): every conv-state copy of one snapshot as ONE launch. Job j is one run of bytes, 24
+// bytes (the encoder's first conv tail) to 492 544 bytes (the decoder's last partial) in the same table, so the grid is laid out by pieces: workgroup x
+// copies piece x - first_piece[j] of the job j whose pieces hold x, found by a scan of the table that every lane does alike (blockIdx alone decides:
+// scalar kernel-argument loads, no workgroup waits for another). A piece is STATE_COPY_PIECE bytes, the last one of a job what is left. The vector width
+// is chosen per job, so it is wave-uniform: 16 bytes per lane where both bases and the length are multiples of 16 (a piece boundary is one too), four
+// loads in flight before the first store; dwords for any other job (column b of a 24-byte tail starts at 24 b). Elements i < n only: no lane reads or
+// writes a byte outside its job's range - the bytes next to it are another conversation's state. Every offset is 64 bit.
+template <typename V> static __device__ __forceinline__ void state_copy_piece(const V * __restrict__ src, V * __restrict__ dst, int n) {
+    for (int i = (int) threadIdx.x; i < n; i += 4 * 256) {
+        const bool p1 = i + 256 < n, p2 = i + 512 < n, p3 = i + 768 < n;
+        V v0 = src[i], v1 = {}, v2 = {}, v3 = {};
+        if (p1) v1 = src[i + 256];
+        if (p2) v2 = src[i + 512];
+        if (p3) v3 = src[i + 768];
+        dst[i] = v0;
+        if (p1) dst[i + 256] = v1;
+        if (p2) dst[i + 512] = v2;
+        if (p3) dst[i + 768] = v3;
+    }
+}
+__global__ void __launch_bounds__(256) state_copy_kernel(state_copy_args a) {
+    const int x = (int) blockIdx.x;
+    int j = 0;
+    for (int k = 1; k < a.n_jobs; k++) if (a.first_piece[k] <= x) j = k;
+    const state_copy_job jb = a.job[j];
+    const int64_t begin = (int64_t) (x - a.first_piece[j]) * STATE_COPY_PIECE;
+    if (begin >= jb.bytes) return;
+    const int64_t left = jb.bytes - begin;
+    const int len = (int) (left < STATE_COPY_PIECE ? left : STATE_COPY_PIECE);
+    if ((((uintptr_t) jb.src | (uintptr_t) jb.dst | (uintptr_t) jb.bytes) & 15) == 0) state_copy_piece((const uint4 *) (jb.src + begin), (uint4 *) (jb.dst + begin), len >> 4);
+    else state_copy_piece((const uint32_t *) (jb.src + begin), (uint32_t *) (jb.dst + begin), len >> 2);
+}
+void k_state_copy(hipStream_t s, const state_copy_args & in) {
+    GGML_ASSERT(in.n_jobs >= 1 && in.n_jobs <= STATE_COPY_MAX);
+    state_copy_args a = in;
+    int64_t pieces = 0;
+    for (int j = 0; j < a.n_jobs; j++) {
+        const state_copy_job & jb = a.job[j];
+        GGML_ASSERT(jb.src && jb.dst && jb.bytes >= 4 && (((uintptr_t) jb.src | (uintptr_t) jb.dst | (uintptr_t) jb.bytes) & 3) == 0);
+        a.first_piece[j] = (int) pieces;
+        pieces += (jb.bytes + STATE_COPY_PIECE - 1) / STATE_COPY_PIECE;
+        GGML_ASSERT(pieces < (1 << 30));
+    }
+    for (int j = a.n_jobs; j <= STATE_COPY_MAX; j++) a.first_piece[j] = (int) pieces;
+    state_copy_kernel<<<(unsigned) pieces, 256, 0, s>>>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // merged launches of the Temporal layer: shared definitions (the kernel itself: inproj_attn_kernel below)
 // ---------------------------------------------------------------------------------------------------

@@ -3252,6 +3252,151 @@ extern "C" int moshi_hot_slot_fork_full(moshi_hot_model_t * m, int src, int dst)
 extern "C" int64_t moshi_hot_slot_save_full(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) { return slot_save(m, b, buf, nbytes, true); }
 extern "C" int moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) { return slot_load(m, b, buf, nbytes, true); }
 
+// ---- codec slot snapshots (moshi_hot.h): fork, save and load a decoder or encoder slot's state -------------------------------------------------------
+namespace {
+// The blob: this header, column b of every carried conv state in model order (each F32 [len, C], zero-padded to a multiple of 16 bytes), then per codec
+// transformer layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous).
+struct CodecBlobHeader {
+    uint32_t magic, version, kind, reserved;   // kind: 1 a decoder slot, 2 an encoder slot
+    uint64_t fingerprint;
+    int64_t total_bytes, pos, n_rows;          // pos in frames; n_rows = min(pos x rows per frame, capacity): the live ring rows
+};
+const uint32_t CODEC_BLOB_MAGIC = 0x4C53434Du, CODEC_BLOB_VERSION = 1;   // "MCSL"
+static_assert(sizeof(CodecBlobHeader) == 48, "the blob header has no padding and is a multiple of 16 bytes");
+
+uint32_t codec_kind(const moshi_hot_model * m) { return m->kind == ModelKind::codec_slots ? 1u : 2u; }
+Transformer & codec_tr(moshi_hot_model * m) { return m->kind == ModelKind::codec_slots ? m->dec_tr : m->enc_tr; }
+// ring rows a frame writes (dec_T / enc_T): known once the model's graph is built, which a snapshot call does if no frame has run yet
+int64_t codec_rows_per_frame(moshi_hot_model * m) {
+    if (m->kind == ModelKind::codec_slots) { if (!m->g_dec) build_decode_graph(m); return m->dec_T; }
+    if (!m->g_enc) build_encode_graph(m);
+    return m->enc_T;
+}
+// the carried conv states in model order: the tensors moshi_hot_codec_slot_open clears, [len, C, B] F32 each
+std::vector<T> codec_states(moshi_hot_model * m) {
+    std::vector<T> out;
+    auto add = [&](T t) { if (t) out.push_back(t); };
+    add(m->upsample.prev);
+    for (auto & cv : m->dec_convs) add(cv.prev);
+    for (auto & ct : m->dec_convtrs) add(ct.prev);
+    for (auto & rb : m->dec_res) { add(rb.block1.prev); add(rb.block3.prev); }
+    for (auto & cv : m->enc_convs) add(cv.prev);
+    for (auto & rb : m->enc_res) { add(rb.block1.prev); add(rb.block3.prev); }
+    add(m->downsample.prev);
+    return out;
+}
+int64_t codec_state_floats(T t) { return (t->ne[0] * t->ne[1] + 3) / 4 * 4; }   // a column, padded to 16 bytes
+int64_t codec_states_bytes(moshi_hot_model * m) {
+    int64_t n = 0;
+    for (T t : codec_states(m)) n += codec_state_floats(t) * 4;
+    return n;
+}
+int64_t codec_ring_bytes(moshi_hot_model * m, int64_t n_rows) {
+    const Transformer & tr = codec_tr(m);
+    return 2 * (int64_t) tr.layers.size() * (int64_t) tr.dim * n_rows * 2;   // 2 x layers x H x n x D BF16
+}
+int64_t codec_live_rows(moshi_hot_model * m, int64_t pos) {
+    const int64_t C = codec_tr(m).capacity, T_ = codec_rows_per_frame(m);
+    return pos >= (C + T_ - 1) / T_ ? C : pos * T_;
+}
+// FNV-1a (as slot_fingerprint) over what a blob's bytes depend on
+uint64_t codec_fingerprint(moshi_hot_model * m) {
+    const Transformer & tr = codec_tr(m);
+    uint64_t h = 0xcbf29ce484222325ull;
+    auto mix = [&](int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; };
+    mix(codec_kind(m)); mix(tr.dim); mix(tr.heads); mix((int64_t) tr.layers.size()); mix(tr.capacity); mix(codec_rows_per_frame(m)); mix(tr.layers[0].kcache->type);
+    for (T t : codec_states(m)) { mix(t->ne[0]); mix(t->ne[1]); }
+    return h;
+}
+
+// The device half as ONE scratch graph, built as slot_state_graph is: per codec transformer layer a cpy of K and a cpy of V between [D, n, H] views (the
+// LM snapshot's nodes: one k_ring_copy launch), then one cpy per carried conv state between the contiguous [len, C] view of column src and that of column
+// dst - for a save or a load (dst < 0 / src < 0) the other side a 16-byte-aligned slice of ONE contiguous F32 staging tensor, uploaded from states_in
+// first or read back to states_out afterwards (its padding zeroed). The device plan turns the state copies into one launch (hip_backend.hip
+// match_state_copies); the oracle and a plan without fusion run them as the generic copies they are.
+void codec_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * states_in, const void * rings_in, void * states_out, void * rings_out) {
+    Builder & s = *m->scratch;
+    const Transformer & tr = codec_tr(m);
+    const int64_t H = tr.heads, D = tr.dim / H;
+    const bool staged = src < 0 || dst < 0;
+    const std::vector<T> states = codec_states(m);
+    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
+    T st_stage = staged ? s.tensor(GGML_TYPE_F32, codec_states_bytes(m) / 4) : nullptr;
+    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
+    auto column = [&](T t, int b) { return ggml_view_2d(s, t, t->ne[0], t->ne[1], t->nb[1], (size_t) b * t->nb[2]); };
+    int64_t j = 0;
+    if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
+        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
+        j++;
+        s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
+    }
+    int64_t off = 0;   // floats into the staging tensor
+    for (T t : states) {
+        T part = st_stage ? ggml_view_2d(s, st_stage, t->ne[0], t->ne[1], (size_t) t->ne[0] * 4, (size_t) off * 4) : nullptr;
+        off += codec_state_floats(t);
+        s.expand(ggml_cpy(s, src >= 0 ? column(t, src) : part, dst >= 0 ? column(t, dst) : part));
+    }
+    ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph, as slot_state_graph
+    s.alloc();
+    if (src < 0) {
+        ggml_backend_tensor_set(st_stage, states_in, 0, ggml_nbytes(st_stage));
+        if (stage) ggml_backend_tensor_set(stage, rings_in, 0, ggml_nbytes(stage));
+    }
+    s.compute();
+    if (dst < 0) {
+        ggml_backend_tensor_get(st_stage, states_out, 0, ggml_nbytes(st_stage));
+        if (stage) ggml_backend_tensor_get(stage, rings_out, 0, ggml_nbytes(stage));
+    }
+    ggml_backend_synchronize(m->be);   // the calls block
+    s.release_scratch();
+    ggml_backend_mi355x_set_capture(m->be, 1);
+    if (dst < 0) {   // the padding behind each column was never written on the device: zeros in the blob
+        float * out = (float *) states_out;
+        for (T t : states) {
+            for (int64_t i = t->ne[0] * t->ne[1]; i < codec_state_floats(t); i++) out[i] = 0.f;
+            out += codec_state_floats(t);
+        }
+    }
+}
+}  // namespace
+
+extern "C" int moshi_hot_codec_slot_fork(moshi_hot_model_t * m, int src, int dst) {
+    moshi_hot_model::CodecColumn * a = codec_slot(m, src), * b = codec_slot(m, dst);
+    if (!a || !b || src == dst || !a->open || b->open || a->pos < 0) return -1;
+    codec_state_graph(m, src, dst, codec_live_rows(m, a->pos), nullptr, nullptr, nullptr, nullptr);
+    *b = *a;
+    return 0;
+}
+extern "C" int64_t moshi_hot_codec_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) {
+    const moshi_hot_model::CodecColumn * col = codec_slot(m, b);
+    if (!col || !col->open || col->pos < 0 || codec_tr(m).layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    const int64_t n = codec_live_rows(m, col->pos), host = (int64_t) sizeof(CodecBlobHeader) + codec_states_bytes(m), total = host + codec_ring_bytes(m, n);
+    if (!buf) return total;
+    if (nbytes < total) return -1;
+    uint8_t * out = (uint8_t *) buf;
+    CodecBlobHeader h;
+    memset(&h, 0, sizeof(h));
+    h.magic = CODEC_BLOB_MAGIC; h.version = CODEC_BLOB_VERSION; h.kind = codec_kind(m); h.fingerprint = codec_fingerprint(m);
+    h.total_bytes = total; h.pos = col->pos; h.n_rows = n;
+    memcpy(out, &h, sizeof(h));
+    codec_state_graph(m, b, -1, n, nullptr, nullptr, out + sizeof(h), out + host);
+    return total;
+}
+extern "C" int moshi_hot_codec_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) {
+    moshi_hot_model::CodecColumn * col = codec_slot(m, b);
+    if (!col || col->open || !buf || nbytes < (int64_t) sizeof(CodecBlobHeader) || codec_tr(m).layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    const uint8_t * in = (const uint8_t *) buf;
+    CodecBlobHeader h;
+    memcpy(&h, in, sizeof(h));
+    if (h.magic != CODEC_BLOB_MAGIC || h.version != CODEC_BLOB_VERSION || h.kind != codec_kind(m) || h.reserved != 0 || h.fingerprint != codec_fingerprint(m)) return -1;
+    if (h.pos < 0 || h.n_rows != codec_live_rows(m, h.pos)) return -1;
+    const int64_t host = (int64_t) sizeof(CodecBlobHeader) + codec_states_bytes(m);
+    if (h.total_bytes != host + codec_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
+    codec_state_graph(m, -1, b, h.n_rows, in + sizeof(h), in + host, nullptr, nullptr);
+    col->pos = h.pos; col->open = true;
+    return 0;
+}
+
 static const int32_t PERSONAPLEX_PROMPT_TOKENS[PERSONAPLEX_PROMPT_COLUMNS] ={ 3, 948, 243, 1178, 546, 1736, 1030, 1978, 2008, 430, 1268, 381, 1611, 1095, 1495, 56, 472 };
 extern "C" const int32_t * moshi_hot_personaplex_prompt_tokens(void) { return PERSONAPLEX_PROMPT_TOKENS; }
 

@@ -142,6 +142,9 @@ SIGNATURES = {
     "moshi_hot_codec_slot_close": (C.c_int, [P, C.c_int]),
     "moshi_hot_codec_slot_position": (C.c_int64, [P, C.c_int]),
     "moshi_hot_codec_slot_set_fill": (None, [P, C.c_int, C.c_int64]),
+    "moshi_hot_codec_slot_fork": (C.c_int, [P, C.c_int, C.c_int]),
+    "moshi_hot_codec_slot_save": (C.c_int64, [P, C.c_int, P, C.c_int64]),
+    "moshi_hot_codec_slot_load": (C.c_int, [P, C.c_int, P, C.c_int64]),
     "moshi_hot_mimi_decode_slots": (C.c_int, [P, P, P, P]),
     "moshi_hot_create_encoder_slots": (P, [P, C.POINTER(Config), C.c_uint64, C.c_int]),
     "moshi_hot_mimi_encode_slots": (C.c_int, [P, P, P, P]),
