@@ -1122,7 +1122,7 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     return true;
 }
 
-// the decoder-slots form: Tn = 2 rows of B > 1 columns (moshi_hot.cpp transformer_graph_build_codec_slots) - mask [C, Tn, 1, B], index [Tn, 1, B] and the
+// the decoder-slots form: Tn = 2 rows of B > 1 columns (moshi_hot.cpp transformer_graph_build_columns) - mask [C, Tn, 1, B], index [Tn, 1, B] and the
 // RoPE table [D, Tn * B] viewed as [D/2, Tn, 1, B] halves, each column's block dense and one behind the other
 static bool match_attention_codec_slots(const analysis & an, int pos, attn_group & grp) {
     attn_chain c; rope_pair r;
@@ -1248,104 +1248,101 @@ static bool match_timestep_of_add(const analysis & an, int pos, timestep_group &
     return true;
 }
 
-// B''''. slot snapshots (moshi_hot.cpp slot_state_graph): a run of cpy(a, b) of one type between [D, n, H] row-range views - each head one contiguous run
-//      of n x D elements on both sides - at least one side inside ONE column of a [D, C, H, B] ring (B > 1), with nothing but layout nodes between the
-//      copies: one k_ring_copy launch for up to RING_COPY_MAX of them. A copy whose bases, head strides or run length are no multiples of 16 bytes, whose
-//      ranges overlap, or that touches what an earlier job of the run writes (or writes what one reads) is declined and stays a generic copy.
+// B''''. snapshots (moshi_hot.cpp state_graph): a run of cpy(a, b) of one type with nothing but layout nodes between the copies, at least one side of each
+//      inside ONE column of a B-column root (B > 1), as one launch. Two forms on one run walk, which differ in what a side must be:
+//      ring copies   [D, n, H] row-range views - each head one contiguous run of n x D elements on both sides - a side inside one column of a [D, C, H, B]
+//                    ring: one k_ring_copy launch for up to RING_COPY_MAX of them. Bases, head strides and run length are multiples of 16 bytes, and H
+//                    and the run length are the same for the whole run.
+//      state copies  contiguous unquantised tensors - each side one run of bytes - a side exactly one column of a [len, C, B] root (a carried conv
+//                    state): one k_state_copy launch for up to STATE_COPY_MAX of them. Bases and length are multiples of 4 bytes. The run is taken only
+//                    if at least two of its jobs are columns of two or more rows (view ne[1] >= 2): a lone column copy (cond_cross in a tts fork) and
+//                    1-D row copies (transformer_out, cond_sum) stay the generic copies they always were.
+//      A copy that fails its form's test, a side that leaves its root tensor, a source that overlaps its destination, or a copy that touches what an
+//      earlier job of the run writes (or writes what one reads) ends the run and stays a generic copy.
 struct ring_copy_group : group { ring_copy_args a; };
+struct state_copy_group : group { state_copy_args a; };
 struct byte_range { const char * lo, * hi; bool overlaps(const byte_range & o) const { return lo < o.hi && o.lo < hi; } };
-// t as H runs of contiguous bytes inside its root tensor: base, head stride, run length and the range they span
-static bool ring_copy_side(const ggml_tensor * t, const char ** base, int64_t * hs, int64_t * run, byte_range * span, bool * ring_column) {
-    const int64_t es = (int64_t) ggml_type_size(t->type);
-    if (!t->data || ggml_is_quantized(t->type) || t->ne[3] != 1 || (int64_t) t->nb[0] != es || (int64_t) t->nb[1] != t->ne[0] * es) return false;
+struct copy_side { byte_range span; bool column; };
+// sd.span (the bytes of t) against t's root tensor: false when it leaves the root. sd.column: t is a view inside one column of the root along dimension
+// d (ne[d] > 1), in one of two senses:
+//   exact = false (ring copies)   the span lies within a column's nb[d] bytes: some rows of every head of one ring column
+//   exact = true  (state copies)  the root is contiguous and ends with d, and the span is one whole column of it, first byte to last
+static bool copy_side_in_root(const ggml_tensor * t, int d, bool exact, copy_side & sd) {
     const ggml_tensor * root = t;
     while (root->view_src) root = root->view_src;
-    *base = (const char *) t->data; *hs = (int64_t) t->nb[2]; *run = t->ne[0] * t->ne[1] * es;
-    if (*hs < *run) return false;
-    span->lo = *base; span->hi = *base + (t->ne[2] - 1) * *hs + *run;
-    if (!root->data || span->lo < (const char *) root->data || span->hi > (const char *) root->data + ggml_nbytes(root)) return false;
-    // inside one column of a B-column ring?
-    *ring_column = false;
-    if (root != t && root->ne[3] > 1 && root->nb[3] > 0) {
-        const int64_t off = span->lo - (const char *) root->data, col = off / (int64_t) root->nb[3];
-        *ring_column = span->hi <= (const char *) root->data + (col + 1) * (int64_t) root->nb[3];
+    const byte_range & sp = sd.span;
+    if (!root->data || sp.lo < (const char *) root->data || sp.hi > (const char *) root->data + ggml_nbytes(root)) return false;
+    sd.column = false;
+    if (root != t && root->ne[d] > 1 && root->nb[d] > 0 && (!exact || (root->ne[3] == 1 && ggml_is_contiguous(root)))) {
+        const int64_t col = (int64_t) root->nb[d], off = sp.lo - (const char *) root->data;
+        sd.column = exact ? off % col == 0 && sp.hi - sp.lo == col : sp.hi <= (const char *) root->data + (off / col + 1) * col;
     }
-    return ((uintptr_t) *base | (uintptr_t) *hs | (uintptr_t) *run) % 16 == 0;
+    return true;
+}
+// t as H runs of contiguous bytes inside its root tensor: base span.lo, head stride nb[2], run length *run
+static bool ring_copy_side(const ggml_tensor * t, int64_t * run, copy_side & sd) {
+    const int64_t es = (int64_t) ggml_type_size(t->type), hs = (int64_t) t->nb[2];
+    if (!t->data || ggml_is_quantized(t->type) || t->ne[3] != 1 || (int64_t) t->nb[0] != es || (int64_t) t->nb[1] != t->ne[0] * es) return false;
+    *run = t->ne[0] * t->ne[1] * es;
+    if (hs < *run) return false;
+    sd.span.lo = (const char *) t->data; sd.span.hi = sd.span.lo + (t->ne[2] - 1) * hs + *run;
+    return copy_side_in_root(t, 3, false, sd) && ((uintptr_t) sd.span.lo | (uintptr_t) hs | (uintptr_t) *run) % 16 == 0;
+}
+// t as one run of bytes inside its root tensor
+static bool state_copy_side(const ggml_tensor * t, copy_side & sd) {
+    if (!t->data || ggml_is_quantized(t->type) || !ggml_is_contiguous(t) || ggml_nbytes(t) == 0) return false;
+    sd.span.lo = (const char *) t->data; sd.span.hi = sd.span.lo + ggml_nbytes(t);
+    return copy_side_in_root(t, 2, true, sd) && ((uintptr_t) sd.span.lo | (uintptr_t) (sd.span.hi - sd.span.lo)) % 4 == 0;
+}
+// The run walk from node pos on, for up to max_jobs copies: sides(cp, src, dst) resolves a copy's two sides under its form's conditions, take(cp, src, dst)
+// appends the job of a copy the walk has accepted (job grp.members.size()). -> the number of jobs
+template <class Sides, class Take> static int walk_copy_run(const analysis & an, int pos, int max_jobs, group & grp, Sides sides, Take take) {
+    const ggml_cgraph * g = an.g;
+    grp.members.clear();
+    std::vector<byte_range> reads, writes;
+    for (int i = pos; i < g->n_nodes && (int) grp.members.size() < max_jobs; i++) {
+        const ggml_tensor * cp = g->nodes[i];
+        if (is_view_op(cp->op) && !an.skip[(size_t) i]) continue;   // (the views that feed the next copy)
+        if (cp->op != GGML_OP_CPY || an.skip[(size_t) i] || uses_of(an, cp) != 0) break;
+        copy_side sa, sb;
+        if (cp->src[0]->type != cp->type || !sides(cp, sa, sb)) break;
+        const byte_range & ra = sa.span, & rb = sb.span;
+        if (!(sa.column || sb.column) || ra.overlaps(rb)) break;
+        bool hazard = false;
+        for (const byte_range & w : writes) if (w.overlaps(ra) || w.overlaps(rb)) hazard = true;
+        for (const byte_range & r : reads) if (r.overlaps(rb)) hazard = true;
+        if (hazard) break;
+        take(cp, sa, sb);
+        reads.push_back(ra); writes.push_back(rb);
+        grp.members.push_back(i);
+        grp.emit_pos = i;
+    }
+    return (int) grp.members.size();
 }
 static bool match_ring_copies(const analysis & an, int pos, ring_copy_group & grp) {
-    const ggml_cgraph * g = an.g;
-    memset(&grp.a, 0, sizeof(grp.a));
-    grp.members.clear();
-    std::vector<byte_range> reads, writes;
-    for (int i = pos; i < g->n_nodes && grp.a.n_jobs < RING_COPY_MAX; i++) {
-        const ggml_tensor * cp = g->nodes[i];
-        if (is_view_op(cp->op) && !an.skip[(size_t) i]) continue;   // (the views that feed the next copy)
-        if (cp->op != GGML_OP_CPY || an.skip[(size_t) i] || uses_of(an, cp) != 0) break;
+    ring_copy_args & ar = grp.a;
+    memset(&ar, 0, sizeof(ar));
+    ar.n_jobs = walk_copy_run(an, pos, RING_COPY_MAX, grp, [&](const ggml_tensor * cp, copy_side & sa, copy_side & sb) {
         const ggml_tensor * a = cp->src[0];
-        if (a->type != cp->type || a->ne[0] != cp->ne[0] || a->ne[1] != cp->ne[1] || a->ne[2] != cp->ne[2] || cp->ne[2] < 2) break;
-        ring_copy_job jb; int64_t run_a = 0, run_b = 0; byte_range ra, rb; bool col_a = false, col_b = false; const char * dst = nullptr;
-        if (!ring_copy_side(a, &jb.src, &jb.src_hs, &run_a, &ra, &col_a) || !ring_copy_side(cp, &dst, &jb.dst_hs, &run_b, &rb, &col_b)) break;
-        if (run_a != run_b || !(col_a || col_b) || ra.overlaps(rb)) break;
-        if (grp.a.n_jobs && (cp->ne[2] != grp.a.H || run_a != grp.a.run_bytes)) break;
-        bool hazard = false;
-        for (const byte_range & w : writes) if (w.overlaps(ra) || w.overlaps(rb)) hazard = true;
-        for (const byte_range & r : reads) if (r.overlaps(rb)) hazard = true;
-        if (hazard) break;
-        jb.dst = (char *) dst;
-        grp.a.H = (int) cp->ne[2]; grp.a.run_bytes = run_a;
-        grp.a.job[grp.a.n_jobs++] = jb;
-        reads.push_back(ra); writes.push_back(rb);
-        grp.members.push_back(i);
-        grp.emit_pos = i;
-    }
-    return grp.a.n_jobs > 0;
-}
-
-// B'''''. codec slot snapshots (moshi_hot.cpp codec_state_graph): a run of cpy(a, b) of one unquantised type between contiguous tensors - each side
-//      one run of bytes - at least one side exactly ONE column of a [len, C, B] root (B > 1: a carried conv state), with nothing but layout nodes
-//      between the copies: one k_state_copy launch for up to STATE_COPY_MAX of them. The run is taken only if at least two of its jobs are columns of
-//      two or more rows (view ne[1] >= 2): a lone column copy (cond_cross in a tts fork) and 1-D row copies (transformer_out, cond_sum) stay the generic
-//      copies they always were. A copy whose bases or length are no multiples of 4 bytes, a side that leaves its root tensor, a source that overlaps its
-//      destination, or a copy that touches what an earlier job of the run writes (or writes what one reads) ends the run and stays a generic copy.
-struct state_copy_group : group { state_copy_args a; };
-// t as one run of bytes inside its root tensor; column: it is exactly one column of a 3-D root with ne[2] > 1
-static bool state_copy_side(const ggml_tensor * t, byte_range * span, bool * column) {
-    if (!t->data || ggml_is_quantized(t->type) || !ggml_is_contiguous(t)) return false;
-    const ggml_tensor * root = t;
-    while (root->view_src) root = root->view_src;
-    span->lo = (const char *) t->data; span->hi = span->lo + ggml_nbytes(t);
-    if (!root->data || span->hi <= span->lo || span->lo < (const char *) root->data || span->hi > (const char *) root->data + ggml_nbytes(root)) return false;
-    *column = false;
-    if (root != t && root->ne[2] > 1 && root->ne[3] == 1 && ggml_is_contiguous(root)) {
-        const int64_t off = span->lo - (const char *) root->data, col = (int64_t) root->nb[2];
-        *column = off % col == 0 && span->hi - span->lo == col;
-    }
-    return ((uintptr_t) span->lo | (uintptr_t) (span->hi - span->lo)) % 4 == 0;
+        int64_t run_a = 0, run_b = 0;
+        if (a->ne[0] != cp->ne[0] || a->ne[1] != cp->ne[1] || a->ne[2] != cp->ne[2] || cp->ne[2] < 2) return false;
+        if (!ring_copy_side(a, &run_a, sa) || !ring_copy_side(cp, &run_b, sb) || run_a != run_b) return false;
+        return grp.members.empty() || (cp->ne[2] == ar.H && run_a == ar.run_bytes);
+    }, [&](const ggml_tensor * cp, const copy_side & sa, const copy_side & sb) {
+        ar.H = (int) cp->ne[2]; ar.run_bytes = cp->ne[0] * cp->ne[1] * (int64_t) ggml_type_size(cp->type);
+        ar.job[grp.members.size()] = { sa.span.lo, (char *) sb.span.lo, (int64_t) cp->src[0]->nb[2], (int64_t) cp->nb[2] };
+    });
+    return ar.n_jobs > 0;
 }
 static bool match_state_copies(const analysis & an, int pos, state_copy_group & grp) {
-    const ggml_cgraph * g = an.g;
     memset(&grp.a, 0, sizeof(grp.a));
-    grp.members.clear();
-    std::vector<byte_range> reads, writes;
     int wide = 0;
-    for (int i = pos; i < g->n_nodes && grp.a.n_jobs < STATE_COPY_MAX; i++) {
-        const ggml_tensor * cp = g->nodes[i];
-        if (is_view_op(cp->op) && !an.skip[(size_t) i]) continue;   // (the views that feed the next copy)
-        if (cp->op != GGML_OP_CPY || an.skip[(size_t) i] || uses_of(an, cp) != 0) break;
-        const ggml_tensor * a = cp->src[0];
-        byte_range ra, rb; bool col_a = false, col_b = false;
-        if (a->type != cp->type || !state_copy_side(a, &ra, &col_a) || !state_copy_side(cp, &rb, &col_b)) break;
-        if (ra.hi - ra.lo != rb.hi - rb.lo || !(col_a || col_b) || ra.overlaps(rb)) break;
-        bool hazard = false;
-        for (const byte_range & w : writes) if (w.overlaps(ra) || w.overlaps(rb)) hazard = true;
-        for (const byte_range & r : reads) if (r.overlaps(rb)) hazard = true;
-        if (hazard) break;
-        grp.a.job[grp.a.n_jobs++] = { ra.lo, (char *) rb.lo, (int64_t) (ra.hi - ra.lo) };
-        if ((col_a && a->ne[1] >= 2) || (col_b && cp->ne[1] >= 2)) wide++;
-        reads.push_back(ra); writes.push_back(rb);
-        grp.members.push_back(i);
-        grp.emit_pos = i;
-    }
+    grp.a.n_jobs = walk_copy_run(an, pos, STATE_COPY_MAX, grp, [&](const ggml_tensor * cp, copy_side & sa, copy_side & sb) {
+        return state_copy_side(cp->src[0], sa) && state_copy_side(cp, sb) && sa.span.hi - sa.span.lo == sb.span.hi - sb.span.lo;
+    }, [&](const ggml_tensor * cp, const copy_side & sa, const copy_side & sb) {
+        grp.a.job[grp.members.size()] = { sa.span.lo, (char *) sb.span.lo, (int64_t) (sa.span.hi - sa.span.lo) };
+        if ((sa.column && cp->src[0]->ne[1] >= 2) || (sb.column && cp->ne[1] >= 2)) wide++;
+    });
     return grp.a.n_jobs > 0 && wide >= 2;
 }
 
@@ -1716,15 +1713,46 @@ static bool match_lowrank_embed(const analysis & an, int pos, lowrank_group & gr
 struct step_group : group { std::vector<step_fn> steps; sample_args smp; vq_level_args vq; bool has_vq = false; };   // smp / vq: match_sampler's / match_vq_level's arguments
 
 static bool is_elu(const ggml_tensor * t) { return t->op == GGML_OP_UNARY && t->op_params[0] == GGML_UNARY_OP_ELU && t->view_src == NULL; }
+// an elu in front of a convolution's input x, all `uses` uses of it the group's: it joins the members and x becomes its input. -> 1 if so, else 0
+static int peel_elu(const analysis & an, const ggml_tensor *& x, int uses, std::vector<int> & members) {
+    if (!is_elu(x) || uses_of(an, x) != uses || pos_of(an, x) < 0) return 0;
+    members.push_back(pos_of(an, x));
+    x = x->src[0];
+    return 1;
+}
+// add(x, b) with b a contiguous F32 leaf of OC values behind ne[0] = 1: the bias of a codec convolution (the conv forms also ask for ne[1] = OC, the
+// transposed-conv tail never did). -> b, or null
+static const ggml_tensor * conv_bias_of(const ggml_tensor * add, const ggml_tensor * x, int64_t OC) {
+    if (!add || add->op != GGML_OP_ADD || add->view_src || add->src[0] != x) return nullptr;
+    const ggml_tensor * b = add->src[1];
+    return b->op == GGML_OP_NONE && b->type == GGML_TYPE_F32 && b->ne[0] == 1 && ggml_nelements(b) == OC && ggml_is_contiguous(b) ? b : nullptr;
+}
+// cont(transpose(out)) as out's only use, a contiguous F32 [n0, n1]: the group's last launch stores through the cont's strides instead - one launch
+// less, the same values. -> the cont (it and the transpose join the members), or null
+static const ggml_tensor * transposed_cont_of(const analysis & an, const ggml_tensor * out, int64_t n0, int64_t n1, std::vector<int> & members) {
+    const ggml_tensor * trn = uses_of(an, out) == 1 ? sole_consumer(an, out) : nullptr;
+    const ggml_tensor * ct = trn && trn->op == GGML_OP_TRANSPOSE && uses_of(an, trn) == 1 ? sole_consumer(an, trn) : nullptr;
+    if (!ct || ct->op != GGML_OP_CONT || ct->type != GGML_TYPE_F32 || !ggml_is_contiguous(ct) || !ct->data || ct->ne[0] != n0 || ct->ne[1] != n1 || ggml_nelements(ct) != n0 * n1 ||
+        pos_of(an, trn) < 0 || pos_of(an, ct) < 0 || getenv("MI355X_NO_CONV_TRANSPOSE_FOLD")) return nullptr;
+    members.push_back(pos_of(an, trn)); members.push_back(pos_of(an, ct));
+    return ct;
+}
+// the head of both conv forms: mm = mul_mat(reshape(im2col(w, .)), reshape(w)), F16 operands, the im2col, its reshape and the product used once each
+struct conv_head { const ggml_tensor * ra, * rw, * im, * w; };
+static bool match_conv_head(const analysis & an, const ggml_tensor * mm, conv_head & h) {
+    if (mm->op != GGML_OP_MUL_MAT) return false;
+    h.ra = mm->src[0]; h.rw = mm->src[1];
+    if (h.ra->op != GGML_OP_RESHAPE || h.rw->op != GGML_OP_RESHAPE) return false;
+    h.im = h.ra->src[0]; h.w = h.rw->src[0];
+    if (h.im->op != GGML_OP_IM2COL || h.im->src[0] != h.w || h.im->type != GGML_TYPE_F16 || h.w->type != GGML_TYPE_F16 || !ggml_is_contiguous(h.w)) return false;
+    return uses_of(an, h.im) == 1 && uses_of(an, h.ra) == 1 && uses_of(an, mm) == 1;
+}
 
 static bool match_conv(const analysis & an, int pos, step_group & grp, emitter & em) {
     const ggml_tensor * mm = an.g->nodes[pos];
-    if (mm->op != GGML_OP_MUL_MAT) return false;
-    const ggml_tensor * ra = mm->src[0], * rw = mm->src[1];
-    if (ra->op != GGML_OP_RESHAPE || rw->op != GGML_OP_RESHAPE) return false;
-    const ggml_tensor * im = ra->src[0], * w = rw->src[0];
-    if (im->op != GGML_OP_IM2COL || im->src[0] != w || im->type != GGML_TYPE_F16 || w->type != GGML_TYPE_F16 || !ggml_is_contiguous(w)) return false;
-    if (uses_of(an, im) != 1 || uses_of(an, ra) != 1 || uses_of(an, mm) != 1) return false;
+    conv_head h;
+    if (!match_conv_head(an, mm, h)) return false;
+    const ggml_tensor * ra = h.ra, * rw = h.rw, * im = h.im, * w = h.w;
     const int s0 = im->op_params[0], p0 = im->op_params[2], d0 = im->op_params[4];
     if (p0 != 0 || d0 != 1 || im->ne[2] != 1 || im->ne[3] != 1) return false;
     const ggml_tensor * cat = im->src[1];
@@ -1749,8 +1777,7 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
         members.push_back(pos_of(an, cat)); members.push_back(pos_of(an, tv)); members.push_back(pos_of(an, tc));
     }
     if (xin->type != GGML_TYPE_F32 || xin->ne[1] != Cin || xin->ne[2] != 1 || xin->ne[3] != 1) return false;
-    int pre_elu = 0;
-    if (is_elu(xin) && uses_of(an, xin) == 1 && pos_of(an, xin) >= 0) { pre_elu = 1; members.push_back(pos_of(an, xin)); xin = xin->src[0]; }
+    const int pre_elu = peel_elu(an, xin, 1, members);
     if (!xin->data) return false;
     // epilogue
     const ggml_tensor * out = sole_consumer(an, mm);
@@ -1760,9 +1787,8 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
     mm_epilogue epi;
     memset(&epi, 0, sizeof(epi));
     const ggml_tensor * nx = sole_consumer(an, out);
-    if (nx && nx->op == GGML_OP_ADD && !nx->view_src && nx->src[0] == out && nx->src[1]->op == GGML_OP_NONE && nx->src[1]->type == GGML_TYPE_F32 && nx->src[1]->ne[0] == 1 &&
-        nx->src[1]->ne[1] == Cout && ggml_nelements(nx->src[1]) == Cout && ggml_is_contiguous(nx->src[1])) {
-        epi.bias = (const float *) nx->src[1]->data;
+    if (const ggml_tensor * b = conv_bias_of(nx, out, Cout); b && b->ne[1] == Cout) {
+        epi.bias = (const float *) b->data;
         out = nx; members.push_back(pos_of(an, out));
         nx = sole_consumer(an, out);
     }
@@ -1774,16 +1800,7 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
     if (!ggml_is_contiguous(out) || !out->data || !im->data) return false;
     // cont(transpose(out)) behind a few-position conv (the encoder's last conv feeding the codec transformer): the product, which stores through its
     // destination's strides at that shape, writes the transposed copy in place of its own output - one launch less, the same values
-    const ggml_tensor * tcont = nullptr;
-    {
-        const ggml_tensor * trn = uses_of(an, out) == 1 ? sole_consumer(an, out) : nullptr;
-        const ggml_tensor * ct = trn && trn->op == GGML_OP_TRANSPOSE && uses_of(an, trn) == 1 ? sole_consumer(an, trn) : nullptr;
-        if (ct && ct->op == GGML_OP_CONT && ct->type == GGML_TYPE_F32 && ggml_is_contiguous(ct) && ct->data && OL <= 8 && ct->ne[0] == Cout && ct->ne[1] == OL &&
-            ggml_nelements(ct) == OL * Cout && pos_of(an, trn) >= 0 && pos_of(an, ct) >= 0 && !(getenv("MI355X_NO_CONV_TRANSPOSE_FOLD"))) {
-            tcont = ct;
-            members.push_back(pos_of(an, trn)); members.push_back(pos_of(an, ct));
-        }
-    }
+    const ggml_tensor * tcont = OL <= 8 ? transposed_cont_of(an, out, Cout, OL, members) : nullptr;
     for (int m : members) if (m < 0) return false;
     // The panel hand-off below is a side effect on the emitter (this group registers a slot for its output and may claim its producer's): it must only happen
     // for a group build_plan will accept, so the clash check it runs on the returned members is made here first.
@@ -1833,13 +1850,11 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
 //     as it is); the product, the view and the add / cont become one launch that stores in the final layout (k_conv_cols).
 static bool match_conv_columns(const analysis & an, int pos, step_group & grp) {
     const ggml_tensor * mm = an.g->nodes[pos];
-    if (mm->op != GGML_OP_MUL_MAT || mm->type != GGML_TYPE_F32 || uses_of(an, mm) != 1) return false;
-    const ggml_tensor * ra = mm->src[0], * rw = mm->src[1];
-    if (ra->op != GGML_OP_RESHAPE || rw->op != GGML_OP_RESHAPE || uses_of(an, ra) != 1 || uses_of(an, rw) != 1) return false;
-    const ggml_tensor * im = ra->src[0], * w = rw->src[0];
-    if (im->op != GGML_OP_IM2COL || im->src[0] != w || im->type != GGML_TYPE_F16 || w->type != GGML_TYPE_F16 || !ggml_is_contiguous(w) || !ggml_is_contiguous(im)) return false;
+    conv_head h;
+    if (!match_conv_head(an, mm, h) || mm->type != GGML_TYPE_F32 || uses_of(an, h.rw) != 1 || !ggml_is_contiguous(h.im)) return false;
+    const ggml_tensor * ra = h.ra, * rw = h.rw, * im = h.im, * w = h.w;
     const int64_t K = im->ne[0], OW = im->ne[1], B = im->ne[2], OC = w->ne[2];
-    if (B < 2 || im->ne[3] != 1 || w->ne[3] != 1 || w->ne[0] * w->ne[1] != K || uses_of(an, im) != 1 || !im->data || !w->data) return false;
+    if (B < 2 || im->ne[3] != 1 || w->ne[3] != 1 || w->ne[0] * w->ne[1] != K || !im->data || !w->data) return false;
     if (ra->ne[0] != K || ra->ne[1] != OW * B || rw->ne[0] != K || rw->ne[1] != OC || ra->data != im->data || rw->data != w->data) return false;
     const ggml_tensor * vw = sole_consumer(an, mm);
     if (!vw || vw->op != GGML_OP_VIEW || vw->data != mm->data || vw->ne[0] != OW || vw->ne[1] != OC || vw->ne[2] != B || vw->ne[3] != 1 || vw->nb[0] != 4 ||
@@ -1847,8 +1862,7 @@ static bool match_conv_columns(const analysis & an, int pos, step_group & grp) {
     const ggml_tensor * out = sole_consumer(an, vw);
     const float * bias = nullptr;
     if (!out) return false;
-    if (out->op == GGML_OP_ADD && !out->view_src && out->src[0] == vw && out->src[1]->op == GGML_OP_NONE && out->src[1]->type == GGML_TYPE_F32 && out->src[1]->ne[0] == 1 &&
-        out->src[1]->ne[1] == OC && ggml_nelements(out->src[1]) == OC && ggml_is_contiguous(out->src[1]) && out->src[1]->data) bias = (const float *) out->src[1]->data;
+    if (const ggml_tensor * b = conv_bias_of(out, vw, OC)) { if (b->ne[1] != OC || !b->data) return false; bias = (const float *) b->data; }
     else if (out->op != GGML_OP_CONT) return false;
     if (out->type != GGML_TYPE_F32 || !ggml_is_contiguous(out) || !out->data || out->ne[0] != OW || out->ne[1] != OC || out->ne[2] != B || out->ne[3] != 1) return false;
     if (K > INT32_MAX || OW * B > INT32_MAX || OC > INT32_MAX) return false;
@@ -1890,9 +1904,8 @@ static bool match_convtr_tail(const analysis & an, const ggml_tensor * y, convtr
     const ggml_tensor * cur = sole_consumer(an, cp);
     t.bias = nullptr;
     t.members = { pos_of(an, lower), pos_of(an, partial), pos_of(an, ai), pos_of(an, full), pos_of(an, cp) };
-    if (cur && cur->op == GGML_OP_ADD && !cur->view_src && cur->src[0] == cp && cur->src[1]->op == GGML_OP_NONE && cur->src[1]->type == GGML_TYPE_F32 &&
-        cur->src[1]->ne[0] == 1 && ggml_nelements(cur->src[1]) == OC && ggml_is_contiguous(cur->src[1])) {
-        t.bias = (const float *) cur->src[1]->data;
+    if (const ggml_tensor * b = conv_bias_of(cur, cp, OC)) {
+        t.bias = (const float *) b->data;
         t.members.push_back(pos_of(an, cur));
         cur = sole_consumer(an, cur);
     }
@@ -1915,8 +1928,7 @@ static bool match_convtr(const analysis & an, int pos, step_group & grp, emitter
     if (!match_convtr_tail(an, ct, t) || t.PT != PT) return false;
     std::vector<int> members = t.members;
     members.push_back(pos);
-    int pre_elu = 0;
-    if (is_elu(xin) && uses_of(an, xin) == 1 && pos_of(an, xin) >= 0) { pre_elu = 1; members.push_back(pos_of(an, xin)); xin = xin->src[0]; }
+    const int pre_elu = peel_elu(an, xin, 1, members);
     if (!xin->data) return false;
     for (int m : members) if (m < 0) return false;
     for (int m : members) if (an.skip[(size_t) m]) return false;   // (as in match_conv: no slot is registered for a group build_plan would drop)
@@ -1980,9 +1992,8 @@ static bool match_convtr_columns(const analysis & an, int pos, step_group & grp,
     convtr_tail t;
     if (!match_convtr_tail(an, y, t, lower) || t.PT != PT) return false;
     for (int m : t.members) members.push_back(m);
-    int pre_elu = 0;
     const ggml_tensor * xin = x;
-    if (is_elu(xin) && uses_of(an, xin) == (int) B && pos_of(an, xin) >= 0) { pre_elu = 1; members.push_back(pos_of(an, xin)); xin = xin->src[0]; }
+    const int pre_elu = peel_elu(an, xin, (int) B, members);
     if (!xin->data || xin->type != GGML_TYPE_F32 || xin->ne[2] != B) return false;
     if (t.out->type != GGML_TYPE_F32 || t.out->ne[0] != (int64_t) L * s0 || t.out->ne[1] != OC || t.out->ne[2] != B) return false;
     for (int m : members) if (m < 0 || an.skip[(size_t) m]) return false;
@@ -2037,15 +2048,7 @@ static bool match_dw_convtr(const analysis & an, int pos, step_group & grp) {
     // cont(transpose(out)) behind it (the decoder's upsampler feeding the codec transformer): written directly, as above
     int64_t out_cs = K - PT, out_ks = 1;
     const ggml_tensor * emit = t.out;
-    {
-        const ggml_tensor * trn = uses_of(an, t.out) == 1 ? sole_consumer(an, t.out) : nullptr;
-        const ggml_tensor * ct = trn && trn->op == GGML_OP_TRANSPOSE && uses_of(an, trn) == 1 ? sole_consumer(an, trn) : nullptr;
-        if (ct && ct->op == GGML_OP_CONT && ct->type == GGML_TYPE_F32 && ggml_is_contiguous(ct) && ct->data && ct->ne[0] == C && ct->ne[1] == K - PT && ggml_nelements(ct) == C * (K - PT) &&
-            pos_of(an, trn) >= 0 && pos_of(an, ct) >= 0 && !(getenv("MI355X_NO_CONV_TRANSPOSE_FOLD"))) {
-            out = (float *) ct->data; out_cs = 1; out_ks = C; emit = ct;
-            members.push_back(pos_of(an, trn)); members.push_back(pos_of(an, ct));
-        }
-    }
+    if (const ggml_tensor * ct = transposed_cont_of(an, t.out, C, K - PT, members)) { out = (float *) ct->data; out_cs = 1; out_ks = C; emit = ct; }
     grp.steps.clear();
     grp.steps.push_back([=](hipStream_t s) { k_dw_convtr_frame(s, out, pv, bias, xp, x_cs, wp, w_cs, K, PT, Cn, out_cs, out_ks); });
     grp.members = members;
@@ -2065,80 +2068,103 @@ static const ggml_tensor * find_consumer(const analysis & an, const ggml_tensor 
     return nullptr;
 }
 
-static bool match_vq_level(const analysis & an, int pos, step_group & grp, emitter & em) {
-    const ggml_tensor * am = an.g->nodes[pos];
-    if (am->op != GGML_OP_ARGMAX || ggml_nelements(am) != 1) return false;
-    auto one_use = [&](const ggml_tensor * t, enum ggml_op op) { return t && t->op == op && !t->view_src && uses_of(an, t) == 1; };
-    const ggml_tensor * dv = am->src[0];
-    if (!one_use(dv, GGML_OP_DIV)) return false;
-    const ggml_tensor * num = dv->src[0], * ad = dv->src[1];
-    if (!one_use(ad, GGML_OP_ADD)) return false;
-    const ggml_tensor * rs = ad->src[0], * addc = ad->src[1];
-    if (rs->op != GGML_OP_RESHAPE || uses_of(an, rs) != 1) return false;
-    const ggml_tensor * sr = rs->src[0];
-    if (!one_use(sr, GGML_OP_SUM_ROWS)) return false;
-    const ggml_tensor * sq = sr->src[0];
-    if (!one_use(sq, GGML_OP_MUL) || sq->src[0] != sq->src[1]) return false;
+// The chain both forms of a level share, walked up from the argmax at pos:
+//     argmax(div(num, add(reshape(sum_rows(mul(d, d))), addc))), d = sub(repeat(emb), reshape(repeat(reshape(cont(L(resid)))))), L the form's layout node
+// with the checks on the codebook, num (one value per code and column) and addc, and the F32 cast that consumes the codes. A level is emitted at that
+// cast: everything the kernel reads precedes the argmax, and the next residual is only consumed after its own (later) position; tensors never share
+// storage (ggml_backend_alloc_ctx_tensors). members: the chain and the cast.
+struct vq_chain {
+    const ggml_tensor * am, * dv, * rs, * sr, * rb, * ra2, * ra, * ra0, * ac, * xp, * emb, * num, * addc, * resid, * cs;
+    int64_t D, NC;
+    std::vector<int> members;
+    bool one_use(const analysis & an, const ggml_tensor * t, enum ggml_op op) const { return t && t->op == op && !t->view_src && uses_of(an, t) == 1; }
+    bool layout_use(const analysis & an, const ggml_tensor * t, enum ggml_op op) const { return t && t->op == op && uses_of(an, t) == 1; }
+    // kernel arguments of either form: the codebook, the two constants, the codes as F32 and I32, the next residual (null at the last level)
+    template <class A> void fill(A & a, float * resid_out) const {
+        a.emb = (const char *) emb->data; a.emb_row_bytes = (int64_t) emb->nb[1]; a.D = (int) D; a.NC = (int) NC;
+        a.add_c = (const float *) addc->data; a.num = (const float *) num->data;
+        a.resid_out = resid_out; a.idx_f = (float *) cs->data; a.idx_i = (int32_t *) am->data;
+    }
+};
+static bool walk_vq_chain(const analysis & an, int pos, enum ggml_op layout, vq_chain & c) {
+    c.am = an.g->nodes[pos];
+    if (c.am->op != GGML_OP_ARGMAX) return false;
+    c.dv = c.am->src[0];
+    if (!c.one_use(an, c.dv, GGML_OP_DIV)) return false;
+    c.num = c.dv->src[0];
+    const ggml_tensor * ad = c.dv->src[1];
+    if (!c.one_use(an, ad, GGML_OP_ADD)) return false;
+    c.rs = ad->src[0]; c.addc = ad->src[1];
+    if (!c.layout_use(an, c.rs, GGML_OP_RESHAPE)) return false;
+    c.sr = c.rs->src[0];
+    if (!c.one_use(an, c.sr, GGML_OP_SUM_ROWS)) return false;
+    const ggml_tensor * sq = c.sr->src[0];
+    if (!c.one_use(an, sq, GGML_OP_MUL) || sq->src[0] != sq->src[1]) return false;
     const ggml_tensor * df = sq->src[0];
-    if (!one_use(df, GGML_OP_SUB)) return false;
-    const ggml_tensor * rb = df->src[0], * ra2 = df->src[1];
-    if (!one_use(rb, GGML_OP_REPEAT) || ra2->op != GGML_OP_RESHAPE || uses_of(an, ra2) != 1) return false;
-    const ggml_tensor * emb = rb->src[0], * ra = ra2->src[0];
-    if (!one_use(ra, GGML_OP_REPEAT)) return false;
-    const ggml_tensor * ra0 = ra->src[0];
-    if (ra0->op != GGML_OP_RESHAPE || uses_of(an, ra0) != 1) return false;
-    const ggml_tensor * ac = ra0->src[0];
-    if (!one_use(ac, GGML_OP_CONT)) return false;
-    const ggml_tensor * xp = ac->src[0];
-    if (xp->op != GGML_OP_PERMUTE || uses_of(an, xp) != 1) return false;
-    const ggml_tensor * resid = xp->src[0];
-    const int64_t D = emb->ne[0], NC = emb->ne[1];
-    if (emb->op != GGML_OP_NONE || emb->type != GGML_TYPE_F32 || !dense_rows(emb) || D != 256 || NC > 4096) return false;
+    if (!c.one_use(an, df, GGML_OP_SUB)) return false;
+    c.rb = df->src[0]; c.ra2 = df->src[1];
+    if (!c.one_use(an, c.rb, GGML_OP_REPEAT) || !c.layout_use(an, c.ra2, GGML_OP_RESHAPE)) return false;
+    c.emb = c.rb->src[0]; c.ra = c.ra2->src[0];
+    if (!c.one_use(an, c.ra, GGML_OP_REPEAT)) return false;
+    c.ra0 = c.ra->src[0];
+    if (!c.layout_use(an, c.ra0, GGML_OP_RESHAPE)) return false;
+    c.ac = c.ra0->src[0];
+    if (!c.one_use(an, c.ac, GGML_OP_CONT)) return false;
+    c.xp = c.ac->src[0];
+    if (!c.layout_use(an, c.xp, layout)) return false;
+    c.resid = c.xp->src[0];
+    c.D = c.emb->ne[0]; c.NC = c.emb->ne[1];
+    if (c.emb->op != GGML_OP_NONE || c.emb->type != GGML_TYPE_F32 || !dense_rows(c.emb) || c.D != 256 || c.NC > 4096) return false;
+    if (c.num->op != GGML_OP_NONE || c.num->type != GGML_TYPE_F32 || ggml_nelements(c.num) != c.NC * ggml_nelements(c.am) || !ggml_is_contiguous(c.num)) return false;
+    if (c.addc->op != GGML_OP_NONE || c.addc->type != GGML_TYPE_F32 || ggml_nelements(c.addc) != 1) return false;
+    // consumers of the codes: the F32 cast (always) and, in each form's own shape, the centroid gather feeding the next residual (all but the last level)
+    c.cs = find_consumer(an, c.am, GGML_OP_CPY);
+    if (!c.cs || c.cs->type != GGML_TYPE_F32 || c.cs->src[0] != c.am || c.cs->view_src) return false;
+    c.members = { pos };
+    for (const ggml_tensor * t : { c.dv, ad, c.rs, c.sr, sq, df, c.rb, c.ra2, c.ra, c.ra0, c.ac, c.xp, c.cs }) c.members.push_back(pos_of(an, t));
+    for (int m : c.members) if (m < 0) return false;
+    return c.members.back() >= pos;
+}
+// the next residual behind the gathered centroids qc: sub(resid, qc), the residual's only other use; tail joins the members
+static float * vq_next_residual(const analysis & an, vq_chain & c, const ggml_tensor * qc, std::initializer_list<const ggml_tensor *> tail) {
+    const ggml_tensor * sb = sole_consumer(an, qc);
+    if (!sb || sb->op != GGML_OP_SUB || sb->view_src || sb->src[0] != c.resid || sb->src[1] != qc || !ggml_is_contiguous(sb) || !sb->data) return nullptr;
+    if (uses_of(an, c.resid) != 2 || pos_of(an, sb) < 0) return nullptr;
+    for (const ggml_tensor * t : tail) { if (pos_of(an, t) < 0) return nullptr; c.members.push_back(pos_of(an, t)); }
+    c.members.push_back(pos_of(an, sb));
+    return (float *) sb->data;
+}
+
+static bool match_vq_level(const analysis & an, int pos, step_group & grp, emitter & em) {
+    vq_chain c;
+    if (ggml_nelements(an.g->nodes[pos]) != 1 || !walk_vq_chain(an, pos, GGML_OP_PERMUTE, c)) return false;
+    const ggml_tensor * am = c.am, * resid = c.resid;
+    const int64_t D = c.D, NC = c.NC;
     if (resid->type != GGML_TYPE_F32 || resid->ne[0] != 1 || resid->ne[1] != D || ggml_nelements(resid) != D || !resid->data) return false;
-    if (ggml_nelements(rb) != D * NC || ggml_nelements(ra) != D * NC || ggml_nelements(dv) != NC) return false;
-    if (num->op != GGML_OP_NONE || num->type != GGML_TYPE_F32 || ggml_nelements(num) != NC || !ggml_is_contiguous(num)) return false;
-    if (addc->op != GGML_OP_NONE || addc->type != GGML_TYPE_F32 || ggml_nelements(addc) != 1) return false;
-    std::vector<int> members = { pos, pos_of(an, dv), pos_of(an, ad), pos_of(an, rs), pos_of(an, sr), pos_of(an, sq), pos_of(an, df), pos_of(an, rb),
-                                 pos_of(an, ra2), pos_of(an, ra), pos_of(an, ra0), pos_of(an, ac), pos_of(an, xp) };
-    // consumers of the code: the F32 cast (always) and the centroid gather feeding the next residual (all but the last level)
-    const ggml_tensor * cs = find_consumer(an, am, GGML_OP_CPY);
-    if (!cs || cs->type != GGML_TYPE_F32 || cs->src[0] != am || cs->view_src) return false;
-    members.push_back(pos_of(an, cs));
-    int last = pos_of(an, cs);
+    if (ggml_nelements(c.rb) != D * NC || ggml_nelements(c.ra) != D * NC || ggml_nelements(c.dv) != NC) return false;
     float * resid_out = nullptr;
-    const ggml_tensor * ci = find_consumer(an, am, GGML_OP_CONT);
+    const ggml_tensor * ci = find_consumer(an, am, GGML_OP_CONT);   // cont -> get_rows -> permute -> cont -> sub
     if (ci) {
         if (uses_of(an, am) != 2 || uses_of(an, ci) != 1) return false;
         const ggml_tensor * gr = sole_consumer(an, ci);
-        if (!one_use(gr, GGML_OP_GET_ROWS) || gr->src[0] != emb || gr->src[1] != ci) return false;
+        if (!c.one_use(an, gr, GGML_OP_GET_ROWS) || gr->src[0] != c.emb || gr->src[1] != ci) return false;
         const ggml_tensor * pm = sole_consumer(an, gr);
-        if (!pm || pm->op != GGML_OP_PERMUTE || uses_of(an, pm) != 1) return false;
+        if (!c.layout_use(an, pm, GGML_OP_PERMUTE)) return false;
         const ggml_tensor * qc = sole_consumer(an, pm);
-        if (!one_use(qc, GGML_OP_CONT)) return false;
-        const ggml_tensor * sb = sole_consumer(an, qc);
-        if (!sb || sb->op != GGML_OP_SUB || sb->view_src || sb->src[0] != resid || sb->src[1] != qc || !ggml_is_contiguous(sb) || !sb->data) return false;
-        if (uses_of(an, resid) != 2) return false;
-        resid_out = (float *) sb->data;
-        for (const ggml_tensor * t : { ci, gr, pm, qc, sb }) members.push_back(pos_of(an, t));
-        if (pos_of(an, sb) > last) last = pos_of(an, sb);
+        if (!c.one_use(an, qc, GGML_OP_CONT)) return false;
+        resid_out = vq_next_residual(an, c, qc, { ci, gr, pm, qc });
+        if (!resid_out) return false;
     } else if (uses_of(an, am) != 1) return false;
-    for (int m : members) if (m < 0) return false;
-    // Emitted where the F32 code is produced: everything the kernel reads precedes the argmax, and the next residual is
-    // only consumed after its own (later) position; tensors never share storage (ggml_backend_alloc_ctx_tensors).
-    last = pos_of(an, cs);
-    if (last < pos) return false;
     char * ws = (char *) em.ws(VQ_LEVEL_WS_BYTES);
     HIP_CHECK(hipMemsetAsync(ws, 0, VQ_LEVEL_WS_BYTES, em.c->stream));   // stream-ordered behind the block's previous user (plans are built outside capture)
     vq_level_args a;
-    a.emb = (const char *) emb->data; a.emb_row_bytes = (int64_t) emb->nb[1]; a.D = (int) D; a.NC = (int) NC;
+    c.fill(a, resid_out);
     a.resid = (const char *) resid->data; a.resid_stride = (int64_t) resid->nb[1];
-    a.add_c = (const float *) addc->data; a.num = (const float *) num->data;
-    a.resid_out = resid_out; a.idx_f = (float *) cs->data; a.idx_i = (int32_t *) am->data;
     a.cand_val = (float *) ws; a.cand_idx = (int32_t *) (ws + 1024); a.counter = (unsigned *) (ws + 2048);
     grp.steps.clear();
     grp.steps.push_back([=](hipStream_t s) { k_vq_level(s, a); });
-    grp.members = members;
-    grp.emit_pos = last;
+    grp.members = c.members;
+    grp.emit_pos = pos_of(an, c.cs);
     grp.vq = a; grp.has_vq = true;
     return true;
 }
@@ -2149,88 +2175,49 @@ static bool match_vq_level(const analysis & an, int pos, step_group & grp, emitt
 static bool match_vq_level_columns(const analysis & an, int pos, step_group & grp, emitter & em) {
     const ggml_tensor * am = an.g->nodes[pos];
     const int64_t B = am->ne[0];
-    if (am->op != GGML_OP_ARGMAX || B < 2 || B > VQ_COLS_MAX_B || ggml_nelements(am) != B || !am->data) return false;
-    auto one_use = [&](const ggml_tensor * t, enum ggml_op op) { return t && t->op == op && !t->view_src && uses_of(an, t) == 1; };
-    auto reshape_use = [&](const ggml_tensor * t) { return t && t->op == GGML_OP_RESHAPE && uses_of(an, t) == 1; };
+    vq_chain c;
+    if (B < 2 || B > VQ_COLS_MAX_B || ggml_nelements(am) != B || !am->data || !walk_vq_chain(an, pos, GGML_OP_RESHAPE, c)) return false;
     auto shape = [](const ggml_tensor * t, int64_t n0, int64_t n1, int64_t n2) { return t->ne[0] == n0 && t->ne[1] == n1 && t->ne[2] == n2 && t->ne[3] == 1; };
-    const ggml_tensor * dv = am->src[0];
-    if (!one_use(dv, GGML_OP_DIV)) return false;
-    const ggml_tensor * num = dv->src[0], * ad = dv->src[1];
-    if (!one_use(ad, GGML_OP_ADD)) return false;
-    const ggml_tensor * rs = ad->src[0], * addc = ad->src[1];
-    if (!reshape_use(rs)) return false;
-    const ggml_tensor * sr = rs->src[0];
-    if (!one_use(sr, GGML_OP_SUM_ROWS)) return false;
-    const ggml_tensor * sq = sr->src[0];
-    if (!one_use(sq, GGML_OP_MUL) || sq->src[0] != sq->src[1]) return false;
-    const ggml_tensor * df = sq->src[0];
-    if (!one_use(df, GGML_OP_SUB)) return false;
-    const ggml_tensor * rb = df->src[0], * ra2 = df->src[1];
-    if (!one_use(rb, GGML_OP_REPEAT) || !reshape_use(ra2)) return false;
-    const ggml_tensor * emb = rb->src[0], * ra = ra2->src[0];
-    if (!one_use(ra, GGML_OP_REPEAT)) return false;
-    const ggml_tensor * ra0 = ra->src[0];
-    if (!reshape_use(ra0)) return false;
-    const ggml_tensor * ac = ra0->src[0];
-    if (!one_use(ac, GGML_OP_CONT)) return false;
-    const ggml_tensor * xp = ac->src[0];
-    if (!reshape_use(xp)) return false;
-    const ggml_tensor * resid = xp->src[0];
-    const int64_t D = emb->ne[0], NC = emb->ne[1];
-    if (emb->op != GGML_OP_NONE || emb->type != GGML_TYPE_F32 || !dense_rows(emb) || D != 256 || NC < 1 || NC > 4096 || emb->ne[2] != 1 || emb->ne[3] != 1 || !emb->data) return false;
+    const ggml_tensor * emb = c.emb, * resid = c.resid, * cs = c.cs;
+    const int64_t D = c.D, NC = c.NC;
+    if (NC < 1 || emb->ne[2] != 1 || emb->ne[3] != 1 || !emb->data || !c.num->data || !c.addc->data) return false;
     if (resid->type != GGML_TYPE_F32 || !shape(resid, 1, D, B) || !ggml_is_contiguous(resid) || !resid->data || ((uintptr_t) resid->data & 15)) return false;
     // row b * NC + c of the difference is centroid c against residual b
-    if (!shape(xp, D, B, 1) || !shape(ac, D, B, 1) || !shape(ra0, D, 1, B) || !shape(ra, D, NC, B) || !shape(ra2, D, NC * B, 1) || !shape(rb, D, NC * B, 1) ||
-        !shape(sr, 1, NC * B, 1) || !shape(rs, NC, B, 1) || !shape(dv, NC, B, 1)) return false;
-    if (num->op != GGML_OP_NONE || num->type != GGML_TYPE_F32 || ggml_nelements(num) != NC * B || !ggml_is_contiguous(num) || !num->data) return false;
-    if (addc->op != GGML_OP_NONE || addc->type != GGML_TYPE_F32 || ggml_nelements(addc) != 1 || !addc->data) return false;
-    std::vector<int> members = { pos, pos_of(an, dv), pos_of(an, ad), pos_of(an, rs), pos_of(an, sr), pos_of(an, sq), pos_of(an, df), pos_of(an, rb),
-                                 pos_of(an, ra2), pos_of(an, ra), pos_of(an, ra0), pos_of(an, ac), pos_of(an, xp) };
-    // consumers of the codes: the F32 cast (always) and the centroid gather feeding the next residuals (all but the last level)
-    const ggml_tensor * cs = find_consumer(an, am, GGML_OP_CPY);
-    if (!cs || cs->type != GGML_TYPE_F32 || cs->src[0] != am || cs->view_src || !ggml_is_contiguous(cs) || ggml_nelements(cs) != B || !cs->data) return false;
-    members.push_back(pos_of(an, cs));
+    if (!shape(c.xp, D, B, 1) || !shape(c.ac, D, B, 1) || !shape(c.ra0, D, 1, B) || !shape(c.ra, D, NC, B) || !shape(c.ra2, D, NC * B, 1) || !shape(c.rb, D, NC * B, 1) ||
+        !shape(c.sr, 1, NC * B, 1) || !shape(c.rs, NC, B, 1) || !shape(c.dv, NC, B, 1)) return false;
+    if (!ggml_is_contiguous(cs) || ggml_nelements(cs) != B || !cs->data) return false;
     float * resid_out = nullptr;
-    const ggml_tensor * i2 = find_consumer(an, am, GGML_OP_RESHAPE);
+    const ggml_tensor * i2 = find_consumer(an, am, GGML_OP_RESHAPE);   // reshape -> cont -> reshape -> get_rows -> reshape -> permute -> cont -> sub
     if (i2) {
         if (uses_of(an, am) != 2 || uses_of(an, i2) != 1) return false;
         const ggml_tensor * ci = sole_consumer(an, i2);
-        if (!one_use(ci, GGML_OP_CONT)) return false;
+        if (!c.one_use(an, ci, GGML_OP_CONT)) return false;
         const ggml_tensor * r1 = sole_consumer(an, ci);
-        if (!reshape_use(r1) || r1->ne[0] != B || ggml_nelements(r1) != B) return false;
+        if (!c.layout_use(an, r1, GGML_OP_RESHAPE) || r1->ne[0] != B || ggml_nelements(r1) != B) return false;
         const ggml_tensor * gr = sole_consumer(an, r1);
-        if (!one_use(gr, GGML_OP_GET_ROWS) || gr->src[0] != emb || gr->src[1] != r1) return false;
+        if (!c.one_use(an, gr, GGML_OP_GET_ROWS) || gr->src[0] != emb || gr->src[1] != r1) return false;
         const ggml_tensor * r3 = sole_consumer(an, gr);
-        if (!reshape_use(r3)) return false;
+        if (!c.layout_use(an, r3, GGML_OP_RESHAPE)) return false;
         const ggml_tensor * pm = sole_consumer(an, r3);
-        if (!pm || pm->op != GGML_OP_PERMUTE || uses_of(an, pm) != 1) return false;
+        if (!c.layout_use(an, pm, GGML_OP_PERMUTE)) return false;
         const ggml_tensor * qc = sole_consumer(an, pm);
-        if (!one_use(qc, GGML_OP_CONT) || !shape(qc, 1, D, B)) return false;
-        const ggml_tensor * sb = sole_consumer(an, qc);
-        if (!sb || sb->op != GGML_OP_SUB || sb->view_src || sb->src[0] != resid || sb->src[1] != qc || !ggml_is_contiguous(sb) || !sb->data || !shape(sb, 1, D, B) ||
-            ((uintptr_t) sb->data & 15)) return false;
-        if (uses_of(an, resid) != 2) return false;
-        resid_out = (float *) sb->data;
-        for (const ggml_tensor * t : { i2, ci, r1, gr, r3, pm, qc, sb }) members.push_back(pos_of(an, t));
+        if (!c.one_use(an, qc, GGML_OP_CONT) || !shape(qc, 1, D, B)) return false;
+        resid_out = vq_next_residual(an, c, qc, { i2, ci, r1, gr, r3, pm, qc });
+        if (!resid_out || !shape(sole_consumer(an, qc), 1, D, B) || ((uintptr_t) resid_out & 15)) return false;
     } else if (uses_of(an, am) != 1) return false;
-    for (int m : members) if (m < 0) return false;
-    // emitted where the F32 codes are produced, as the single-column level is (match_vq_level)
-    const int last = pos_of(an, cs);
-    if (last < pos) return false;
     const size_t ws_bytes = k_vq_level_cols_ws_size((int) NC, (int) B);
     char * ws = (char *) em.ws(ws_bytes);
     HIP_CHECK(hipMemsetAsync(ws, 0, ws_bytes, em.c->stream));   // stream-ordered behind the block's previous user (plans are built outside capture)
     const size_t n_cand = (ws_bytes - 256) / 8;
     vq_level_cols_args a;
-    a.emb = (const char *) emb->data; a.emb_row_bytes = (int64_t) emb->nb[1]; a.D = (int) D; a.NC = (int) NC; a.B = (int) B;
+    c.fill(a, resid_out);
+    a.B = (int) B;
     a.resid = (const char *) resid->data; a.resid_col_bytes = (int64_t) resid->nb[2];
-    a.add_c = (const float *) addc->data; a.num = (const float *) num->data;
-    a.resid_out = resid_out; a.idx_f = (float *) cs->data; a.idx_i = (int32_t *) am->data;
     a.counter = (unsigned *) ws; a.cand_val = (float *) (ws + 256); a.cand_idx = (int32_t *) (ws + 256 + n_cand * 4);
     grp.steps.clear();
     grp.steps.push_back([=](hipStream_t s) { k_vq_level_cols(s, a); });
-    grp.members = members;
-    grp.emit_pos = last;
+    grp.members = c.members;
+    grp.emit_pos = pos_of(an, cs);
     return true;
 }
 
@@ -2268,33 +2255,6 @@ static bool collect_scalar_leaves(const analysis & an, const ggml_tensor * t, bo
     }
     return false;
 }
-static bool match_scalar_gather(const analysis & an, int pos, step_group & grp) {
-    const ggml_tensor * top = an.g->nodes[pos];
-    const ggml_tensor * tree = top;
-    std::vector<int> members;
-    if (top->op == GGML_OP_CPY && top->view_src == NULL && top->type == GGML_TYPE_I32 && top->src[0]->type == GGML_TYPE_F32 && ggml_is_contiguous(top)) {
-        members.push_back(pos);
-        tree = top->src[0];
-        if (uses_of(an, tree) != 1) return false;
-    } else if (top->op != GGML_OP_CONCAT || !ggml_is_contiguous(top)) return false;
-    if (!vector_like(top) || !top->data) return false;
-    std::vector<const ggml_tensor *> leaves;
-    if (!collect_scalar_leaves(an, tree, tree == top, leaves, members)) return false;
-    if ((int64_t) leaves.size() != ggml_nelements(top) || leaves.size() < 3 || leaves.size() > GATHER_MAX) return false;
-    for (int m : members) if (m < 0) return false;
-    gather_args a;
-    memset(&a, 0, sizeof(a));
-    a.n = (int) leaves.size();
-    for (int i = 0; i < a.n; i++) a.src[i] = (const float *) leaves[(size_t) i]->data;
-    a.dst = top->data;
-    a.dst_type = top->type;
-    a.B = 1;
-    grp.steps.clear();
-    grp.steps.push_back([=](hipStream_t s) { k_gather_scalars(s, a); });
-    grp.members = members;
-    grp.emit_pos = pos;
-    return true;
-}
 // G'. the same tree at B > 1 columns (encoder slots): concats along dim 1 of [1, k, B] tensors whose leaves are reshapes [1, 1, B] of B-element F32
 //     tensors (a level's codes), optionally cast to I32 at the top - dst[b * n + i] = leaf i's element b, one launch.
 static bool collect_column_leaves(const analysis & an, const ggml_tensor * t, bool top, int64_t B, std::vector<const ggml_tensor *> & leaves, std::vector<int> & members) {
@@ -2313,21 +2273,27 @@ static bool collect_column_leaves(const analysis & an, const ggml_tensor * t, bo
     leaves.push_back(base);
     return true;
 }
-static bool match_column_gather(const analysis & an, int pos, step_group & grp, int & n_cols) {
+// either tree, matched at its top: one k_gather_scalars launch. -> the number of columns (0 for the single-column tree), -1 for no match. The two forms part
+// on the top's shape alone - [1, n, B] with n and B >= 2 is not vector-like - and differ in their leaf collectors; columns_ok = false declines the B-column one
+static int match_code_gather(const analysis & an, int pos, bool columns_ok, step_group & grp) {
     const ggml_tensor * top = an.g->nodes[pos];
     const ggml_tensor * tree = top;
     std::vector<int> members;
     if (top->op == GGML_OP_CPY && top->view_src == NULL && top->type == GGML_TYPE_I32 && top->src[0]->type == GGML_TYPE_F32) {
         members.push_back(pos);
         tree = top->src[0];
-        if (uses_of(an, tree) != 1) return false;
-    } else if (top->op != GGML_OP_CONCAT) return false;
-    const int64_t n = top->ne[1], B = top->ne[2];
-    if (!ggml_is_contiguous(top) || !top->data || top->ne[0] != 1 || top->ne[3] != 1 || B < 2 || n < 2 || n > GATHER_MAX || !ggml_are_same_shape(top, tree)) return false;
+        if (uses_of(an, tree) != 1) return -1;
+    } else if (top->op != GGML_OP_CONCAT) return -1;
+    if (!ggml_is_contiguous(top) || !top->data) return -1;
+    const bool cols = !vector_like(top);
+    const int64_t n = cols ? top->ne[1] : ggml_nelements(top), B = cols ? top->ne[2] : 1;
     std::vector<const ggml_tensor *> leaves;
-    if (!collect_column_leaves(an, tree, tree == top, B, leaves, members)) return false;
-    if ((int64_t) leaves.size() != n) return false;
-    for (int m : members) if (m < 0) return false;
+    if (cols) {
+        if (!columns_ok || top->ne[0] != 1 || top->ne[3] != 1 || B < 2 || n < 2 || !ggml_are_same_shape(top, tree)) return -1;
+        if (!collect_column_leaves(an, tree, tree == top, B, leaves, members)) return -1;
+    } else if (n < 3 || !collect_scalar_leaves(an, tree, tree == top, leaves, members)) return -1;
+    if ((int64_t) leaves.size() != n || n > GATHER_MAX) return -1;
+    for (int m : members) if (m < 0) return -1;
     gather_args a;
     memset(&a, 0, sizeof(a));
     a.n = (int) n; a.B = (int) B;
@@ -2338,8 +2304,7 @@ static bool match_column_gather(const analysis & an, int pos, step_group & grp, 
     grp.steps.push_back([=](hipStream_t s) { k_gather_scalars(s, a); });
     grp.members = members;
     grp.emit_pos = pos;
-    n_cols = (int) B;
-    return true;
+    return cols ? (int) B : 0;
 }
 
 // H. the top-k sampler (moshi_sample_token with temp > 0, sampling.h:4-64), matched at its last node:
@@ -2626,7 +2591,7 @@ static void pass_heads_streams(planner & pl) {
     }
 }
 
-// slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp slot_state_graph) - one launch for the whole run
+// slot snapshots: the K / V ring copies of a fork, a save or a load (moshi_hot.cpp state_graph) - one launch for the whole run
 static void pass_ring_copies(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         ring_copy_group grp;
@@ -2638,7 +2603,7 @@ static void pass_ring_copies(planner & pl) {
     }
 }
 
-// codec slot snapshots: the conv-state column copies of a fork, a save or a load (moshi_hot.cpp codec_state_graph) - one launch for the whole run
+// codec slot snapshots: the conv-state column copies of a fork, a save or a load (moshi_hot.cpp state_graph) - one launch for the whole run
 static void pass_state_copies(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         state_copy_group grp;
@@ -2701,9 +2666,8 @@ static void pass_scalar_gathers(planner & pl) {
     for (int i = pl.g->n_nodes - 1; i >= 0; i--) {
         if (pl.an.skip[(size_t) i] || !(pl.g->nodes[i]->op == GGML_OP_CPY || pl.g->nodes[i]->op == GGML_OP_CONCAT)) continue;
         step_group grp;
-        int n_cols = 0;
-        if (!match_scalar_gather(pl.an, i, grp) && ((pl.c->flags & 8192) || !match_column_gather(pl.an, i, grp, n_cols))) continue;
-        if (!claim_group(pl, grp)) continue;
+        const int n_cols = match_code_gather(pl.an, i, !(pl.c->flags & 8192), grp);
+        if (n_cols < 0 || !claim_group(pl, grp)) continue;
         pl.p->n_code_gather_columns += n_cols;
         for (auto & f : grp.steps) pl.at_pos[grp.emit_pos].push_back(f);
     }

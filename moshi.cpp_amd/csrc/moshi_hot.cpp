@@ -600,23 +600,30 @@ T transformer_graph_build(Builder & g, Transformer & tr, T x) {
     return x;
 }
 
-// transformer_graph_build for stream slots (moshi_hot_create_slots): x = [dim, 1, B], every column at a stream position of its own. The position
-// inputs gain the batch dimension: g_bias [C, 1, 1, B] (one mask row per slot), g_offset [B] (one RoPE phase per slot: the timestep table [D, B],
-// viewed as [D/2, 1, 1, B] halves that apply_rope's products broadcast over the heads) and g_indices [1, 1, B] (one ring slot per slot).
-T transformer_graph_build_slots(Builder & g, Transformer & tr, T x) {
-    const int64_t B = x->ne[2], C = tr.capacity, D = tr.dim / tr.heads;
-    create_bias_pattern(g.be, tr, 1);
-    tr.g_bias = g.tensor(GGML_TYPE_F32, C, 1, 1, B);
+// transformer_graph_build for B columns (decoder and encoder slots, and stream slots at Tn = 1): x = [dim, Tn, B], column b's Tn rows at its own stream
+// position. The position inputs gain the batch dimension: g_bias [C, Tn, 1, B] (column b's Tn mask rows, bias_pattern_index's T = Tn quirk included),
+// g_offset [Tn * B] (the timesteps themselves, pos_b + i: what arange(Tn) + offset gives the single stream, exact in float; the table [D, Tn * B] is
+// viewed as [D/2, Tn, 1, B] halves that apply_rope's products broadcast over the heads) and g_indices [Tn, 1, B] (column b's Tn ring rows).
+T transformer_graph_build_columns(Builder & g, Transformer & tr, T x) {
+    const int64_t Tn = x->ne[1], B = x->ne[2], C = tr.capacity, D = tr.dim / tr.heads;
+    tr.g_bias = g.tensor(GGML_TYPE_F32, C, Tn, 1, B);
     Rot rot;
     if (tr.max_period) {
-        tr.g_offset = g.tensor(GGML_TYPE_F32, B);
-        T table = ggml_timestep_embedding(g, tr.g_offset, (int) D, tr.max_period);   // (the single stream's arange(1) + offset is offset exactly)
-        rot.rotr = ggml_view_4d(g, table, D / 2, 1, 1, B, table->nb[1], table->nb[1], table->nb[1], 0);
-        rot.roti = ggml_view_4d(g, table, D / 2, 1, 1, B, table->nb[1], table->nb[1], table->nb[1], table->nb[0] * (size_t) (D / 2));
+        tr.g_offset = g.tensor(GGML_TYPE_F32, Tn * B);
+        T table = ggml_timestep_embedding(g, tr.g_offset, (int) D, tr.max_period);
+        rot.rotr = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, 0);
+        rot.roti = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, table->nb[0] * (size_t) (D / 2));
     }
-    tr.g_indices = g.tensor(GGML_TYPE_I32, 1, 1, B);
+    tr.g_indices = g.tensor(GGML_TYPE_I32, Tn, 1, B);
     for (auto & L : tr.layers) x = transformer_layer(g, tr, L, 0, tr.g_indices, x, tr.g_bias, tr.max_period ? &rot : nullptr, false);
     return x;
+}
+
+// for stream slots (moshi_hot_create_slots): x = [dim, 1, B], one mask row, one RoPE phase and one ring slot per slot. The B-column form at Tn = 1, plus
+// the bias table that transformer_graph_step_slots cuts each slot's mask row from (the codec slots write their mask rows out on the host instead).
+T transformer_graph_build_slots(Builder & g, Transformer & tr, T x) {
+    create_bias_pattern(g.be, tr, 1);
+    return transformer_graph_build_columns(g, tr, x);
 }
 
 // transformer_graph_step of stream slots: slot b's mask row (bias_pattern_index at pos[b], copied into row b of g_bias by the scratch graph - the
@@ -635,24 +642,6 @@ void transformer_graph_step_slots(Builder & scratch, Transformer & tr, const std
     ggml_backend_tensor_set(tr.g_indices, idx.data(), 0, idx.size() * 4);
 }
 
-// transformer_graph_build for decoder slots (moshi_hot_create_codec_slots): x = [dim, Tn, B], column b's Tn rows at its own stream position. The slot
-// form above with Tn rows per column: g_bias [C, Tn, 1, B] (column b's Tn mask rows, bias_pattern_index's T = Tn quirk included), g_offset [Tn * B]
-// (the timesteps themselves, pos_b + i: what arange(Tn) + offset gives the single stream, exact in float; the table [D, Tn * B] is viewed as
-// [D/2, Tn, 1, B] halves) and g_indices [Tn, 1, B] (column b's Tn ring rows).
-T transformer_graph_build_codec_slots(Builder & g, Transformer & tr, T x) {
-    const int64_t Tn = x->ne[1], B = x->ne[2], C = tr.capacity, D = tr.dim / tr.heads;
-    tr.g_bias = g.tensor(GGML_TYPE_F32, C, Tn, 1, B);
-    Rot rot;
-    if (tr.max_period) {
-        tr.g_offset = g.tensor(GGML_TYPE_F32, Tn * B);
-        T table = ggml_timestep_embedding(g, tr.g_offset, (int) D, tr.max_period);
-        rot.rotr = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, 0);
-        rot.roti = ggml_view_4d(g, table, D / 2, Tn, 1, B, table->nb[1], table->nb[1] * (size_t) Tn, table->nb[1] * (size_t) Tn, table->nb[0] * (size_t) (D / 2));
-    }
-    tr.g_indices = g.tensor(GGML_TYPE_I32, Tn, 1, B);
-    for (auto & L : tr.layers) x = transformer_layer(g, tr, L, 0, tr.g_indices, x, tr.g_bias, tr.max_period ? &rot : nullptr, false);
-    return x;
-}
 // its per-step inputs: column b's rows start at stream position pos[b] (transformer_graph_step_at per column; tr.offset is not used). The B x Tn mask
 // rows are the windows bias_pattern_index cuts from create_bias_pattern's table, written out on the host and uploaded with the other two inputs: one
 // upload for all columns instead of 2 B copy nodes in a scratch graph (the table holds 0 and -inf only: the same bytes).
@@ -1273,7 +1262,7 @@ void build_decode_graph(moshi_hot_model * m) {
     m->dec_T = (int) emb->ne[0];
     // moshi_projected_transformer_graph_build (transformer.h:1356-1365)
     T x = ggml_cont(g, ggml_transpose(g, emb));
-    x = m->kind == ModelKind::codec_slots ? transformer_graph_build_codec_slots(g, m->dec_tr, x) : transformer_graph_build(g, m->dec_tr, x);
+    x = m->kind == ModelKind::codec_slots ? transformer_graph_build_columns(g, m->dec_tr, x) : transformer_graph_build(g, m->dec_tr, x);
     x = ggml_transpose(g, x);
     // moshi_seanet_decoder (seanet.h:179-211)
     x = streaming_conv(g, m->dec_convs[0], x);
@@ -1309,7 +1298,7 @@ void build_encode_graph(moshi_hot_model * m) {
     x = streaming_conv(g, m->enc_convs[5], x);
     m->enc_T = (int) x->ne[0];
     x = ggml_cont(g, ggml_transpose(g, x));
-    x = cols ? transformer_graph_build_codec_slots(g, m->enc_tr, x) : transformer_graph_build(g, m->enc_tr, x);
+    x = cols ? transformer_graph_build_columns(g, m->enc_tr, x) : transformer_graph_build(g, m->enc_tr, x);
     x = ggml_transpose(g, x);
     x = streaming_conv(g, m->downsample, x);
     // moshi_split_rvq_encode (vq.h:97-114)
@@ -3088,10 +3077,111 @@ extern "C" int moshi_hot_slot_hold(moshi_hot_model_t * m, int b, int hold) {
     return 0;
 }
 
+// ---- snapshots (moshi_hot.h): what the LM slots' calls and the codec slots' calls share -------------------------------------------------------------
+namespace {
+// FNV-1a over what a blob's bytes depend on: a blob only loads into a model that would have laid the same conversation out the same way
+struct Fingerprint {
+    uint64_t h = 0xcbf29ce484222325ull;
+    void mix(int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; }
+};
+// the K / V part of a blob: per layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous)
+int64_t ring_bytes(const Transformer & tr, int64_t n_rows) { return 2 * (int64_t) tr.layers.size() * (int64_t) tr.dim * n_rows * 2; }
+
+// column b of a state tensor: its first `dims` dimensions at b * nb[batch_dim]. In a blob and in the staging tensor a column is padded to 16 bytes.
+struct ColumnCopy { T t; int dims, batch_dim; };
+T column_of(Builder & s, const ColumnCopy & c, int b) {
+    T t = c.t;
+    const size_t off = (size_t) b * t->nb[c.batch_dim];
+    return c.dims == 1 ? ggml_view_1d(s, t, t->ne[0], off) : c.dims == 2 ? ggml_view_2d(s, t, t->ne[0], t->ne[1], t->nb[1], off)
+                                                                         : ggml_view_3d(s, t, t->ne[0], t->ne[1], t->ne[2], t->nb[1], t->nb[2], off);
+}
+int64_t column_floats(const ColumnCopy & c) { return c.dims == 1 ? c.t->ne[0] : c.dims == 2 ? c.t->ne[0] * c.t->ne[1] : c.t->ne[0] * c.t->ne[1] * c.t->ne[2]; }
+int64_t staged_floats(const ColumnCopy & c) { return (column_floats(c) + 3) / 4 * 4; }
+int64_t staged_bytes(const std::vector<ColumnCopy> & copies) {
+    int64_t n = 0;
+    for (const ColumnCopy & c : copies) n += staged_floats(c) * 4;
+    return n;
+}
+
+// The device half of every snapshot call as ONE scratch graph: per layer of tr a cpy of K and a cpy of V between [D, n, H] views - ring rows [0, n) of
+// every head of column src (src < 0: of a contiguous BF16 staging tensor [D, n, H, 2 L], uploaded from rings_in first) into the same rows of column dst
+// (dst < 0: into the staging tensor, read back to rings_out) - then one cpy per entry of `copies`, in order, between column src and column dst of that
+// state tensor; for a save or a load the other side is a 16-byte-aligned slice of ONE contiguous F32 staging tensor, uploaded from cols_in first or read
+// back to cols_out afterwards (its padding zeroed). A staged 1-D column (the LM's transformer_out row) stands alone and is the staging tensor itself.
+// The device plan turns the ring copies into one launch (hip_backend.hip match_ring_copies; [D, len, H] columns that follow them, the cross-attention K / V of a tts fork,
+// into a second run) and a run of contiguous columns into another (match_state_copies: the codec's conv states); the oracle and a plan without fusion
+// run them all as the generic copies they are.
+void state_graph(moshi_hot_model * m, const Transformer & tr, int64_t n, const std::vector<ColumnCopy> & copies, int src, int dst,
+                 const void * cols_in, const void * rings_in, void * cols_out, void * rings_out) {
+    Builder & s = *m->scratch;
+    const int64_t H = tr.heads, D = tr.dim / H;
+    const bool staged = src < 0 || dst < 0;
+    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
+    T col_stage = staged ? s.tensor(GGML_TYPE_F32, staged_bytes(copies) / 4) : nullptr;
+    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
+    int64_t j = 0;
+    if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
+        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
+        j++;
+        s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
+    }
+    int64_t off = 0;   // floats into the staging tensor
+    for (const ColumnCopy & c : copies) {
+        // What a save or a load stages: the LM's lone transformer_out row (1-D: the staging tensor as it is, no view node, as it always was) or the codec's
+        // [len, C] states (2-D slices). The 3-D cross-attention columns and the rows beside them belong to a tts fork, which stages nothing.
+        GGML_ASSERT(!staged || (c.dims == 1 ? copies.size() == 1 : c.dims == 2));
+        T part = !staged ? nullptr : c.dims == 1 ? col_stage : ggml_view_2d(s, col_stage, c.t->ne[0], c.t->ne[1], (size_t) c.t->ne[0] * 4, (size_t) off * 4);
+        off += staged_floats(c);
+        s.expand(ggml_cpy(s, src >= 0 ? column_of(s, c, src) : part, dst >= 0 ? column_of(s, c, dst) : part));
+    }
+    ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph: a repeated fork of the same pair must not pay for a hipGraph capture
+    s.alloc();
+    if (src < 0) {
+        ggml_backend_tensor_set(col_stage, cols_in, 0, ggml_nbytes(col_stage));
+        if (stage) ggml_backend_tensor_set(stage, rings_in, 0, ggml_nbytes(stage));
+    }
+    s.compute();
+    if (dst < 0) {
+        ggml_backend_tensor_get(col_stage, cols_out, 0, ggml_nbytes(col_stage));
+        if (stage) ggml_backend_tensor_get(stage, rings_out, 0, ggml_nbytes(stage));
+    }
+    ggml_backend_synchronize(m->be);   // the calls block
+    s.release_scratch();
+    ggml_backend_mi355x_set_capture(m->be, 1);
+    if (dst < 0) {   // the padding behind each column was never written on the device: zeros in the blob
+        float * out = (float *) cols_out;
+        for (const ColumnCopy & c : copies) {
+            for (int64_t i = column_floats(c); i < staged_floats(c); i++) out[i] = 0.f;
+            out += staged_floats(c);
+        }
+    }
+}
+
+// The save scaffold of both blob kinds. h: the finished header (total_bytes included); host: the bytes in front of the ring rows, zeroed here. The LM blob
+// needs that for its padding; the codec blob, whose states and padding state_graph writes in full, only pays a memset for it (under 1 MB, same bytes).
+// -> where the part behind the header goes, or nullptr with ret = what the call returns: the size when buf is NULL, -1 for a buffer that is too small
+template <class Header> uint8_t * blob_save_begin(void * buf, int64_t nbytes, int64_t host, const Header & h, int64_t & ret) {
+    ret = h.total_bytes;
+    if (!buf) return nullptr;
+    if (nbytes < h.total_bytes) { ret = -1; return nullptr; }
+    memset(buf, 0, (size_t) host);
+    memcpy(buf, &h, sizeof(h));
+    return (uint8_t *) buf + sizeof(h);
+}
+// The load scaffold: the header out of a buffer that holds one; -> the part behind it, or nullptr for another magic, version or fingerprint or a blob
+// that is not nbytes long. What each format refuses beyond that, and its size equation (which needs the checked row count), follow at the caller.
+template <class Header> const uint8_t * blob_load_begin(const void * buf, int64_t nbytes, uint32_t magic, uint32_t version, uint64_t fingerprint, Header & h) {
+    if (!buf || nbytes < (int64_t) sizeof(h)) return nullptr;
+    memcpy(&h, buf, sizeof(h));
+    if (h.magic != magic || h.version != version || h.fingerprint != fingerprint || nbytes != h.total_bytes) return nullptr;
+    return (const uint8_t *) buf + sizeof(h);
+}
+}  // namespace
+
 // ---- slot snapshots (moshi_hot.h): fork, save and load a conversation's state without recomputing it ------------------------------------------------
 namespace {
 // The blob: this header, the delay ring (ring_rows x ring_cols int32, row-major), transformer_out (dim F32), zero padding to a multiple of 16 bytes,
-// then per Temporal layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous).
+// then the Temporal ring rows (ring_bytes).
 struct SlotBlobHeader {
     uint32_t magic, version;
     uint64_t fingerprint;
@@ -3105,18 +3195,17 @@ const uint32_t SLOT_BLOB_MAGIC = 0x544C534Du, SLOT_BLOB_VERSION = 1;   // "MSLT"
 const uint32_t SLOT_BLOB_VERSION_FULL = 2;
 static_assert(sizeof(SlotBlobHeader) == 88, "the blob header has no padding");
 
-// FNV-1a over what a blob's bytes depend on: a blob only loads into a model that would have laid the same conversation out the same way
+uint32_t slot_version(const moshi_hot_model * m) { return tts_shape(m) ? SLOT_BLOB_VERSION_FULL : SLOT_BLOB_VERSION; }
 uint64_t slot_fingerprint(const moshi_hot_model * m) {
     const moshi_hot_config & c = m->cfg;
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; };
-    mix(c.dim); mix(c.num_heads); mix(c.num_layers); mix(c.context); mix(c.n_q); mix(c.dep_q); mix(c.card); mix(c.text_card);
-    for (int i = 0; i <= c.n_q; i++) mix(c.delays[i]);
-    mix(m->temporal.layers[0].kcache->type);
-    mix(sampled_model(m) ? 1 : 0);
-    if (persona_shape(m)) { mix(c.persona_columns); mix(m->proto.io_dep_q); }   // (no other shape mixes anything here: their fingerprints are what they were)
-    if (tts_shape(m)) { mix(c.cross_attention); mix(c.cross_attention ? c.cross_len : 0); mix(c.condition_sum); mix(c.demux_second_stream); mix(c.delay_steps); }   // (version 2)
-    return h;
+    Fingerprint f;
+    f.mix(c.dim); f.mix(c.num_heads); f.mix(c.num_layers); f.mix(c.context); f.mix(c.n_q); f.mix(c.dep_q); f.mix(c.card); f.mix(c.text_card);
+    for (int i = 0; i <= c.n_q; i++) f.mix(c.delays[i]);
+    f.mix(m->temporal.layers[0].kcache->type);
+    f.mix(sampled_model(m) ? 1 : 0);
+    if (persona_shape(m)) { f.mix(c.persona_columns); f.mix(m->proto.io_dep_q); }   // (no other shape mixes anything here: their fingerprints are what they were)
+    if (tts_shape(m)) { f.mix(c.cross_attention); f.mix(c.cross_attention ? c.cross_len : 0); f.mix(c.condition_sum); f.mix(c.demux_second_stream); f.mix(c.delay_steps); }   // (version 2)
+    return f.h;
 }
 int64_t slot_cond_floats(const moshi_hot_model * m) {   // a version-2 blob's conditions
     return (m->cond_sum ? (int64_t) m->cfg.dim : 0) + (m->cond_cross ? (int64_t) m->cfg.dim * m->cfg.cross_len : 0);
@@ -3125,55 +3214,19 @@ int64_t slot_host_bytes(const moshi_hot_model * m) {   // everything in front of
     const int64_t n = (int64_t) sizeof(SlotBlobHeader) + (int64_t) m->proto.rows * m->proto.cols() * 4 + (int64_t) m->cfg.dim * 4 + (tts_shape(m) ? slot_cond_floats(m) * 4 : 0);
     return (n + 15) / 16 * 16;
 }
-int64_t slot_ring_bytes(const moshi_hot_model * m, int64_t n_rows) {
-    return 2 * (int64_t) m->temporal.layers.size() * (int64_t) m->cfg.dim * n_rows * 2;   // 2 x layers x H x n x D BF16
-}
 int64_t slot_live_rows(const moshi_hot_model * m, const moshi_hot_model::Column & col) { return col.pos < m->temporal.capacity ? col.pos : m->temporal.capacity; }
 
-// The device half as ONE scratch graph: per Temporal layer a cpy of K and a cpy of V between [D, n, H] views - ring rows [0, n) of every head of column
-// src (src < 0: of a contiguous BF16 staging tensor [D, n, H, 2 L], uploaded from rings_in first) into the same rows of column dst (dst < 0: into the
-// staging tensor, read back to rings_out) - and the row copy of transformer_out (staged through an F32[dim] tensor likewise). The device plan turns the
-// ring copies into one launch (hip_backend.hip match_ring_copies); the oracle and a plan without fusion run them as the generic strided copies they are.
-// conditions (a fork of a tts-shaped slot, src and dst >= 0): also column src's conditions into column dst - every layer's k_cross and v_cross column, which
-// are [D, cross_len, H] views like the ring rows and follow them as a second run of ring copies, then the cond_sum and cond_cross columns as plain copies.
+// state_graph of an LM slot: the Temporal rings, then the transformer_out row (the one copy a save or a load stages: dim x 4 is a multiple of 16).
+// conditions (a fork of a tts-shaped slot): in front of it column src's k_cross and v_cross of every layer, which are [D, cross_len, H] views like the ring
+// rows and follow them as a second run of ring copies; behind it the cond_sum and cond_cross columns as plain copies.
 void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * tout_in, const void * rings_in, void * tout_out, void * rings_out, bool conditions = false) {
-    Builder & s = *m->scratch;
-    const Transformer & tr = m->temporal;
-    const int64_t dim = m->cfg.dim, H = tr.heads, D = dim / H;
-    const bool staged = src < 0 || dst < 0;
-    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
-    T tout_stage = staged ? s.tensor(GGML_TYPE_F32, dim) : nullptr;
-    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
-    auto tout_row = [&](int b) { return ggml_view_1d(s, m->transformer_out, dim, (size_t) b * m->transformer_out->nb[2]); };
-    int64_t j = 0;
-    if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
-        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
-        j++;
-        s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
-    }
-    if (conditions) for (const Layer & L : tr.layers) for (T st : { L.k_cross, L.v_cross }) if (st)
-        s.expand(ggml_cpy(s, ggml_view_3d(s, st, st->ne[0], st->ne[1], st->ne[2], st->nb[1], st->nb[2], (size_t) src * st->nb[3]),
-                          ggml_view_3d(s, st, st->ne[0], st->ne[1], st->ne[2], st->nb[1], st->nb[2], (size_t) dst * st->nb[3])));
-    s.expand(ggml_cpy(s, src >= 0 ? tout_row(src) : tout_stage, dst >= 0 ? tout_row(dst) : tout_stage));
-    if (conditions && m->cond_sum) s.expand(ggml_cpy(s, ggml_view_1d(s, m->cond_sum, dim, (size_t) src * m->cond_sum->nb[1]), ggml_view_1d(s, m->cond_sum, dim, (size_t) dst * m->cond_sum->nb[1])));
-    if (conditions && m->cond_cross) {
-        T cc = m->cond_cross;
-        s.expand(ggml_cpy(s, ggml_view_2d(s, cc, cc->ne[0], cc->ne[1], cc->nb[1], (size_t) src * cc->nb[2]), ggml_view_2d(s, cc, cc->ne[0], cc->ne[1], cc->nb[1], (size_t) dst * cc->nb[2])));
-    }
-    ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph: a repeated fork of the same pair must not pay for a hipGraph capture
-    s.alloc();
-    if (src < 0) {
-        ggml_backend_tensor_set(tout_stage, tout_in, 0, (size_t) dim * 4);
-        if (stage) ggml_backend_tensor_set(stage, rings_in, 0, ggml_nbytes(stage));
-    }
-    s.compute();
-    if (dst < 0) {
-        ggml_backend_tensor_get(tout_stage, tout_out, 0, (size_t) dim * 4);
-        if (stage) ggml_backend_tensor_get(stage, rings_out, 0, ggml_nbytes(stage));
-    }
-    ggml_backend_synchronize(m->be);   // the calls block
-    s.release_scratch();
-    ggml_backend_mi355x_set_capture(m->be, 1);
+    std::vector<ColumnCopy> copies;
+    if (conditions) for (const Layer & L : m->temporal.layers) for (T st : { L.k_cross, L.v_cross }) if (st) copies.push_back({ st, 3, 3 });
+    copies.push_back({ m->transformer_out, 1, 2 });
+    if (conditions && m->cond_sum) copies.push_back({ m->cond_sum, 1, 1 });
+    if (conditions && m->cond_cross) copies.push_back({ m->cond_cross, 2, 2 });
+    GGML_ASSERT(m->cfg.dim % 4 == 0);
+    state_graph(m, m->temporal, n, copies, src, dst, tout_in, rings_in, tout_out, rings_out);
 }
 
 // full: the _full calls, which take a tts-shaped model (and are the plain calls on any other); the plain calls refuse it
@@ -3191,50 +3244,45 @@ int slot_fork(moshi_hot_model_t * m, int src, int dst, bool full) {
 int64_t slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes, bool full) {
     const moshi_hot_model::Column * col = slot(m, b);
     if (!col || !col->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
-    const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m), total = host + slot_ring_bytes(m, n);
-    if (!buf) return total;
-    if (nbytes < total) return -1;
-    uint8_t * out = (uint8_t *) buf;
-    memset(out, 0, (size_t) host);
+    const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m);
     SlotBlobHeader h;
     memset(&h, 0, sizeof(h));
-    h.magic = SLOT_BLOB_MAGIC; h.version = tts_shape(m) ? SLOT_BLOB_VERSION_FULL : SLOT_BLOB_VERSION; h.fingerprint = slot_fingerprint(m);
-    h.total_bytes = total; h.frames = col->ring.frames; h.pos = col->pos; h.n_rows = n;
+    h.magic = SLOT_BLOB_MAGIC; h.version = slot_version(m); h.fingerprint = slot_fingerprint(m);
+    h.total_bytes = host + ring_bytes(m->temporal, n); h.frames = col->ring.frames; h.pos = col->pos; h.n_rows = n;
     h.ring_rows = m->proto.rows; h.ring_cols = m->proto.cols();
     h.seeded = m->sampling[(size_t) b].seeded ? 1 : 0; h.sampling = m->sampling[(size_t) b].s;
-    memcpy(out, &h, sizeof(h));
-    int32_t * ring = (int32_t *) (out + sizeof(h));
+    int64_t ret;
+    int32_t * ring = (int32_t *) blob_save_begin(buf, nbytes, host, h, ret);
+    if (!ring) return ret;
     col->ring.export_rows(ring);
-    slot_state_graph(m, b, -1, n, nullptr, nullptr, ring + col->ring.rows.size(), out + host);
+    slot_state_graph(m, b, -1, n, nullptr, nullptr, ring + col->ring.rows.size(), (uint8_t *) buf + host);
     if (tts_shape(m)) {   // the column's conditions, behind transformer_out
         float * cond = (float *) (ring + col->ring.rows.size()) + m->cfg.dim;
         if (m->cond_sum) { ggml_backend_tensor_get(m->cond_sum, cond, (size_t) b * m->cond_sum->nb[1], (size_t) m->cfg.dim * 4); cond += m->cfg.dim; }
         if (m->cond_cross) ggml_backend_tensor_get(m->cond_cross, cond, (size_t) b * m->cond_cross->nb[2], (size_t) m->cfg.dim * (size_t) m->cfg.cross_len * 4);
     }
-    return total;
+    return ret;
 }
 
 int slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes, bool full) {
     moshi_hot_model::Column * col = slot(m, b);
-    if (!col || col->open || (tts_shape(m) && !full) || !buf || nbytes < (int64_t) sizeof(SlotBlobHeader) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
-    const uint8_t * in = (const uint8_t *) buf;
+    if (!col || col->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     SlotBlobHeader h;
-    memcpy(&h, in, sizeof(h));
+    const int32_t * ring = (const int32_t *) blob_load_begin(buf, nbytes, SLOT_BLOB_MAGIC, slot_version(m), slot_fingerprint(m), h);
+    if (!ring) return -1;
     const moshi_hot_config & c = m->cfg;
     const int64_t host = slot_host_bytes(m), C = m->temporal.capacity;
-    if (h.magic != SLOT_BLOB_MAGIC || h.version != (tts_shape(m) ? SLOT_BLOB_VERSION_FULL : SLOT_BLOB_VERSION) || h.fingerprint != slot_fingerprint(m)) return -1;
     if (h.pos < 0 || h.frames < 0 || h.n_rows != (h.pos < C ? h.pos : C) || h.ring_rows != m->proto.rows || h.ring_cols != m->proto.cols()) return -1;
-    if (h.total_bytes != host + slot_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
+    if (h.total_bytes != host + ring_bytes(m->temporal, h.n_rows)) return -1;
     const moshi_hot_sampling & sp = h.sampling;
     if (sampled_model(m) && (!(sp.temp > 0.f) || !(sp.temp_text > 0.f) || sp.top_k < 1 || sp.top_k > c.top_k || sp.top_k_text < 1 || sp.top_k_text > c.top_k_text)) return -1;
-    const int32_t * ring = (const int32_t *) (in + sizeof(h));
     if (tts_shape(m) && slot_cond_floats(m)) {
         // the conversation's conditions take the column over: uploaded, and the cross-attention state recomputed, exactly as moshi_hot_set_conditions_column
         // does (on the backend that saved the blob the same arithmetic as before the save)
         const float * cond = (const float *) (ring + (size_t) h.ring_rows * (size_t) h.ring_cols) + c.dim;
         moshi_hot_set_conditions_column(m, b, m->cond_sum ? cond : nullptr, m->cond_cross ? cond + (m->cond_sum ? c.dim : 0) : nullptr);
     }
-    slot_state_graph(m, -1, b, h.n_rows, ring + (size_t) h.ring_rows * (size_t) h.ring_cols, in + host, nullptr, nullptr);
+    slot_state_graph(m, -1, b, h.n_rows, ring + (size_t) h.ring_rows * (size_t) h.ring_cols, (const uint8_t *) buf + host, nullptr, nullptr);
     col->ring.import_rows(ring, h.frames);
     col->pos = h.pos; col->open = true; col->held = false;
     m->sampling[(size_t) b] = { sp, h.seeded != 0 && sampled_model(m) };
@@ -3254,8 +3302,8 @@ extern "C" int moshi_hot_slot_load_full(moshi_hot_model_t * m, int b, const void
 
 // ---- codec slot snapshots (moshi_hot.h): fork, save and load a decoder or encoder slot's state -------------------------------------------------------
 namespace {
-// The blob: this header, column b of every carried conv state in model order (each F32 [len, C], zero-padded to a multiple of 16 bytes), then per codec
-// transformer layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous).
+// The blob: this header, column b of every carried conv state in model order (each F32 [len, C], zero-padded to a multiple of 16 bytes), then the codec
+// transformer's ring rows (ring_bytes).
 struct CodecBlobHeader {
     uint32_t magic, version, kind, reserved;   // kind: 1 a decoder slot, 2 an encoder slot
     uint64_t fingerprint;
@@ -3272,10 +3320,10 @@ int64_t codec_rows_per_frame(moshi_hot_model * m) {
     if (!m->g_enc) build_encode_graph(m);
     return m->enc_T;
 }
-// the carried conv states in model order: the tensors moshi_hot_codec_slot_open clears, [len, C, B] F32 each
-std::vector<T> codec_states(moshi_hot_model * m) {
-    std::vector<T> out;
-    auto add = [&](T t) { if (t) out.push_back(t); };
+// the carried conv states in model order: the tensors moshi_hot_codec_slot_open clears, [len, C, B] F32 each; state_graph's copies of a codec slot
+std::vector<ColumnCopy> codec_states(moshi_hot_model * m) {
+    std::vector<ColumnCopy> out;
+    auto add = [&](T t) { if (t) out.push_back({ t, 2, 2 }); };
     add(m->upsample.prev);
     for (auto & cv : m->dec_convs) add(cv.prev);
     for (auto & ct : m->dec_convtrs) add(ct.prev);
@@ -3285,114 +3333,49 @@ std::vector<T> codec_states(moshi_hot_model * m) {
     add(m->downsample.prev);
     return out;
 }
-int64_t codec_state_floats(T t) { return (t->ne[0] * t->ne[1] + 3) / 4 * 4; }   // a column, padded to 16 bytes
-int64_t codec_states_bytes(moshi_hot_model * m) {
-    int64_t n = 0;
-    for (T t : codec_states(m)) n += codec_state_floats(t) * 4;
-    return n;
-}
-int64_t codec_ring_bytes(moshi_hot_model * m, int64_t n_rows) {
-    const Transformer & tr = codec_tr(m);
-    return 2 * (int64_t) tr.layers.size() * (int64_t) tr.dim * n_rows * 2;   // 2 x layers x H x n x D BF16
-}
+int64_t codec_host_bytes(moshi_hot_model * m) { return (int64_t) sizeof(CodecBlobHeader) + staged_bytes(codec_states(m)); }   // everything in front of the ring rows
 int64_t codec_live_rows(moshi_hot_model * m, int64_t pos) {
     const int64_t C = codec_tr(m).capacity, T_ = codec_rows_per_frame(m);
     return pos >= (C + T_ - 1) / T_ ? C : pos * T_;
 }
-// FNV-1a (as slot_fingerprint) over what a blob's bytes depend on
 uint64_t codec_fingerprint(moshi_hot_model * m) {
     const Transformer & tr = codec_tr(m);
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; };
-    mix(codec_kind(m)); mix(tr.dim); mix(tr.heads); mix((int64_t) tr.layers.size()); mix(tr.capacity); mix(codec_rows_per_frame(m)); mix(tr.layers[0].kcache->type);
-    for (T t : codec_states(m)) { mix(t->ne[0]); mix(t->ne[1]); }
-    return h;
-}
-
-// The device half as ONE scratch graph, built as slot_state_graph is: per codec transformer layer a cpy of K and a cpy of V between [D, n, H] views (the
-// LM snapshot's nodes: one k_ring_copy launch), then one cpy per carried conv state between the contiguous [len, C] view of column src and that of column
-// dst - for a save or a load (dst < 0 / src < 0) the other side a 16-byte-aligned slice of ONE contiguous F32 staging tensor, uploaded from states_in
-// first or read back to states_out afterwards (its padding zeroed). The device plan turns the state copies into one launch (hip_backend.hip
-// match_state_copies); the oracle and a plan without fusion run them as the generic copies they are.
-void codec_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const void * states_in, const void * rings_in, void * states_out, void * rings_out) {
-    Builder & s = *m->scratch;
-    const Transformer & tr = codec_tr(m);
-    const int64_t H = tr.heads, D = tr.dim / H;
-    const bool staged = src < 0 || dst < 0;
-    const std::vector<T> states = codec_states(m);
-    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
-    T st_stage = staged ? s.tensor(GGML_TYPE_F32, codec_states_bytes(m) / 4) : nullptr;
-    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
-    auto column = [&](T t, int b) { return ggml_view_2d(s, t, t->ne[0], t->ne[1], t->nb[1], (size_t) b * t->nb[2]); };
-    int64_t j = 0;
-    if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
-        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
-        j++;
-        s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
-    }
-    int64_t off = 0;   // floats into the staging tensor
-    for (T t : states) {
-        T part = st_stage ? ggml_view_2d(s, st_stage, t->ne[0], t->ne[1], (size_t) t->ne[0] * 4, (size_t) off * 4) : nullptr;
-        off += codec_state_floats(t);
-        s.expand(ggml_cpy(s, src >= 0 ? column(t, src) : part, dst >= 0 ? column(t, dst) : part));
-    }
-    ggml_backend_mi355x_set_capture(m->be, 0);   // a one-off graph, as slot_state_graph
-    s.alloc();
-    if (src < 0) {
-        ggml_backend_tensor_set(st_stage, states_in, 0, ggml_nbytes(st_stage));
-        if (stage) ggml_backend_tensor_set(stage, rings_in, 0, ggml_nbytes(stage));
-    }
-    s.compute();
-    if (dst < 0) {
-        ggml_backend_tensor_get(st_stage, states_out, 0, ggml_nbytes(st_stage));
-        if (stage) ggml_backend_tensor_get(stage, rings_out, 0, ggml_nbytes(stage));
-    }
-    ggml_backend_synchronize(m->be);   // the calls block
-    s.release_scratch();
-    ggml_backend_mi355x_set_capture(m->be, 1);
-    if (dst < 0) {   // the padding behind each column was never written on the device: zeros in the blob
-        float * out = (float *) states_out;
-        for (T t : states) {
-            for (int64_t i = t->ne[0] * t->ne[1]; i < codec_state_floats(t); i++) out[i] = 0.f;
-            out += codec_state_floats(t);
-        }
-    }
+    Fingerprint f;
+    f.mix(codec_kind(m)); f.mix(tr.dim); f.mix(tr.heads); f.mix((int64_t) tr.layers.size()); f.mix(tr.capacity); f.mix(codec_rows_per_frame(m)); f.mix(tr.layers[0].kcache->type);
+    for (const ColumnCopy & c : codec_states(m)) { f.mix(c.t->ne[0]); f.mix(c.t->ne[1]); }
+    return f.h;
 }
 }  // namespace
 
 extern "C" int moshi_hot_codec_slot_fork(moshi_hot_model_t * m, int src, int dst) {
     moshi_hot_model::CodecColumn * a = codec_slot(m, src), * b = codec_slot(m, dst);
     if (!a || !b || src == dst || !a->open || b->open || a->pos < 0) return -1;
-    codec_state_graph(m, src, dst, codec_live_rows(m, a->pos), nullptr, nullptr, nullptr, nullptr);
+    state_graph(m, codec_tr(m), codec_live_rows(m, a->pos), codec_states(m), src, dst, nullptr, nullptr, nullptr, nullptr);
     *b = *a;
     return 0;
 }
 extern "C" int64_t moshi_hot_codec_slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes) {
     const moshi_hot_model::CodecColumn * col = codec_slot(m, b);
     if (!col || !col->open || col->pos < 0 || codec_tr(m).layers[0].kcache->type != GGML_TYPE_BF16) return -1;
-    const int64_t n = codec_live_rows(m, col->pos), host = (int64_t) sizeof(CodecBlobHeader) + codec_states_bytes(m), total = host + codec_ring_bytes(m, n);
-    if (!buf) return total;
-    if (nbytes < total) return -1;
-    uint8_t * out = (uint8_t *) buf;
+    const int64_t n = codec_live_rows(m, col->pos), host = codec_host_bytes(m);
     CodecBlobHeader h;
     memset(&h, 0, sizeof(h));
     h.magic = CODEC_BLOB_MAGIC; h.version = CODEC_BLOB_VERSION; h.kind = codec_kind(m); h.fingerprint = codec_fingerprint(m);
-    h.total_bytes = total; h.pos = col->pos; h.n_rows = n;
-    memcpy(out, &h, sizeof(h));
-    codec_state_graph(m, b, -1, n, nullptr, nullptr, out + sizeof(h), out + host);
-    return total;
+    h.total_bytes = host + ring_bytes(codec_tr(m), n); h.pos = col->pos; h.n_rows = n;
+    int64_t ret;
+    uint8_t * states = blob_save_begin(buf, nbytes, host, h, ret);
+    if (states) state_graph(m, codec_tr(m), n, codec_states(m), b, -1, nullptr, nullptr, states, (uint8_t *) buf + host);
+    return ret;
 }
 extern "C" int moshi_hot_codec_slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes) {
     moshi_hot_model::CodecColumn * col = codec_slot(m, b);
-    if (!col || col->open || !buf || nbytes < (int64_t) sizeof(CodecBlobHeader) || codec_tr(m).layers[0].kcache->type != GGML_TYPE_BF16) return -1;
-    const uint8_t * in = (const uint8_t *) buf;
+    if (!col || col->open || codec_tr(m).layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     CodecBlobHeader h;
-    memcpy(&h, in, sizeof(h));
-    if (h.magic != CODEC_BLOB_MAGIC || h.version != CODEC_BLOB_VERSION || h.kind != codec_kind(m) || h.reserved != 0 || h.fingerprint != codec_fingerprint(m)) return -1;
-    if (h.pos < 0 || h.n_rows != codec_live_rows(m, h.pos)) return -1;
-    const int64_t host = (int64_t) sizeof(CodecBlobHeader) + codec_states_bytes(m);
-    if (h.total_bytes != host + codec_ring_bytes(m, h.n_rows) || nbytes != h.total_bytes) return -1;
-    codec_state_graph(m, -1, b, h.n_rows, in + sizeof(h), in + host, nullptr, nullptr);
+    const uint8_t * states = blob_load_begin(buf, nbytes, CODEC_BLOB_MAGIC, CODEC_BLOB_VERSION, codec_fingerprint(m), h);
+    if (!states || h.kind != codec_kind(m) || h.reserved != 0 || h.pos < 0 || h.n_rows != codec_live_rows(m, h.pos)) return -1;
+    const int64_t host = codec_host_bytes(m);
+    if (h.total_bytes != host + ring_bytes(codec_tr(m), h.n_rows)) return -1;
+    state_graph(m, codec_tr(m), h.n_rows, codec_states(m), -1, b, states, (const uint8_t *) buf + host, nullptr, nullptr);
     col->pos = h.pos; col->open = true;
     return 0;
 }

@@ -1,6 +1,9 @@
 """The plan counters of every model kind, graph by graph: one two-layer synthetic model per kind, two steps (plus the frames a tts model waits
 before its first Depth step) or the batched passes of its kind and a live step, the counters read after every call that computes graphs, then each
 cached graph computed once more on its own and read again. Shared by tests/test_plan_shape_gpu.py (asserts the counters) and tests/microbench/plan_dump_shapes.py (prints them)."""
+import codec_slot_state_util as cs
+import codec_slots_util as du
+import encoder_slots_util as eu
 import hot_util as hu
 import persona_util as pp
 import sampling_util as sp
@@ -21,7 +24,9 @@ COUNTERS = ("kernels_in_last_plan", "fused_nodes_in_last_plan", "nodes_in_last_p
             "ring_copy_launches_in_last_plan", "ring_copy_jobs_in_last_plan", "attention_folds_planned",
             "attn_row_launches_in_last_plan", "attn_row_jobs_in_last_plan", "attn_row_rows_in_last_plan", "cross_block_launches_in_last_plan",
             "cross_block_jobs_in_last_plan", "float_batched_mms_in_last_plan", "float_acc_mms_in_last_plan", "pass_input_launches_in_last_plan",
-            "pass_input_rows_in_last_plan")
+            "pass_input_rows_in_last_plan",
+            "convtr_column_groups_in_last_plan", "codec_attn_launches_in_last_plan", "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan",
+            "state_copy_launches_in_last_plan", "state_copy_jobs_in_last_plan")
 GRAPHS = ((0, "temporal graph"), (1, "depth graph"))
 RING = 8
 
@@ -211,6 +216,38 @@ def single_prefill():
     return cached_graphs(m, out)
 
 
+def codec_single():
+    cfg = du.cfg_of()                                      # tests/test_codec_slots_gpu.py's single-stream reference, with the encoder beside it
+    cfg.enable_mimi_encoder = 1
+    m = hu.Model("hip", cfg)
+    m.mimi_encode(eu.pcm(900)[0])                          # single-column conv, dw-conv, VQ levels and the chained VQ
+    out = [("encode", counters(m))]
+    m.mimi_decode(du.codes(900)[0].tolist())               # single-column code gather, convtr, dw-convtr
+    out.append(("decode", counters(m)))
+    m.free()
+    return out
+
+
+def codec_slots(half):
+    """the codec graphs have no cached-graph accessor: the counters after every call that computes one"""
+    s = half.make("hip", 2)                                # tests/test_codec_slot_state_gpu.py
+    fr = half.frames(900, 2)
+    out = []
+    for b in range(2):
+        assert s.open(b) == 0
+    for k in range(2):
+        half.step(s, {0: fr[k], 1: fr[k]})
+        out.append((f"frame {k}", counters(s)))
+    assert s.close(1) == 0 and cs.fork(s, 0, 1) == 0
+    out.append(("fork", counters(s)))
+    blob = cs.save(s, 0)
+    out.append(("save", counters(s)))
+    assert s.close(1) == 0 and cs.load(s, 1, blob) == 0
+    out.append(("load", counters(s)))
+    s.free()
+    return out
+
+
 CASES = {
     "moshika_greedy": lambda: moshika(False),
     "moshika_sampled": lambda: moshika(True),
@@ -224,4 +261,7 @@ CASES = {
     "persona_slots_b2": persona_slots,
     "tts_single": tts_single,
     "single_prefill_t5": single_prefill,
+    "codec_single": codec_single,
+    "decoder_slots_b2": lambda: codec_slots(cs.HALVES[0]),
+    "encoder_slots_b2": lambda: codec_slots(cs.HALVES[1]),
 }
