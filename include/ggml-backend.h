@@ -139,6 +139,7 @@ struct ggml_mi355x_stats {
     int64_t code_gather_columns_in_last_plan;   // columns written by B-column code gathers of the last plan (encoder slots: the [1, n_q, B] code tensor in one k_gather_scalars launch; 0 = a copy per concat)
     int64_t state_copy_launches_in_last_plan;   // k_state_copy launches of the last plan (codec slot snapshots: every conv-state column copy of a fork, a save or a load in one launch) ...
     int64_t state_copy_jobs_in_last_plan;       // ... and the cpy nodes (jobs) they hold
+    int64_t f32_matrix_mms_in_last_plan;        // k_mm_f32_batched launches of the last plan (F32 weights against 2..128 activation rows on f64 MFMA tiles, set_f32_matrix)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -186,6 +187,16 @@ GGML_API void ggml_backend_mi355x_set_max_columns(ggml_backend_t backend, int n_
 // The environment variable MI355X_MMF=2 (read once per process) makes 1 the starting value of every fresh handle; MI355X_MMF=0 keeps turning both
 // mat-muls off. No-op on other backends.
 GGML_API void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t backend, int mode);
+// How this handle multiplies F32 weights by 2 .. 128 activation rows (the linears of the Mimi codec transformer in decoder and encoder slots). 0 (a
+// fresh handle): the generic product, a wave per output, which rounds every product to float before it adds it in double - the CPU product's bits.
+// 1: the f64-MFMA mat-mul (v_mfma_f64_16x16x4_f64 over the activations as they are, one launch, no workspace) - every product exact in double, a
+// double sum, one rounding to float: nearer to the real product, no longer bit-comparable with the CPU product, still bit-reproducible and
+// column-independent (a column's bits depend on K and its own values only, not on the number of rows or its place among them). Taken by contiguous
+// 16-byte aligned F32 products with K % 32 == 0 and at least 16 weight rows that reach the generic product today; single-column products, the
+// fused codec forms and every other weight type are untouched. A change of value drops the handle's cached plans;
+// ggml_backend_mi355x_init_stream inherits the value. The environment variable MI355X_MMF32=1 (read once per process) makes 1 the starting value of
+// every fresh handle; MI355X_NO_BATCHED_MM turns it off with the other batched mat-muls. No-op on other backends.
+GGML_API void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t backend, int on);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 // Makes the backend's HIP device current on the calling thread. A caller that talks to another HIP-based library itself on this backend's stream (RCCL:

@@ -86,6 +86,14 @@ struct moshi_hot_config {
     // shape of a B > 1 model ("PersonaPlex streams and slots" below). 1 without personaplex = 1, or beside anything the moshika shape excludes: NULL.
     // Ignored by a single-stream model. (It sits in front of float_accumulate, which tests/test_float_acc_streams_gpu.py pins as the struct's last field.)
     int32_t persona_columns;
+    // 1: the create calls switch the handle the model is created on to the f64-MFMA mat-mul for F32 weights, ggml_backend_mi355x_set_f32_matrix(backend, 1):
+    // the F32 linears of the codec transformers of moshi_hot_create_codec_slots / moshi_hot_mimi_decode_slots and moshi_hot_create_encoder_slots /
+    // moshi_hot_mimi_encode_slots ([512, 2 B] activations in the decoder) run as one matrix-core launch each instead of a wave per output. Every product
+    // is then exact in double and summed in double with one rounding - nearer to the real product than the CPU reference's float-rounded products,
+    // not bit-comparable with it; bit-reproducible and column-independent (the same conversation in any slot of any B gets the same bits). It belongs
+    // to the HANDLE and is never lowered, as float_accumulate below; single-column models plan no such product and are unchanged. Ignored on any other
+    // backend. (Like persona_columns it sits in front of float_accumulate.)
+    int32_t f32_matrix;
     // 1: moshi_hot_create / _create_streams / _create_slots / _create_from_gguf switch the handle the model is created on (and its codec sibling stream,
     // if one is made) to the float-accumulating mat-mul, ggml_backend_mi355x_set_float_accumulate(backend, 1): every B-column product of BF16 / F16
     // linears - streams and slots steps, moshi_hot_slots_prefill / _long, moshi_hot_slots_replay, the [dim, T] passes of moshi_hot_prefill - sums in

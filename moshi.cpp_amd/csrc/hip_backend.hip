@@ -59,6 +59,7 @@ struct hip_ctx {
     int flags = 0;
     int max_columns = 16;        // ggml_backend_mi355x_set_max_columns: the widest B-column sampler graph planned as one launch
     int float_acc = 0;           // ggml_backend_mi355x_set_float_accumulate: 1 = BF16 / F16 weights against 2..64 rows take the float-accumulating mat-mul
+    int f32_matrix = 0;          // ggml_backend_mi355x_set_f32_matrix: 1 = F32 weights against 2..128 rows take the f64-MFMA mat-mul (k_mm_f32_batched)
     bool no_capture = false;     // ggml_backend_mi355x_set_capture(.., 0): plans of repeated graphs are reused but not captured into hipGraphs
     ggml_mi355x_stats stats = {};
     // pooled allocations: size class -> free pointers
@@ -342,7 +343,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -545,6 +546,8 @@ static bool float_batched_ok(const ggml_tensor * w, int64_t T, bool float_acc) {
     return float_acc ? k_mm_f32acc_batched_supported(w->type, w->ne[0], w->ne[1], T) : k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
 }
 // its row converters read the activation rows (and alpha) as float4
+// F32 weights against 2..128 activation rows: MI355X_MMF32=1 makes the f64-MFMA mat-mul (k_mm_f32_batched) the starting mode of every fresh handle
+static int mmf32_env() { static const int v = [] { const char * e = getenv("MI355X_MMF32"); return e && atoi(e) == 1 ? 1 : 0; }(); return v; }
 static bool aligned16(const void * p) { return p != nullptr && (uintptr_t) p % 16 == 0; }
 
 static bool fill_matvec_base(mv_args & a, const ggml_tensor * mm) {
@@ -669,6 +672,15 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
                     const int wt = (int) w0->type;
                     if (em.c->float_acc) { em.push([=](hipStream_t s) { k_mm_f32acc_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_acc_mms++; }
                     else { em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_batched_mms++; }
+                    return;
+                }
+                // ... against F32 weights, opted into (set_f32_matrix): f64 MFMA tiles over the activations as they are
+                if (em.c->f32_matrix && !no_batched && w0->type == GGML_TYPE_F32 && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1 &&
+                    x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) &&
+                    aligned16(w0->data) && aligned16(x1->data) && aligned16(n->data) && k_mm_f32_batched_supported(w0->type, w0->ne[0], w0->ne[1], Tn)) {
+                    const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
+                    const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                    em.push([=](hipStream_t s) { k_mm_f32_batched(s, wp, rb, K, M, Tn, xp, K, yp, M, nullptr, 0); }); em.p->n_f32_matrix_mms++;
                     return;
                 }
             }
@@ -3359,6 +3371,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
+    c->stats.f32_matrix_mms_in_last_plan = p->n_f32_matrix_mms;
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
@@ -3522,8 +3535,8 @@ static ggml_backend_t hip_dev_init(ggml_backend_dev_t d, const char *) {
     ctx_init_lazy(c);
     // a fresh backend handle starts from default flags, the default sampler width and zeroed counters (the device context is shared)
     const int float_acc0 = mmf_env() == 2 ? 1 : 0;   // MI355X_MMF=2: the float-accumulating mat-mul from the start
-    if (c->flags != 0 || c->max_columns != 16 || c->float_acc != float_acc0) {
-        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16; c->float_acc = float_acc0;
+    if (c->flags != 0 || c->max_columns != 16 || c->float_acc != float_acc0 || c->f32_matrix != mmf32_env()) {
+        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16; c->float_acc = float_acc0; c->f32_matrix = mmf32_env();
     }
     c->stats = {};
     auto * b = new ggml_backend;
@@ -3582,6 +3595,16 @@ extern "C" void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t b, int m
     c->plans.clear();
     c->float_acc = mode;
 }
+extern "C" void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t b, int on) {
+    if (!b || b->iface.get_name != hip_backend_name) return;   // any other backend: nothing to do
+    hip_ctx * c = (hip_ctx *) b->context;
+    on = on ? 1 : 0;
+    if (on == c->f32_matrix) return;
+    if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
+    for (auto & kv : c->plans) plan_free(c, kv.second);   // the plans hold the other kernel's launches
+    c->plans.clear();
+    c->f32_matrix = on;
+}
 extern "C" void ggml_backend_mi355x_set_flags(ggml_backend_t b, int flags) {
     hip_ctx * c = ctx_of(b);
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
@@ -3621,5 +3644,6 @@ extern "C" ggml_backend_t ggml_backend_mi355x_init_stream(ggml_backend_t base) {
     c->no_capture = b0->no_capture;
     c->max_columns = b0->max_columns;
     c->float_acc = b0->float_acc;     // (a fresh handle holds no plans yet)
+    c->f32_matrix = b0->f32_matrix;
     return b;
 }

@@ -180,6 +180,12 @@ void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes,
 bool k_mm_f32acc_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
 void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
                          void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
+// F32 weights against 2 .. 128 F32 activation rows, opt-in (ggml_backend_mi355x_set_f32_matrix): one launch of 16x16x4 f64 MFMA tiles, no workspace -
+// exact products, a double sum, one rounding to float. NOT the generic product's bits (which round every product to float first); a column's bits
+// depend on K and its own values only. Rows and columns dense and 16-byte aligned (w, row_bytes, x, 4 x_cs); residual optional
+bool k_mm_f32_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
+void k_mm_f32_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                      float * y, int64_t y_cs, const float * residual, int64_t r_cs);
 
 // streaming self-attention over a ring KV cache (T <= 4 new tokens): RoPE(q,k) -> cache write -> masked
 // softmax(K q) V restricted to un-masked slots; see hip_kernels_fused.hip

@@ -1574,6 +1574,18 @@ void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_b
     else mm_f32acc_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
 }
 
+// ---- the batched mat-mul for F32 weights: exact products, double sums on f64 MFMA tiles (hip_mm_f32.h); no converter pass, no workspace -----------
+#include "hip_mm_f32.h"
+bool k_mm_f32_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) { return wtype == GGML_TYPE_F32 && K % 32 == 0 && M >= 16 && T >= 2 && T <= 128; }
+void k_mm_f32_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                      float * y, int64_t y_cs, const float * residual, int64_t r_cs) {
+    const int nch = (int) (K / 32);
+    const dim3 grid((unsigned) ((M + 15) / 16), T > 64 ? 2 : 1);   // T > 64: columns 0..63 and 64..T - 1, the second half clamped inside its four tiles
+#define MM32_LAUNCH(NT) mm_f32_mfma_kernel<NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, x, x_cs, y, y_cs, residual, r_cs)
+    if (T <= 16) MM32_LAUNCH(1); else if (T <= 32) MM32_LAUNCH(2); else if (T <= 48) MM32_LAUNCH(3); else MM32_LAUNCH(4);
+#undef MM32_LAUNCH
+}
+
 static mv_profile * g_mv_profile = nullptr;
 void k_matvec_set_profile(mv_profile * p) { g_mv_profile = p; }
 
