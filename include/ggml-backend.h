@@ -140,6 +140,7 @@ struct ggml_mi355x_stats {
     int64_t state_copy_launches_in_last_plan;   // k_state_copy launches of the last plan (codec slot snapshots: every conv-state column copy of a fork, a save or a load in one launch) ...
     int64_t state_copy_jobs_in_last_plan;       // ... and the cpy nodes (jobs) they hold
     int64_t f32_matrix_mms_in_last_plan;        // k_mm_f32_batched launches of the last plan (F32 weights against 2..128 activation rows on f64 MFMA tiles, set_f32_matrix)
+    int64_t convtr_matrix_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan that are ONE k_convtr_cols_mfma launch (f64 MFMA tiles, no workspace; bit 1 of set_f32_matrix) - a subset of convtr_column_groups_in_last_plan
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -196,6 +197,13 @@ GGML_API void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t backend, i
 // fused codec forms and every other weight type are untouched. A change of value drops the handle's cached plans;
 // ggml_backend_mi355x_init_stream inherits the value. The environment variable MI355X_MMF32=1 (read once per process) makes 1 the starting value of
 // every fresh handle; MI355X_NO_BATCHED_MM turns it off with the other batched mat-muls. No-op on other backends.
+// `on` is a set of bits; the above is bit 0 (value 1). Bit 1 (value 2) sends the streaming transposed convolutions at B >= 2 columns (the four SEANet
+// upsampling layers of decoder slots) to ONE launch of f64 MFMA tiles each instead of a partial-product launch, a workspace of double partials and a
+// finish launch: per tap one double sum of exact products over the input channels, one rounding, then float adds of the two taps, the carried tail
+// and the bias - the same trade (nearer to the real value, not bit-comparable with the CPU product, bit-reproducible and column-independent), and
+// the plan reserves no partials. Taken by dense F32 weights [K, OC, IC] with K == 2 x stride, lcm(K, 16) of 16, 48 or 80, IC % 32 == 0 and OC K % 4 == 0 whose
+// slab of lcm(K, 16) taps fits the LDS; F16 weights, other shapes and the single-column form keep the pair. 3 sets both bits; MI355X_MMF32=2 / 3
+// likewise. Bits above bit 1 are ignored.
 GGML_API void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t backend, int on);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);

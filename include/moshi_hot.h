@@ -93,6 +93,9 @@ struct moshi_hot_config {
     // not bit-comparable with it; bit-reproducible and column-independent (the same conversation in any slot of any B gets the same bits). It belongs
     // to the HANDLE and is never lowered, as float_accumulate below; single-column models plan no such product and are unchanged. Ignored on any other
     // backend. (Like persona_columns it sits in front of float_accumulate.)
+    // The value is a set of bits, passed to ggml_backend_mi355x_set_f32_matrix as it is: 1 the F32 linears (above); 2 the four streaming transposed
+    // convolutions of moshi_hot_mimi_decode_slots as one f64-MFMA launch each, without the workspace of double partials (the same trade: exact
+    // products, one double sum per tap, not bit-comparable with the CPU reference, column-independent); 3 both.
     int32_t f32_matrix;
     // 1: moshi_hot_create / _create_streams / _create_slots / _create_from_gguf switch the handle the model is created on (and its codec sibling stream,
     // if one is made) to the float-accumulating mat-mul, ggml_backend_mi355x_set_float_accumulate(backend, 1): every B-column product of BF16 / F16

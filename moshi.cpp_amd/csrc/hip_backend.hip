@@ -59,7 +59,7 @@ struct hip_ctx {
     int flags = 0;
     int max_columns = 16;        // ggml_backend_mi355x_set_max_columns: the widest B-column sampler graph planned as one launch
     int float_acc = 0;           // ggml_backend_mi355x_set_float_accumulate: 1 = BF16 / F16 weights against 2..64 rows take the float-accumulating mat-mul
-    int f32_matrix = 0;          // ggml_backend_mi355x_set_f32_matrix: 1 = F32 weights against 2..128 rows take the f64-MFMA mat-mul (k_mm_f32_batched)
+    int f32_matrix = 0;          // ggml_backend_mi355x_set_f32_matrix, bits: 1 = F32 weights against 2..128 rows take the f64-MFMA mat-mul (k_mm_f32_batched), 2 = B-column transposed convolutions take k_convtr_cols_mfma
     bool no_capture = false;     // ggml_backend_mi355x_set_capture(.., 0): plans of repeated graphs are reused but not captured into hipGraphs
     ggml_mi355x_stats stats = {};
     // pooled allocations: size class -> free pointers
@@ -343,7 +343,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -546,8 +546,9 @@ static bool float_batched_ok(const ggml_tensor * w, int64_t T, bool float_acc) {
     return float_acc ? k_mm_f32acc_batched_supported(w->type, w->ne[0], w->ne[1], T) : k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
 }
 // its row converters read the activation rows (and alpha) as float4
-// F32 weights against 2..128 activation rows: MI355X_MMF32=1 makes the f64-MFMA mat-mul (k_mm_f32_batched) the starting mode of every fresh handle
-static int mmf32_env() { static const int v = [] { const char * e = getenv("MI355X_MMF32"); return e && atoi(e) == 1 ? 1 : 0; }(); return v; }
+// MI355X_MMF32=1 / 2 / 3: the starting value of set_f32_matrix on every fresh handle - bit 0 the f64-MFMA mat-mul for F32 weights against 2..128 activation
+// rows (k_mm_f32_batched), bit 1 the one-launch f64-MFMA transposed convolution at B columns (k_convtr_cols_mfma)
+static int mmf32_env() { static const int v = [] { const char * e = getenv("MI355X_MMF32"); const int m = e ? atoi(e) : 0; return m >= 0 && m <= 3 ? m : 0; }(); return v; }
 static bool aligned16(const void * p) { return p != nullptr && (uintptr_t) p % 16 == 0; }
 
 static bool fill_matvec_base(mv_args & a, const ggml_tensor * mm) {
@@ -675,7 +676,7 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
                     return;
                 }
                 // ... against F32 weights, opted into (set_f32_matrix): f64 MFMA tiles over the activations as they are
-                if (em.c->f32_matrix && !no_batched && w0->type == GGML_TYPE_F32 && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1 &&
+                if ((em.c->f32_matrix & 1) && !no_batched && w0->type == GGML_TYPE_F32 && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1 &&
                     x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) &&
                     aligned16(w0->data) && aligned16(x1->data) && aligned16(n->data) && k_mm_f32_batched_supported(w0->type, w0->ne[0], w0->ne[1], Tn)) {
                     const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
@@ -1962,7 +1963,7 @@ static bool match_convtr(const analysis & an, int pos, step_group & grp, emitter
 // E'. the same at B columns (decoder slots, moshi_hot.cpp streaming_conv_transpose): for b = 0 .. B - 1, in graph order, conv_transpose_1d(w, view of
 //     column b of x) copied into column b of one [OLf, OC, B] tensor y that no node computes, then the streaming tail ONCE over the B columns of y and of
 //     prev. Matched at column 0's conv_transpose_1d; all of it becomes one partial launch over the B x L positions and one finish launch (k_convtr_cols).
-static bool match_convtr_columns(const analysis & an, int pos, step_group & grp, emitter & em) {
+static bool match_convtr_columns(const analysis & an, int pos, step_group & grp, emitter & em, bool & matrix) {
     const ggml_cgraph * g = an.g;
     const ggml_tensor * ct0 = g->nodes[pos];
     if (ct0->op != GGML_OP_CONV_TRANSPOSE_1D || uses_of(an, ct0) != 1) return false;
@@ -2009,12 +2010,22 @@ static bool match_convtr_columns(const analysis & an, int pos, step_group & grp,
     if (!xin->data || xin->type != GGML_TYPE_F32 || xin->ne[2] != B) return false;
     if (t.out->type != GGML_TYPE_F32 || t.out->ne[0] != (int64_t) L * s0 || t.out->ne[1] != OC || t.out->ne[2] != B) return false;
     for (int m : members) if (m < 0 || an.skip[(size_t) m]) return false;
-    void * ws = em.ws(k_convtr_cols_ws_size(w, L, B));
-    const tdesc d_w = make_tdesc(w), d_x = make_tdesc(xin), d_out = make_tdesc(t.out);
     float * pv = (float *) t.prev->data;
     const float * bias = t.bias;
     grp.steps.clear();
-    grp.steps.push_back([=](hipStream_t s) { k_convtr_cols(s, d_out, pv, bias, d_w, d_x, s0, pre_elu, ws); });
+    // opted into (bit 1 of set_f32_matrix): the whole group as one launch of f64 MFMA tiles, no partials in the workspace
+    if ((em.c->f32_matrix & 2) && ggml_is_contiguous(w) && aligned16(w->data) && ggml_is_contiguous(xin) && ggml_is_contiguous(t.out) &&
+        k_convtr_cols_mfma_supported(w->type, K, OC, w->ne[2], s0, L, B)) {
+        const float * wp = (const float *) w->data, * xp = (const float *) xin->data;
+        float * op = (float *) t.out->data;
+        const int IC = (int) w->ne[2], Bn = (int) B;
+        grp.steps.push_back([=](hipStream_t s) { k_convtr_cols_mfma(s, op, pv, bias, wp, xp, K, OC, IC, s0, L, Bn, pre_elu); });
+        matrix = true;
+    } else {
+        void * ws = em.ws(k_convtr_cols_ws_size(w, L, B));
+        const tdesc d_w = make_tdesc(w), d_x = make_tdesc(xin), d_out = make_tdesc(t.out);
+        grp.steps.push_back([=](hipStream_t s) { k_convtr_cols(s, d_out, pv, bias, d_w, d_x, s0, pre_elu, ws); });
+    }
     grp.members = members;
     grp.emit_pos = pos_of(an, t.out);
     return true;
@@ -2648,11 +2659,11 @@ static void pass_codec_convs(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i]) continue;
         step_group grp;
-        bool convtr_columns = false, vq_columns = false;
+        bool convtr_columns = false, convtr_matrix = false, vq_columns = false;
         const enum ggml_op op = pl.g->nodes[i]->op;
         if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em) && !match_conv_columns(pl.an, i, grp)) continue; }
         else if (op == GGML_OP_CONV_TRANSPOSE_1D) {
-            if (match_convtr_columns(pl.an, i, grp, pl.em)) convtr_columns = true;
+            if (match_convtr_columns(pl.an, i, grp, pl.em, convtr_matrix)) convtr_columns = true;
             else if (!match_convtr(pl.an, i, grp, pl.em)) continue;
         }
         else if (op == GGML_OP_ARGMAX) {
@@ -2665,6 +2676,7 @@ static void pass_codec_convs(planner & pl) {
         else continue;
         if (!claim_group(pl, grp)) continue;
         if (convtr_columns) pl.p->n_convtr_column_groups++;
+        if (convtr_matrix) pl.p->n_convtr_matrix_groups++;
         if (vq_columns) pl.p->n_vq_column_levels++;
         for (auto & f : grp.steps) {
             pl.at_pos[grp.emit_pos].push_back(f);
@@ -3371,7 +3383,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
-    c->stats.f32_matrix_mms_in_last_plan = p->n_f32_matrix_mms;
+    c->stats.f32_matrix_mms_in_last_plan = p->n_f32_matrix_mms; c->stats.convtr_matrix_groups_in_last_plan = p->n_convtr_matrix_groups;
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
@@ -3598,7 +3610,7 @@ extern "C" void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t b, int m
 extern "C" void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t b, int on) {
     if (!b || b->iface.get_name != hip_backend_name) return;   // any other backend: nothing to do
     hip_ctx * c = (hip_ctx *) b->context;
-    on = on ? 1 : 0;
+    on &= 3;   // bit 0: the F32 linears, bit 1: the B-column transposed convolutions
     if (on == c->f32_matrix) return;
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
     for (auto & kv : c->plans) plan_free(c, kv.second);   // the plans hold the other kernel's launches

@@ -87,6 +87,11 @@ int  k_conv_transpose_1d_partial(hipStream_t s, tdesc w, tdesc x, void * ws, int
 void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w, const float * bias, int K, int OW, int OC, int B);
 size_t k_convtr_cols_ws_size(const struct ggml_tensor * w, int64_t L, int64_t B);
 void k_convtr_cols(hipStream_t s, tdesc out, float * prev, const float * bias, tdesc w, tdesc x, int s0, int pre_elu, void * ws);
+// the same as ONE launch of 16x16x4 f64 MFMA tiles without a workspace, opt-in (bit 1 of ggml_backend_mi355x_set_f32_matrix): exact products, one
+// double sum over IC per tap, one rounding, then float adds of the two taps, the old tail and the bias. NOT k_convtr_cols' bits; a column's bits depend
+// on the layer and its own values only. F32 w [K, OC, IC] with K == 2 s0, x [L, IC, B], prev and out all dense, w 16-byte aligned
+bool k_convtr_cols_mfma_supported(int wtype, int64_t K, int64_t OC, int64_t IC, int s0, int64_t L, int64_t B);
+void k_convtr_cols_mfma(hipStream_t s, float * out, float * prev, const float * bias, const float * w, const float * x, int K, int OC, int IC, int s0, int L, int B, int pre_elu);
 // scatter of batched small uploads: descs/blob live in pinned host memory mapped into the device
 struct upload_desc { char * dst; uint32_t offset; uint32_t size; };
 void k_scatter_uploads(hipStream_t s, const upload_desc * descs, const char * blob, int n);

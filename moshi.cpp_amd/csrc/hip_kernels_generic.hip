@@ -852,6 +852,32 @@ void k_convtr_cols(hipStream_t s, tdesc out, float * prev, const float * bias, t
     convtr_finish_cols_kernel<<<dim3((unsigned) nblocks(n), (unsigned) B), BLOCK, 0, s>>>(out, prev, bias, (const double *) ws, K, OC, L, BL, s0, nsplit);
 }
 
+// ---- the same as ONE launch of f64 MFMA tiles, no workspace (hip_convtr_mfma.h); opt-in, not the pair's bits ----
+#include "hip_convtr_mfma.h"
+// n tiles of a channel group: lcm(K, 16) / 16
+static int ctm_ntg(int K) { int a = K, b = 16; while (b) { const int t = a % b; a = b; b = t; } return K / a; }
+bool k_convtr_cols_mfma_supported(int wtype, int64_t K, int64_t OC, int64_t IC, int s0, int64_t L, int64_t B) {
+    if (wtype != GGML_TYPE_F32 || K != 2 * (int64_t) s0 || K > 80 /* (five n tiles at the most) */ || IC % 32 != 0 || (OC * K) % 4 != 0 || B < 2 || B > 65535 || L < 1 || B * L > (1 << 30)) return false;
+    const int ntg = ctm_ntg((int) K);
+    return (ntg == 1 || ntg == 3 || ntg == 5) && ctm_lds_floats(ntg * 16, (int) IC) * 4 <= 160 * 1024;
+}
+void k_convtr_cols_mfma(hipStream_t s, float * out, float * prev, const float * bias, const float * w, const float * x, int K, int OC, int IC, int s0, int L, int B, int pre_elu) {
+    GGML_ASSERT(k_convtr_cols_mfma_supported(GGML_TYPE_F32, K, OC, IC, s0, L, B));
+    const int ntg = ctm_ntg(K), NW = ntg * 16, nx = (OC * K + NW - 1) / NW;
+    // whole columns per workgroup: at least a round of positions, and no more workgroups than the machine needs
+    int ny = std::max(1, (CTM_TARGET_WGS + nx - 1) / nx);
+    int cols = std::max((B + ny - 1) / ny, (CTM_ROWS + L - 1) / L);
+    if (cols > B) cols = B;
+    ny = (B + cols - 1) / cols;
+    const size_t lds = ctm_lds_floats(NW, IC) * 4;
+    static size_t granted[3] = { 0, 0, 0 };
+#define CTM_LAUNCH(NTG, slot) do { \
+        if (lds > 64 * 1024 && granted[slot] < lds) { HIP_CHECK(hipFuncSetAttribute((const void *) convtr_cols_mfma_kernel<NTG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); granted[slot] = 160 * 1024; } \
+        convtr_cols_mfma_kernel<NTG><<<dim3((unsigned) nx, (unsigned) ny), 256, lds, s>>>(w, x, prev, bias, out, K, s0, IC, OC, L, B, cols, pre_elu); } while (0)
+    if (ntg == 1) CTM_LAUNCH(1, 0); else if (ntg == 3) CTM_LAUNCH(3, 1); else CTM_LAUNCH(5, 2);
+#undef CTM_LAUNCH
+}
+
 // depthwise variant for one input frame: y[k, c] = x[c] * w[k, c]; y[:PT] += prev[K-PT:]; prev = y; out = (y + bias)[:K-PT]
 __global__ void dw_convtr_frame_kernel(float * out, float * prev, const float * bias, const char * x, int64_t x_cs, const char * w, int64_t w_cs, int K, int PT, int C, int64_t out_cs, int64_t out_ks) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
