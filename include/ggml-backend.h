@@ -130,7 +130,7 @@ struct ggml_mi355x_stats {
     int64_t cross_block_launches_in_last_plan;  // k_cross_attn_blocks launches of the last plan (tts replay: the cross-attention of one layer of a pass) ...
     int64_t cross_block_jobs_in_last_plan;      // ... and the jobs they hold
     int64_t float_batched_mms_in_last_plan;     // k_mm_f_batched launches of the last plan (BF16 / F16 weights against 2..64 activation rows on f64 MFMA tiles)
-    int64_t float_acc_mms_in_last_plan;         // k_mm_f32acc_batched launches of the last plan (the same products on float-accumulating BF16 / F16 MFMA tiles, set_float_accumulate)
+    int64_t float_acc_mms_in_last_plan;         // k_mm_f_batched launches of the last plan with float_acc set (the same products on float-accumulating BF16 / F16 MFMA tiles, set_float_accumulate)
     int64_t pass_input_launches_in_last_plan;   // k_pass_input launches of the last plan (persona passes: the voice rows and embedding sums of a [dim, T] input in one launch) ...
     int64_t pass_input_rows_in_last_plan;       // ... and the rows they write
     int64_t convtr_column_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan (decoder slots: the B convtr + copy nodes of a SEANet layer and their shared streaming tail as one partial and one finish launch)

@@ -539,11 +539,11 @@ struct emitter {
 
 static bool is_qblock(enum ggml_type t) { return t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0; }
 // BF16 / F16 weights against 2..64 activation rows: the f64-MFMA mat-mul (k_mm_f_batched). MI355X_MMF=0 sends them back to the generic product (the A/B of DESIGN.md 23)
-// MI355X_MMF=2 makes the float-accumulating mat-mul (k_mm_f32acc_batched) the starting mode of every fresh handle
+// MI355X_MMF=2 makes its float-accumulating form (set_float_accumulate) the starting mode of every fresh handle
 static int mmf_env() { static const int v = [] { const char * e = getenv("MI355X_MMF"); return e ? atoi(e) : 1; }(); return v; }
-static bool float_batched_ok(const ggml_tensor * w, int64_t T, bool float_acc) {
+static bool float_batched_ok(const ggml_tensor * w, int64_t T) {
     if (mmf_env() == 0 || !w->data || (uintptr_t) w->data % 16 != 0 || w->nb[1] % 16 != 0) return false;
-    return float_acc ? k_mm_f32acc_batched_supported(w->type, w->ne[0], w->ne[1], T) : k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
+    return k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
 }
 // its row converters read the activation rows (and alpha) as float4
 // MI355X_MMF32=1 / 2 / 3: the starting value of set_f32_matrix on every fresh handle - bit 0 the f64-MFMA mat-mul for F32 weights against 2..128 activation
@@ -651,36 +651,31 @@ static void emit_generic(emitter & em, ggml_tensor * n) {
                 em.push([=](hipStream_t s) { k_matvec(s, mv); });
                 return;
             }
-            {   // several activation rows against Q4_K weights (batched prompt prefill): int8 MFMA tiles
+            {   // several activation rows against a dense weight matrix (batched prompt prefill, B-column steps): MFMA tiles
                 const ggml_tensor * w0 = n->src[0], * x1 = n->src[1];
                 const int64_t Tn = ggml_nelements(x1) / x1->ne[0];
                 static const bool no_batched = getenv("MI355X_NO_BATCHED_MM") != nullptr;
-                if (!no_batched && x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && ggml_is_contiguous(n) && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1 &&
-                    k_mm_q4k_batched_supported(w0->type, w0->ne[0], w0->ne[1], Tn)) {
-                    const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
-                    const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                const bool dense = !no_batched && x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && ggml_is_contiguous(n) && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1;
+                const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
+                const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                const int wt = (int) w0->type;
+                // Q4_K / Q8_0 / Q4_0 weights: int8 MFMA tiles
+                if (dense && k_mm_q4k_batched_supported(w0->type, K, M, Tn)) {
                     void * ws = em.ws(k_mm_q4k_batched_ws_size(K, Tn));
-                    const int wt = (int) w0->type;
                     em.push([=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); });
                     return;
                 }
-                // ... against BF16 / F16 weights: f64 MFMA tiles
-                if (!no_batched && x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) && ggml_is_contiguous(w0) &&
-                    w0->ne[2] == 1 && w0->ne[3] == 1 && aligned16(x1->data) && float_batched_ok(w0, Tn, em.c->float_acc != 0)) {
-                    const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
-                    const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                // BF16 / F16 weights: f64 MFMA tiles, or float-accumulating ones (set_float_accumulate)
+                if (dense && n->type == GGML_TYPE_F32 && aligned16(x1->data) && float_batched_ok(w0, Tn)) {
                     void * ws = em.ws(k_mm_f_batched_ws_size(K, Tn));
-                    const int wt = (int) w0->type;
-                    if (em.c->float_acc) { em.push([=](hipStream_t s) { k_mm_f32acc_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_acc_mms++; }
-                    else { em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0); }); em.p->n_float_batched_mms++; }
+                    const bool facc = em.c->float_acc != 0;
+                    em.push([=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, K, ws, yp, M, nullptr, 0, facc); });
+                    (facc ? em.p->n_float_acc_mms : em.p->n_float_batched_mms)++;
                     return;
                 }
-                // ... against F32 weights, opted into (set_f32_matrix): f64 MFMA tiles over the activations as they are
-                if ((em.c->f32_matrix & 1) && !no_batched && w0->type == GGML_TYPE_F32 && ggml_is_contiguous(w0) && w0->ne[2] == 1 && w0->ne[3] == 1 &&
-                    x1->type == GGML_TYPE_F32 && ggml_is_contiguous(x1) && n->type == GGML_TYPE_F32 && ggml_is_contiguous(n) &&
-                    aligned16(w0->data) && aligned16(x1->data) && aligned16(n->data) && k_mm_f32_batched_supported(w0->type, w0->ne[0], w0->ne[1], Tn)) {
-                    const char * wp = (const char *) w0->data; const int64_t rb = (int64_t) w0->nb[1], K = w0->ne[0], M = w0->ne[1];
-                    const float * xp = (const float *) x1->data; float * yp = (float *) n->data;
+                // F32 weights, opted into (set_f32_matrix): f64 MFMA tiles over the activations as they are
+                if ((em.c->f32_matrix & 1) && dense && n->type == GGML_TYPE_F32 && aligned16(w0->data) && aligned16(x1->data) && aligned16(n->data) &&
+                    k_mm_f32_batched_supported(w0->type, K, M, Tn)) {
                     em.push([=](hipStream_t s) { k_mm_f32_batched(s, wp, rb, K, M, Tn, xp, K, yp, M, nullptr, 0); }); em.p->n_f32_matrix_mms++;
                     return;
                 }
@@ -1372,7 +1367,7 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
     if (x1->type != GGML_TYPE_F32 || !ggml_is_contiguous(x1) || mm->type != GGML_TYPE_F32 || !ggml_is_contiguous(mm) || mm->view_src) return false;
     const int64_t K = w0->ne[0], M = w0->ne[1], Tn = ggml_nelements(x1) / K;
     const bool facc = fw && em.c->float_acc != 0;
-    if (fw ? !float_batched_ok(w0, Tn, facc) : !k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
+    if (fw ? !float_batched_ok(w0, Tn) :!k_mm_q4k_batched_supported(w0->type, K, M, Tn)) return false;
     grp.float_weights = fw; grp.float_acc = facc;
     grp.members.assign(1, pos);
     grp.emit_pos = pos;
@@ -1429,8 +1424,7 @@ static bool match_batched_mm(const analysis & an, int pos, emitter & em, bmm_gro
     const int64_t rb = (int64_t) w0->nb[1];
     void * ws = em.ws(fw ? k_mm_f_batched_ws_size(K, Tn) : k_mm_q4k_batched_ws_size(K, Tn));
     const int wt = (int) w0->type;
-    if (facc) grp.run = [=](hipStream_t s) { k_mm_f32acc_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
-    else if (fw) grp.run = [=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
+    if (fw) grp.run = [=](hipStream_t s) { k_mm_f_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, facc, prologue, alpha, eps); };
     else grp.run = [=](hipStream_t s) { k_mm_q4k_batched(s, wt, wp, rb, K, M, Tn, xp, x_cs, ws, yp, M, res, M, prologue, alpha, eps); };
     return true;
 }

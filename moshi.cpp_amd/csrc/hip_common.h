@@ -175,16 +175,13 @@ void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_byte
                       void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
 
 // the same for BF16 / F16 weights (K % 32 == 0, dense rows): rows rounded to the weight's type into `ws`, then 16x16x4 f64 MFMA tiles - exact products,
-// double accumulation, one rounding to float (ggml's generic BF16 / F16 product); all T <= 64 columns in one pass, a column's bits independent of T
+// double accumulation, one rounding to float (ggml's generic BF16 / F16 product); all T <= 64 columns in one pass, a column's bits independent of T.
+// float_acc (ggml_backend_mi355x_set_float_accumulate): the same rows, workspace and folds, the sums in float on 16x16x32 BF16 / F16 MFMA tiles - not
+// bit-comparable with the generic product, a column's bits still independent of T and its neighbours
 size_t k_mm_f_batched_ws_size(int64_t K, int64_t T);
 bool k_mm_f_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
-void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                    void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
-// the opt-in float-accumulating form (ggml_backend_mi355x_set_float_accumulate): the same rows, workspace (k_mm_f_batched_ws_size) and folds, the sums
-// in float on 16x16x32 BF16 / F16 MFMA tiles - not bit-comparable with the generic product, a column's bits still independent of T and its neighbours
-bool k_mm_f32acc_batched_supported(int wtype, int64_t K, int64_t M, int64_t T);
-void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                         void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
+void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs, void * ws,
+                    float * y, int64_t y_cs, const float * residual, int64_t r_cs, bool float_acc, int prologue = 0, const float * alpha = nullptr, float eps = 0.f);
 // F32 weights against 2 .. 128 F32 activation rows, opt-in (ggml_backend_mi355x_set_f32_matrix): one launch of 16x16x4 f64 MFMA tiles, no workspace -
 // exact products, a double sum, one rounding to float. NOT the generic product's bits (which round every product to float first); a column's bits
 // depend on K and its own values only. Rows and columns dense and 16-byte aligned (w, row_bytes, x, 4 x_cs); residual optional

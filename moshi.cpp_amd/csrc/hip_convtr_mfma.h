@@ -15,7 +15,7 @@
 // [IC][16 NTG] is fetched once into LDS (n past OC K zero-filled) and reused for every position it walks. The run is walked in rounds of 64 positions
 // in increasing p; in a round wave v owns the 16 positions of tile v against all NTG n tiles over all of IC: no cross-wave reduction, one order of
 // sums. One MFMA step: lane (r = lane & 15, g = lane >> 4) feeds x of position r at ic kb + g on the A side and w[kb + g][16 nt + r] on the B side,
-// and holds Z[position g + 4 q][n r], q = 0..3 (the lane map at the top of hip_mm_float.h). The activations are read as they are, eight steps ahead.
+// and holds Z[position g + 4 q][n r], q = 0..3 (the f64 lane map at the top of hip_mm_tile.h). The activations are read as they are, eight steps ahead.
 //
 // The rounded taps of a round meet in LDS (zb, row 0 = the last position of the round before: the tap carry - a run starts at a column's l = 0, so a
 // round never needs a position its workgroup did not compute, and no halo is recomputed). After a barrier the 256 threads walk (channel, position, j)

@@ -1470,6 +1470,11 @@ __global__ void __launch_bounds__(64 * MMQ_NW) mm_q80_mfma_kernel(const char * w
 }
 
 static int env_int(const char * name, int def);
+// the column tiles (16 columns each) that T <= 64 columns of one launch take, as a compile-time constant: f(std::integral_constant<int, NT>)
+template <typename F> static void with_nt(int64_t T, F && f) {
+    if (T <= 16) f(std::integral_constant<int, 1>()); else if (T <= 32) f(std::integral_constant<int, 2>());
+    else if (T <= 48) f(std::integral_constant<int, 3>()); else f(std::integral_constant<int, 4>());
+}
 #define MMQ_WIDE_DEFAULT 3   // the Q4_K kernels take 33..64 columns in one pass; the Q8_0 / Q4_0 kernel was 3-5 % slower that way and keeps passes of 32
 size_t k_mm_q4k_batched_ws_size(int64_t K, int64_t T) { return (size_t) (K / 256) * (size_t) T * sizeof(xblkb); }
 bool k_mm_q4k_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) {
@@ -1498,92 +1503,72 @@ void k_mm_q4k_batched(hipStream_t s, int wtype, const char * w, int64_t row_byte
             const xblk80b * xq = xq0 + c0 * nb;
             float * yc = y + c0 * y_cs;
             const float * rc = residual ? residual + c0 * r_cs : nullptr;
-#define MMQ80_LAUNCH(NT, FMT) mm_q80_mfma_kernel<NT, FMT><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
-            if (wtype == GGML_TYPE_Q8_0) {
-                if (Tc <= 16) MMQ80_LAUNCH(1, MVF_Q80); else if (Tc <= 32) MMQ80_LAUNCH(2, MVF_Q80); else if (Tc <= 48) MMQ80_LAUNCH(3, MVF_Q80); else MMQ80_LAUNCH(4, MVF_Q80);
-            } else {
-                if (Tc <= 16) MMQ80_LAUNCH(1, MVF_Q40); else if (Tc <= 32) MMQ80_LAUNCH(2, MVF_Q40); else if (Tc <= 48) MMQ80_LAUNCH(3, MVF_Q40); else MMQ80_LAUNCH(4, MVF_Q40);
-            }
-#undef MMQ80_LAUNCH
+            with_nt(Tc, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                if (wtype == GGML_TYPE_Q8_0) mm_q80_mfma_kernel<NT, MVF_Q80><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+                else mm_q80_mfma_kernel<NT, MVF_Q40><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+            });
         }
         return;
     }
     if (prologue == MV_RMSNORM) rms_quant_rows_q8k_kernel<<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, nb, (xblkb *) ws);
     else if (prologue == MV_GATE_SILU) gate_quant_rows_q8k_kernel<<<(int) (T * nb), 64, 0, s>>>(x, x_cs, (int) K, nb, (xblkb *) ws);
     else quant_rows_q8k_kernel<<<(int) (T * nb), 64, 0, s>>>(x, x_cs, nb, (xblkb *) ws);
-    const int grid = (int) ((M + 15) / 16);
+    const int grid = (int) ((M + 15) / 16), grid64 = (int) ((M + 63) / 64);
     const int thr = 64 * MMQ_NW;
     for (int64_t c0 = 0; c0 < T; c0 += pass) {
         const int Tc = (int) (T - c0 < pass ? T - c0 : pass);
         const xblkb * xq = (const xblkb *) ws + c0 * nb;
         float * yc = y + c0 * y_cs;
         const float * rc = residual ? residual + c0 * r_cs : nullptr;
-#define MMQ4K_ROWS(NT) mm_q4k_mfma_rows_kernel<NT><<<grid64, 256, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
-#define MMQ4K_LAUNCH(NT) mm_q4k_mfma_kernel<NT><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs)
-        if (M >= rows_min) {
-            const int grid64 = (int) ((M + 63) / 64);
-            if (Tc <= 16) MMQ4K_ROWS(1); else if (Tc <= 32) MMQ4K_ROWS(2); else if (Tc <= 48) MMQ4K_ROWS(3); else MMQ4K_ROWS(4);
-        } else if (Tc <= 16) MMQ4K_LAUNCH(1); else if (Tc <= 32) MMQ4K_LAUNCH(2); else if (Tc <= 48) MMQ4K_LAUNCH(3); else MMQ4K_LAUNCH(4);
-#undef MMQ4K_ROWS
-#undef MMQ4K_LAUNCH
+        with_nt(Tc, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (M >= rows_min) mm_q4k_mfma_rows_kernel<NT><<<grid64, 256, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+            else mm_q4k_mfma_kernel<NT><<<grid, thr, 0, s>>>(w, row_bytes, nb, (int) M, Tc, xq, yc, y_cs, rc, r_cs);
+        });
     }
 }
 
-// ---- the batched mat-mul for BF16 / F16 weights: double-accumulating f64 MFMA tiles (hip_mm_float.h) ------------------------------------------
-#include "hip_mm_float.h"
+// ---- the float MFMA batched mat-muls: one chunk-walk kernel, three operand forms (hip_mm_tile.h); row converters for the BF16 / F16 forms ---------
+#include "hip_mm_cvt_rows.h"
+#include "hip_mm_tile.h"
+template <typename Op>
+static void launch_mm_mfma(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const void * x, int64_t x_cb,
+                           float * y, int64_t y_cs, const float * residual, int64_t r_cs) {
+    const dim3 grid((unsigned) ((M + 15) / 16), T > 64 ? 2 : 1);   // T > 64 (F32 only): columns 0..63 and 64..T - 1, the second half clamped inside its four tiles
+    with_nt(T, [&](auto nt) {
+        mm_mfma_kernel<Op, decltype(nt)::value><<<grid, 256, 0, s>>>(w, row_bytes, (int) (K / 32), (int) M, (int) T, (const char *) x, x_cb, y, y_cs, residual, r_cs);
+    });
+}
+// BF16 / F16 weights: the rows rounded to the weight's type into the workspace (prologue folded in), then f64 tiles or - float_acc - float-accumulating tiles
 size_t k_mm_f_batched_ws_size(int64_t K, int64_t T) { return (size_t) K * (size_t) T * 2; }
 bool k_mm_f_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) {
     return (wtype == GGML_TYPE_BF16 || wtype == GGML_TYPE_F16) && K % 32 == 0 && T >= 2 && T <= 64 && M >= 16;
 }
 template <int WT>
-static void mm_f_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                         uint16_t * xa, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
+static void launch_cvt_rows(hipStream_t s, int64_t K, int64_t T, const float * x, int64_t x_cs, uint16_t * xa, int prologue, const float * alpha, float eps) {
     const int64_t total8 = K * T / 8;
     if (prologue == MV_RMSNORM) rms_cvt_rows_kernel<WT><<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, xa);
     else if (prologue == MV_GATE_SILU) gate_cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
     else cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
-    const int nch = (int) (K / 32), grid = (int) ((M + 15) / 16);
-#define MMF_LAUNCH(NT) mm_f_mfma_kernel<WT, NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, xa, y, y_cs, residual, r_cs)
-    if (T <= 16) MMF_LAUNCH(1); else if (T <= 32) MMF_LAUNCH(2); else if (T <= 48) MMF_LAUNCH(3); else MMF_LAUNCH(4);
-#undef MMF_LAUNCH
+}
+template <int WT>
+static void mm_f_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
+                         uint16_t * xa, float * y, int64_t y_cs, const float * residual, int64_t r_cs, bool float_acc, int prologue, const float * alpha, float eps) {
+    launch_cvt_rows<WT>(s, K, T, x, x_cs, xa, prologue, alpha, eps);
+    if (float_acc) launch_mm_mfma<mm_op_f32acc<WT>>(s, w, row_bytes, K, M, T, xa, K * 2, y, y_cs, residual, r_cs);
+    else launch_mm_mfma<mm_op_f64<WT>>(s, w, row_bytes, K, M, T, xa, K * 2, y, y_cs, residual, r_cs);
 }
 void k_mm_f_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                    void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
-    if (wtype == GGML_TYPE_BF16) mm_f_batched<GGML_TYPE_BF16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
-    else mm_f_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
+                    void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, bool float_acc, int prologue, const float * alpha, float eps) {
+    if (wtype == GGML_TYPE_BF16) mm_f_batched<GGML_TYPE_BF16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, float_acc, prologue, alpha, eps);
+    else mm_f_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, float_acc, prologue, alpha, eps);
 }
-
-// ---- the same product with float sums: v_mfma_f32_16x16x32_bf16 / _f16 tiles (hip_mm_float_acc.h); the row converters and the workspace are shared ----
-#include "hip_mm_float_acc.h"
-bool k_mm_f32acc_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) { return k_mm_f_batched_supported(wtype, K, M, T); }
-template <int WT>
-static void mm_f32acc_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                              uint16_t * xa, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
-    const int64_t total8 = K * T / 8;
-    if (prologue == MV_RMSNORM) rms_cvt_rows_kernel<WT><<<(int) T, 256, 0, s>>>(x, x_cs, alpha, eps, (int) K, xa);
-    else if (prologue == MV_GATE_SILU) gate_cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
-    else cvt_rows_kernel<WT><<<(int) ((total8 + 255) / 256), 256, 0, s>>>(x, x_cs, (int) K, total8, xa);
-    const int nch = (int) (K / 32), grid = (int) ((M + 15) / 16);
-#define MMA_LAUNCH(NT) mm_f32acc_mfma_kernel<WT, NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, xa, y, y_cs, residual, r_cs)
-    if (T <= 16) MMA_LAUNCH(1); else if (T <= 32) MMA_LAUNCH(2); else if (T <= 48) MMA_LAUNCH(3); else MMA_LAUNCH(4);
-#undef MMA_LAUNCH
-}
-void k_mm_f32acc_batched(hipStream_t s, int wtype, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
-                         void * ws, float * y, int64_t y_cs, const float * residual, int64_t r_cs, int prologue, const float * alpha, float eps) {
-    if (wtype == GGML_TYPE_BF16) mm_f32acc_batched<GGML_TYPE_BF16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
-    else mm_f32acc_batched<GGML_TYPE_F16>(s, w, row_bytes, K, M, T, x, x_cs, (uint16_t *) ws, y, y_cs, residual, r_cs, prologue, alpha, eps);
-}
-
-// ---- the batched mat-mul for F32 weights: exact products, double sums on f64 MFMA tiles (hip_mm_f32.h); no converter pass, no workspace -----------
-#include "hip_mm_f32.h"
+// F32 weights: the activations as they are - no converter pass, no workspace
 bool k_mm_f32_batched_supported(int wtype, int64_t K, int64_t M, int64_t T) { return wtype == GGML_TYPE_F32 && K % 32 == 0 && M >= 16 && T >= 2 && T <= 128; }
 void k_mm_f32_batched(hipStream_t s, const char * w, int64_t row_bytes, int64_t K, int64_t M, int64_t T, const float * x, int64_t x_cs,
                       float * y, int64_t y_cs, const float * residual, int64_t r_cs) {
-    const int nch = (int) (K / 32);
-    const dim3 grid((unsigned) ((M + 15) / 16), T > 64 ? 2 : 1);   // T > 64: columns 0..63 and 64..T - 1, the second half clamped inside its four tiles
-#define MM32_LAUNCH(NT) mm_f32_mfma_kernel<NT><<<grid, 256, 0, s>>>(w, row_bytes, nch, (int) M, (int) T, x, x_cs, y, y_cs, residual, r_cs)
-    if (T <= 16) MM32_LAUNCH(1); else if (T <= 32) MM32_LAUNCH(2); else if (T <= 48) MM32_LAUNCH(3); else MM32_LAUNCH(4);
-#undef MM32_LAUNCH
+    launch_mm_mfma<mm_op_f64_f32>(s, w, row_bytes, K, M, T, x, x_cs * 4, y, y_cs, residual, r_cs);
 }
 
 static mv_profile * g_mv_profile = nullptr;

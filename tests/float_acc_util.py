@@ -1,10 +1,10 @@
-"""Helpers for the float-accumulating BF16 / F16 mat-mul (ggml_backend_mi355x_set_float_accumulate, k_mm_f32acc_batched): a graph runner that sets
+"""Helpers for the float-accumulating BF16 / F16 mat-mul (ggml_backend_mi355x_set_float_accumulate, k_mm_f_batched with float_acc set): a graph runner that sets
 the mode on the handle before the compute, integer operands, and a CPU float32 emulation of the kernel's summation order."""
 import numpy as np
 
 import ggml_util as gu
 
-MMA_U = 4        # hip_mm_float_acc.h: chunks of 32 k dealt in groups of four round-robin to four waves
+MMA_U = 4        # mm_op_f32acc::U (hip_mm_tile.h): chunks of 32 k dealt in groups of four round-robin to four waves
 WAVES = 4
 
 

@@ -8,7 +8,7 @@ FRAMES frames of "on", wall clock around work that ends in the call's own read-b
 the medians, off / on, the launches of the plan and the f64-MFMA linears in it, and the max-abs difference of the two models' last outputs.
     python tests/microbench/f32_matrix_bench.py [--out FILE]
     python tests/microbench/f32_matrix_bench.py --trace decode|encode B     (a kernel-trace run of its own: plain launches, TRACE_FRAMES frames of
-                                                                             "off", then of "on" - mul_mat_kernel against mm_f32_mfma_kernel)"""
+                                                                             "off", then of "on" - mul_mat_kernel against mm_mfma_kernel<mm_op_f64_f32, NT>)"""
 import ctypes as C
 import json
 import os

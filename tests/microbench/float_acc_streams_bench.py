@@ -1,4 +1,4 @@
-"""float_streams_bench.py with one more setting: `fast` = MI355X_MMF=2, the float-accumulating BF16 mat-mul (k_mm_f32acc_batched) as the
+"""float_streams_bench.py with one more setting: `fast` = MI355X_MMF=2, the float-accumulating BF16 mat-mul (k_mm_f_batched with float_acc set) as the
 starting mode of the child's handle, alternated with `default` (the f64-MFMA mat-mul) on the same box. Method, children, time limits and output are
 float_streams_bench.py's own (moshika BF16, lockstep streams, context 750, one fresh child per line, 5 warm-up frames + 3 rounds of 40 frames - 10 at
 B = 64 - median round; nothing is started after a failure). A `fast` line reports float_batched_mms_in_temporal_plan = 0 (that counter keeps counting

@@ -1,7 +1,7 @@
 // Issue rate of v_mfma_f32_16x16x32_bf16 on gfx950: a bare loop of it (four independent accumulator chains per wave, no memory traffic) on every CU.
 // Prints TFLOP/s (2 * 16 * 16 * 32 FLOP per instruction) and ns per instruction per SIMD - both measured - and that time in cycles of the device's
 // REPORTED maximum clock (hipDeviceProp_t::clockRate; the clock the run sustained is not read, so the cycle figure is an upper bound).
-// The companion of mfma_f64_rate.hip for the float-accumulating mat-mul (hip_mm_float_acc.h).
+// The companion of mfma_f64_rate.hip for the float-accumulating mat-mul (mm_op_f32acc in hip_mm_tile.h).
 // Build: hipcc --offload-arch=gfx950 -O2 mfma_f32_bf16_rate.hip -o mfma_f32_bf16_rate
 #include <hip/hip_runtime.h>
 #include <stdio.h>

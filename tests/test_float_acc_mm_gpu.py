@@ -1,4 +1,4 @@
-"""The float-accumulating batched mat-mul for BF16 / F16 weights (k_mm_f32acc_batched: v_mfma_f32_16x16x32_bf16 / _f16 tiles, 2 .. 64 activation rows),
+"""The float-accumulating batched mat-mul for BF16 / F16 weights (k_mm_f_batched with float_acc set: v_mfma_f32_16x16x32_bf16 / _f16 tiles, 2 .. 64 activation rows),
 opted into with ggml_backend_mi355x_set_float_accumulate(backend, 1) or MI355X_MMF=2, through the C-ABI. Shapes, operands and graphs are those of
 tests/test_float_batched_mm_gpu.py (imported, not changed).
 

@@ -1,5 +1,5 @@
 """B-column models with BF16 / F16 linears and float_accumulate = 1 (include/moshi_hot.h): their multi-column products run on the float-accumulating
-mat-mul (k_mm_f32acc_batched). Such a model is no longer bit-comparable with the oracle; it stays bit-reproducible and column-independent.
+mat-mul (k_mm_f_batched with float_acc set). Such a model is no longer bit-comparable with the oracle; it stays bit-reproducible and column-independent.
 
 (f) the plans: 4 x num_layers + 1 float-accumulating mat-muls in the Temporal plan, none on the f64 kernel, as many launches as with the field 0.
 (g) one conversation gets the same bits in slot 0 of B = 3, in slot 2 of B = 3 beside other neighbours and in slot 20 of B = 33; a live neighbour is
