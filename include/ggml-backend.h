@@ -141,6 +141,7 @@ struct ggml_mi355x_stats {
     int64_t state_copy_jobs_in_last_plan;       // ... and the cpy nodes (jobs) they hold
     int64_t f32_matrix_mms_in_last_plan;        // k_mm_f32_batched launches of the last plan (F32 weights against 2..128 activation rows on f64 MFMA tiles, set_f32_matrix)
     int64_t convtr_matrix_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan that are ONE k_convtr_cols_mfma launch (f64 MFMA tiles, no workspace; bit 1 of set_f32_matrix) - a subset of convtr_column_groups_in_last_plan
+    int64_t conv_matrix_groups_in_last_plan;    // B-column convolution groups of the last plan that are ONE k_conv_cols_mfma launch ([elu] [concat + tail copy] im2col, product, bias [residual] on F16 MFMA tiles; bit 2 of set_f32_matrix)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
 // accumulated HIP-event timings of the dominant kernel (Q4_K mat-vec), collected while flag 8 is set
@@ -203,7 +204,13 @@ GGML_API void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t backend, i
 // and the bias - the same trade (nearer to the real value, not bit-comparable with the CPU product, bit-reproducible and column-independent), and
 // the plan reserves no partials. Taken by dense F32 weights [K, OC, IC] with K == 2 x stride, lcm(K, 16) of 16, 48 or 80, IC % 32 == 0 and OC K % 4 == 0 whose
 // slab of lcm(K, 16) taps fits the LDS; F16 weights, other shapes and the single-column form keep the pair. 3 sets both bits; MI355X_MMF32=2 / 3
-// likewise. Bits above bit 1 are ignored.
+// likewise. Bit 2 (value 4) sends every codec convolution group at B >= 2 columns (the SEANet convolutions and RVQ projections of decoder and encoder
+// slots) to ONE launch each: the elu in front, concat(prev, x), the copy of the new tail into prev, the F16 im2col, the product, the bias and a
+// residual block's add run as an implicit-im2col GEMM on F16 MFMA tiles that writes neither the concat nor the im2col tensor. Each output is one float
+// sum over all of K in ascending chunks of 32 - as near to the real value as the default tile kernel, NOT its bits nor those of the double-summing dot
+// forms, bit-reproducible and column-independent. Taken by dense F16 weights [Kw, IC, OC] against dense F32 x, prev and out with dilation 1 and no
+// padding; F32 weights, the single-column form and anything else keep today's launches. 4..7 combine it with the bits below; MI355X_MMF32=4..7
+// likewise. Bits above bit 2 are ignored.
 GGML_API void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t backend, int on);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);

@@ -95,7 +95,9 @@ struct moshi_hot_config {
     // backend. (Like persona_columns it sits in front of float_accumulate.)
     // The value is a set of bits, passed to ggml_backend_mi355x_set_f32_matrix as it is: 1 the F32 linears (above); 2 the four streaming transposed
     // convolutions of moshi_hot_mimi_decode_slots as one f64-MFMA launch each, without the workspace of double partials (the same trade: exact
-    // products, one double sum per tap, not bit-comparable with the CPU reference, column-independent); 3 both.
+    // products, one double sum per tap, not bit-comparable with the CPU reference, column-independent); 3 both;
+    // 4 every codec convolution group of moshi_hot_mimi_decode_slots / _encode_slots (elu, concat with the carried tail, tail copy, im2col, product,
+    // bias, residual add) as one F16-MFMA launch with one float sum over K (not the bits of the default launches, column-independent); 5..7 combine.
     int32_t f32_matrix;
     // 1: moshi_hot_create / _create_streams / _create_slots / _create_from_gguf switch the handle the model is created on (and its codec sibling stream,
     // if one is made) to the float-accumulating mat-mul, ggml_backend_mi355x_set_float_accumulate(backend, 1): every B-column product of BF16 / F16

@@ -67,7 +67,8 @@ class Stats(C.Structure):
                                          "convtr_column_groups_in_last_plan", "codec_attn_launches_in_last_plan",
                                          "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan",
                                          "state_copy_launches_in_last_plan", "state_copy_jobs_in_last_plan",
-                                         "f32_matrix_mms_in_last_plan", "convtr_matrix_groups_in_last_plan")]
+                                         "f32_matrix_mms_in_last_plan", "convtr_matrix_groups_in_last_plan",
+                                         "conv_matrix_groups_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

@@ -59,7 +59,7 @@ struct hip_ctx {
     int flags = 0;
     int max_columns = 16;        // ggml_backend_mi355x_set_max_columns: the widest B-column sampler graph planned as one launch
     int float_acc = 0;           // ggml_backend_mi355x_set_float_accumulate: 1 = BF16 / F16 weights against 2..64 rows take the float-accumulating mat-mul
-    int f32_matrix = 0;          // ggml_backend_mi355x_set_f32_matrix, bits: 1 = F32 weights against 2..128 rows take the f64-MFMA mat-mul (k_mm_f32_batched), 2 = B-column transposed convolutions take k_convtr_cols_mfma
+    int f32_matrix = 0;          // ggml_backend_mi355x_set_f32_matrix, bits: 1 = F32 weights against 2..128 rows take the f64-MFMA mat-mul (k_mm_f32_batched), 2 = B-column transposed convolutions take k_convtr_cols_mfma, 4 = B-column convolution groups take k_conv_cols_mfma
     bool no_capture = false;     // ggml_backend_mi355x_set_capture(.., 0): plans of repeated graphs are reused but not captured into hipGraphs
     ggml_mi355x_stats stats = {};
     // pooled allocations: size class -> free pointers
@@ -343,7 +343,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_conv_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -546,9 +546,10 @@ static bool float_batched_ok(const ggml_tensor * w, int64_t T) {
     return k_mm_f_batched_supported(w->type, w->ne[0], w->ne[1], T);
 }
 // its row converters read the activation rows (and alpha) as float4
-// MI355X_MMF32=1 / 2 / 3: the starting value of set_f32_matrix on every fresh handle - bit 0 the f64-MFMA mat-mul for F32 weights against 2..128 activation
-// rows (k_mm_f32_batched), bit 1 the one-launch f64-MFMA transposed convolution at B columns (k_convtr_cols_mfma)
-static int mmf32_env() { static const int v = [] { const char * e = getenv("MI355X_MMF32"); const int m = e ? atoi(e) : 0; return m >= 0 && m <= 3 ? m : 0; }(); return v; }
+// MI355X_MMF32=1 .. 7: the starting value of set_f32_matrix on every fresh handle - bit 0 the f64-MFMA mat-mul for F32 weights against 2..128 activation
+// rows (k_mm_f32_batched), bit 1 the one-launch f64-MFMA transposed convolution at B columns (k_convtr_cols_mfma), bit 2 the
+// one-launch implicit-im2col F16-MFMA convolution group at B columns (k_conv_cols_mfma)
+static int mmf32_env() { static const int v = [] { const char * e = getenv("MI355X_MMF32"); const int m = e ? atoi(e) : 0; return m >= 0 && m <= 7 ? m : 0; }(); return v; }
 static bool aligned16(const void * p) { return p != nullptr && (uintptr_t) p % 16 == 0; }
 
 static bool fill_matvec_base(mv_args & a, const ggml_tensor * mm) {
@@ -1852,10 +1853,74 @@ static bool match_conv(const analysis & an, int pos, step_group & grp, emitter &
     return true;
 }
 
+// D''. the same group widened to ONE launch (bit 2 of set_f32_matrix, k_conv_cols_mfma): besides D' it takes the im2col node, the concat(prev, x) in front
+//      of it with its side copy cpy(view of the last TP samples, prev) (streaming_conv), an elu whose only consumer is that concat (or the im2col of a
+//      stateless convolution), and a trailing add(x_in, out) (resnet_block) as a residual epilogue. None of the tensors in between is written or read.
+//      h / out / bias: what match_conv_columns has matched. Declines - D' then stands - when a member is taken, a tensor is not dense, a tap would lie
+//      outside concat(prev, x), or something the launch writes (out, prev) overlaps something it reads.
+static bool widen_conv_columns(const analysis & an, int pos, const conv_head & h, const ggml_tensor * out, const float * bias, step_group & grp, emitter & em) {
+    const ggml_tensor * im = h.im, * w = h.w, * mm = an.g->nodes[pos], * vw = sole_consumer(an, mm);
+    const int s0 = im->op_params[0], p0 = im->op_params[2], d0 = im->op_params[4];
+    const int64_t Kw = w->ne[0], IC = w->ne[1], OC = w->ne[2], OW = im->ne[1], B = im->ne[2];
+    if (p0 != 0 || d0 != 1 || im->op_params[6] != 0 || pos_of(an, im) < 0) return false;
+    std::vector<int> members = { pos_of(an, im), pos_of(an, h.ra), pos_of(an, h.rw), pos, pos_of(an, vw), pos_of(an, out) };
+    const ggml_tensor * cat = im->src[1], * prev = nullptr, * xin = cat;
+    int64_t TP = 0;
+    if (cat->op == GGML_OP_CONCAT && cat->op_params[0] == 0 && cat->src[0]->op == GGML_OP_NONE && !cat->view_src) {
+        prev = cat->src[0]; xin = cat->src[1];
+        TP = prev->ne[0];
+        if (prev->type != GGML_TYPE_F32 || !ggml_is_contiguous(prev) || !prev->data || prev->ne[1] != IC || prev->ne[2] != B || prev->ne[3] != 1 || uses_of(an, cat) != 2) return false;
+        // the tail update: cpy(view(cat, last TP), prev), a side node
+        const ggml_tensor * tv = nullptr, * tc = nullptr;
+        for (int i = pos_of(an, cat) + 1; i < pos; i++) {
+            const ggml_tensor * n = an.g->nodes[i];
+            if (n->op == GGML_OP_VIEW && n->src[0] == cat) tv = n;
+            if (n->op == GGML_OP_CPY && tv && n->src[0] == tv && n->src[1] == prev) tc = n;
+        }
+        if (!tv || !tc || uses_of(an, tv) != 1 || uses_of(an, tc) != 0) return false;
+        if (tv->ne[0] != TP || tv->ne[1] != IC || tv->ne[2] != B || tv->nb[1] != cat->nb[1] || tv->nb[2] != cat->nb[2] ||
+            (const char *) tv->data - (const char *) cat->data != (int64_t) (cat->ne[0] - TP) * 4) return false;
+        members.push_back(pos_of(an, cat)); members.push_back(pos_of(an, tv)); members.push_back(pos_of(an, tc));
+    }
+    const int pre_elu = peel_elu(an, xin, 1, members);
+    if (xin->type != GGML_TYPE_F32 || xin->nb[0] % 4 || xin->nb[1] % 4 || xin->nb[2] % 4 || !xin->data || xin->ne[1] != IC || xin->ne[2] != B || xin->ne[3] != 1) return false;
+    const int64_t Lx = xin->ne[0];
+    if (!k_conv_cols_mfma_supported(IC, OC, Kw, s0, Lx, TP, OW, B)) return false;
+    // resnet_block's add(x_in, out): product + bias first, then x_in + that - the floats the add node adds
+    const ggml_tensor * resid = nullptr, * nx = sole_consumer(an, out);
+    if (nx && nx->op == GGML_OP_ADD && !nx->view_src && nx->src[1] == out && nx->src[0] != out && nx->src[0]->type == GGML_TYPE_F32 && nx->type == GGML_TYPE_F32 &&
+        ggml_are_same_shape(nx->src[0], out) && ggml_is_contiguous(nx->src[0]) && ggml_is_contiguous(nx) && nx->src[0]->data && nx->data) {
+        resid = nx->src[0]; out = nx; members.push_back(pos_of(an, out));
+    }
+    for (int m : members) if (m < 0 || an.skip[(size_t) m]) return false;
+    auto range = [](const ggml_tensor * t) { return byte_range{ (const char *) t->data, (const char *) t->data + ggml_nbytes(t) }; };
+    std::vector<byte_range> reads = { range(xin), range(w) }, writes = { range(out) };
+    if (resid) reads.push_back(range(resid));
+    if (bias) reads.push_back(byte_range{ (const char *) bias, (const char *) bias + OC * 4 });
+    if (prev) writes.push_back(range(prev));
+    for (const byte_range & wr : writes) for (const byte_range & rd : reads) if (wr.overlaps(rd)) return false;
+    if (prev && writes[0].overlaps(writes[1])) return false;
+    unsigned * counter = nullptr;
+    if (prev) {
+        counter = (unsigned *) em.ws(256);
+        HIP_CHECK(hipMemsetAsync(counter, 0, 256, em.c->stream));   // stream-ordered behind the block's previous user (plans are built outside capture)
+    }
+    float * op = (float *) out->data, * pv = prev ? (float *) prev->data : nullptr;
+    const float * rp = resid ? (const float *) resid->data : nullptr, * xp = (const float *) xin->data;
+    const void * wp = w->data;
+    const int64_t xs0 = (int64_t) xin->nb[0] / 4, xs1 = (int64_t) xin->nb[1] / 4, xs2 = (int64_t) xin->nb[2] / 4;
+    const int ICn = (int) IC, OCn = (int) OC, Kwn = (int) Kw, Lxn = (int) Lx, TPn = (int) TP, OWn = (int) OW, Bn = (int) B;
+    grp.steps.clear();
+    grp.steps.push_back([=](hipStream_t s) { k_conv_cols_mfma(s, op, pv, bias, rp, wp, xp, xs0, xs1, xs2, counter, ICn, OCn, Kwn, s0, Lxn, TPn, OWn, Bn, pre_elu); });
+    grp.members = members;
+    grp.emit_pos = pos_of(an, out);
+    return true;
+}
+
 // D'. a codec convolution at B > 1 columns (decoder slots, moshi_hot.cpp conv_1d_bias): im2col [K, OW, B] F16 -> reshape -> mul_mat(., reshape(w)) ->
 //     the strided [OW, OC, B] view of the [OW * B, OC] product -> + bias (or cont). The im2col node keeps its own launch (it carries the batch dimension
 //     as it is); the product, the view and the add / cont become one launch that stores in the final layout (k_conv_cols).
-static bool match_conv_columns(const analysis & an, int pos, step_group & grp) {
+static bool match_conv_columns(const analysis & an, int pos, step_group & grp, emitter & em, bool & matrix) {
     const ggml_tensor * mm = an.g->nodes[pos];
     conv_head h;
     if (!match_conv_head(an, mm, h) || mm->type != GGML_TYPE_F32 || uses_of(an, h.rw) != 1 || !ggml_is_contiguous(h.im)) return false;
@@ -1873,6 +1938,7 @@ static bool match_conv_columns(const analysis & an, int pos, step_group & grp) {
     else if (out->op != GGML_OP_CONT) return false;
     if (out->type != GGML_TYPE_F32 || !ggml_is_contiguous(out) || !out->data || out->ne[0] != OW || out->ne[1] != OC || out->ne[2] != B || out->ne[3] != 1) return false;
     if (K > INT32_MAX || OW * B > INT32_MAX || OC > INT32_MAX) return false;
+    if ((em.c->f32_matrix & 4) && widen_conv_columns(an, pos, h, out, bias, grp, em)) { matrix = true; return true; }
     grp.members = { pos_of(an, ra), pos_of(an, rw), pos, pos_of(an, vw), pos_of(an, out) };
     for (int m : grp.members) if (m < 0 || an.skip[(size_t) m]) return false;
     float * dst = (float *) out->data; const void * ap = im->data, * wp = w->data;
@@ -2653,9 +2719,9 @@ static void pass_codec_convs(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i]) continue;
         step_group grp;
-        bool convtr_columns = false, convtr_matrix = false, vq_columns = false;
+        bool convtr_columns = false, convtr_matrix = false, conv_matrix = false, vq_columns = false;
         const enum ggml_op op = pl.g->nodes[i]->op;
-        if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em) && !match_conv_columns(pl.an, i, grp)) continue; }
+        if (op == GGML_OP_MUL_MAT) { if (!match_conv(pl.an, i, grp, pl.em) && !match_conv_columns(pl.an, i, grp, pl.em, conv_matrix)) continue; }
         else if (op == GGML_OP_CONV_TRANSPOSE_1D) {
             if (match_convtr_columns(pl.an, i, grp, pl.em, convtr_matrix)) convtr_columns = true;
             else if (!match_convtr(pl.an, i, grp, pl.em)) continue;
@@ -2671,6 +2737,7 @@ static void pass_codec_convs(planner & pl) {
         if (!claim_group(pl, grp)) continue;
         if (convtr_columns) pl.p->n_convtr_column_groups++;
         if (convtr_matrix) pl.p->n_convtr_matrix_groups++;
+        if (conv_matrix) pl.p->n_conv_matrix_groups++;
         if (vq_columns) pl.p->n_vq_column_levels++;
         for (auto & f : grp.steps) {
             pl.at_pos[grp.emit_pos].push_back(f);
@@ -3377,7 +3444,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.cross_block_launches_in_last_plan = p->n_cross_block_launches; c->stats.cross_block_jobs_in_last_plan = p->n_cross_block_jobs;
     c->stats.float_batched_mms_in_last_plan = p->n_float_batched_mms;
     c->stats.float_acc_mms_in_last_plan = p->n_float_acc_mms;
-    c->stats.f32_matrix_mms_in_last_plan = p->n_f32_matrix_mms; c->stats.convtr_matrix_groups_in_last_plan = p->n_convtr_matrix_groups;
+    c->stats.f32_matrix_mms_in_last_plan = p->n_f32_matrix_mms; c->stats.convtr_matrix_groups_in_last_plan = p->n_convtr_matrix_groups; c->stats.conv_matrix_groups_in_last_plan = p->n_conv_matrix_groups;
     c->stats.pass_input_launches_in_last_plan = p->n_pass_input_launches; c->stats.pass_input_rows_in_last_plan = p->n_pass_input_rows;
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
@@ -3604,7 +3671,7 @@ extern "C" void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t b, int m
 extern "C" void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t b, int on) {
     if (!b || b->iface.get_name != hip_backend_name) return;   // any other backend: nothing to do
     hip_ctx * c = (hip_ctx *) b->context;
-    on &= 3;   // bit 0: the F32 linears, bit 1: the B-column transposed convolutions
+    on &= 7;   // bit 0: the F32 linears, bit 1: the B-column transposed convolutions, bit 2: the B-column convolution groups
     if (on == c->f32_matrix) return;
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
     for (auto & kv : c->plans) plan_free(c, kv.second);   // the plans hold the other kernel's launches

@@ -85,6 +85,13 @@ int  k_conv_transpose_1d_partial(hipStream_t s, tdesc w, tdesc x, void * ws, int
 // a codec convolution at B columns (decoder slots): dst F32 [OW, OC, B] dense <- the F16 im2col rows [K, OW * B] (column-major positions) times the F16
 // kernel [K, OC], + bias[oc] (may be NULL). The order of an output's sums depends on (K, OW, OC) alone
 void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w, const float * bias, int K, int OW, int OC, int B);
+// the whole B-column group around k_conv_cols - [elu ->] [concat(prev, .) + the tail copy into prev ->] im2col -> product -> + bias [-> resid + .] - as
+// ONE launch of 16x16x32 F16 MFMA tiles that builds its im2col rows in LDS, opt-in (bit 2 of ggml_backend_mi355x_set_f32_matrix): one float sum over
+// all of K in ascending chunks of 32. NOT k_conv_cols' bits; a column's bits depend on the layer and its own values only. F16 w [Kw, IC, OC],
+// prev [TP, IC, B] (TP = 0: none), resid / out [OW, OC, B], all dense; x [Lx, IC, B] through element strides (a transposed view); counter: 4 zeroed bytes of the plan's own (TP > 0)
+bool k_conv_cols_mfma_supported(int64_t IC, int64_t OC, int64_t Kw, int s0, int64_t Lx, int64_t TP, int64_t OW, int64_t B);
+void k_conv_cols_mfma(hipStream_t s, float * out, float * prev, const float * bias, const float * resid, const void * w, const float * x, int64_t xs0, int64_t xs1, int64_t xs2, unsigned * counter,
+                      int IC, int OC, int Kw, int s0, int Lx, int TP, int OW, int B, int pre_elu);
 size_t k_convtr_cols_ws_size(const struct ggml_tensor * w, int64_t L, int64_t B);
 void k_convtr_cols(hipStream_t s, tdesc out, float * prev, const float * bias, tdesc w, tdesc x, int s0, int pre_elu, void * ws);
 // the same as ONE launch of 16x16x4 f64 MFMA tiles without a workspace, opt-in (bit 1 of ggml_backend_mi355x_set_f32_matrix): exact products, one

@@ -1485,6 +1485,28 @@ void k_conv_cols(hipStream_t s, float * dst, const void * im2col, const void * w
     conv_cols_dot_kernel<<<nblocks(total, 4), 256, 0, s>>>(dst, d_nb1, d_nb2, (const uint16_t *) im2col, (const uint16_t *) w, bias, K, OW, M, total);
 }
 
+// ---- the whole group - elu, concat, tail copy, im2col, product, bias, residual - as ONE launch of F16 MFMA tiles (hip_conv_mfma.h); opt-in, not k_conv_cols' bits ----
+#include "hip_conv_mfma.h"
+bool k_conv_cols_mfma_supported(int64_t IC, int64_t OC, int64_t Kw, int s0, int64_t Lx, int64_t TP, int64_t OW, int64_t B) {
+    if (IC < 1 || OC < 1 || Kw < 1 || s0 < 1 || Lx < 1 || TP < 0 || OW < 1 || B < 2) return false;
+    if (IC * Kw > (1 << 24) || B * OW > (1 << 28) || B * IC * (Lx + TP) > INT32_MAX || OC > (1 << 19)) return false;
+    return (OW - 1) * s0 + Kw <= TP + Lx;   // every tap of every position lies inside concat(prev, x): nothing is padded
+}
+void k_conv_cols_mfma(hipStream_t s, float * out, float * prev, const float * bias, const float * resid, const void * w, const float * x, int64_t xs0, int64_t xs1, int64_t xs2, unsigned * counter,
+                      int IC, int OC, int Kw, int s0, int Lx, int TP, int OW, int B, int pre_elu) {
+    GGML_ASSERT(k_conv_cols_mfma_supported(IC, OC, Kw, s0, Lx, TP, OW, B) && (TP == 0 || (prev && counter)));
+    const int64_t P = (int64_t) B * OW;
+    const int nt = (int) std::min<int64_t>(4, (P + 15) / 16), runs = (int) ((P + 16 * nt - 1) / (16 * nt)), n_oct = (OC + 15) / 16;
+    int ts = 4 * CVM_TW;
+    while (ts > 1 && (int64_t) runs * ((n_oct + ts - 1) / ts) < CVM_TARGET_WGS) ts /= 2;
+    const conv_mfma_args a = { x, prev, (const uint16_t *) w, bias, resid, out, counter, xs0, xs1, xs2, IC, OC, Kw, s0, Lx, TP, OW, B, ts, pre_elu };
+    const dim3 grid((unsigned) runs, (unsigned) ((n_oct + ts - 1) / ts));
+    if (nt == 1) conv_cols_implicit_mfma_kernel<1><<<grid, 256, 0, s>>>(a);
+    else if (nt == 2) conv_cols_implicit_mfma_kernel<2><<<grid, 256, 0, s>>>(a);
+    else if (nt == 3) conv_cols_implicit_mfma_kernel<3><<<grid, 256, 0, s>>>(a);
+    else conv_cols_implicit_mfma_kernel<4><<<grid, 256, 0, s>>>(a);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // batched small uploads
 // ---------------------------------------------------------------------------------------------------
