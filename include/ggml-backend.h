@@ -141,6 +141,7 @@ struct ggml_mi355x_stats {
     int64_t state_copy_jobs_in_last_plan;       // ... and the cpy nodes (jobs) they hold
     int64_t f32_matrix_mms_in_last_plan;        // k_mm_f32_batched launches of the last plan (F32 weights against 2..128 activation rows on f64 MFMA tiles, set_f32_matrix)
     int64_t convtr_matrix_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan that are ONE k_convtr_cols_mfma launch (f64 MFMA tiles, no workspace; bit 1 of set_f32_matrix) - a subset of convtr_column_groups_in_last_plan
+    int64_t q8_attention_blocks_in_last_plan;   // k_attn_streams_q8 launches of the last plan (B-column self-attention blocks over Q8_0 K / V rings, moshi_hot_config::kv_q8; in front of conv_matrix_groups_in_last_plan, which tests/test_conv_matrix_cpu.py pins as the last field)
     int64_t conv_matrix_groups_in_last_plan;    // B-column convolution groups of the last plan that are ONE k_conv_cols_mfma launch ([elu] [concat + tail copy] im2col, product, bias [residual] on F16 MFMA tiles; bit 2 of set_f32_matrix)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);

@@ -86,6 +86,18 @@ struct moshi_hot_config {
     // shape of a B > 1 model ("PersonaPlex streams and slots" below). 1 without personaplex = 1, or beside anything the moshika shape excludes: NULL.
     // Ignored by a single-stream model. (It sits in front of float_accumulate, which tests/test_float_acc_streams_gpu.py pins as the struct's last field.)
     int32_t persona_columns;
+    // moshi_hot_create_streams / moshi_hot_create_slots with n_streams >= 2, moshika, stt and tts shapes: 1 = the Temporal transformer's K / V rings are
+    // GGML_TYPE_Q8_0 [D, C, H, B] (llama.cpp's `-ctk q8_0 -ctv q8_0`): 34 bytes per 32 values, 136 instead of 256 bytes per 128-wide head row, 0.53 of
+    // the ring bytes of a column (0.83 GB instead of 1.57 GB at moshika's widths and context 3000), plus two F32 [D, C, H, B] work tensors shared by
+    // all layers that only the plain-node path touches. The Depth rings stay BF16, the cross-attention K / V stay F32. The attention graph of such a
+    // layer is set_rows into the Q8_0 rings, mul_mat of the Q8_0 ring against q, soft_max, get_rows of the V ring (its dequantised rows), the P x V
+    // mul_mat: ggml's arithmetic for those nodes is the contract and the MI355X backend runs the block as one k_attn_streams_q8 launch.
+    // Not bit-comparable with a kv_q8 = 0 model (k / v are quantised per block of 32 instead of rounded to BF16; p is not rounded).
+    // NULL with 1: n_streams == 1, moshi_hot_create, the codec-slots and encoder-slots creators, head widths that are no multiple of 32, persona_columns.
+    // -1 on such a model, nothing changed: moshi_hot_slots_prefill / _long, moshi_hot_slots_replay, moshi_hot_slots_persona, moshi_hot_slot_fork / _save /
+    // _load and their _full variants (batched passes and snapshots over Q8_0 rings are not built yet).
+    // (It sits in front of f32_matrix: tests pin f32_matrix and float_accumulate as the struct's last two fields.)
+    int32_t kv_q8;
     // 1: the create calls switch the handle the model is created on to the f64-MFMA mat-mul for F32 weights, ggml_backend_mi355x_set_f32_matrix(backend, 1):
     // the F32 linears of the codec transformers of moshi_hot_create_codec_slots / moshi_hot_mimi_decode_slots and moshi_hot_create_encoder_slots /
     // moshi_hot_mimi_encode_slots ([512, 2 B] activations in the decoder) run as one matrix-core launch each instead of a wave per output. Every product
@@ -508,6 +520,9 @@ GGML_API int     moshi_hot_set_host_ring(moshi_hot_model_t * m, const int32_t * 
 // the K (kv = 0) / V (kv = 1) ring of one layer as its bytes (BF16 [D, C, H]), read out (write = 0) or overwritten (write = 1): parity runs that restart every
 // frame from another executor's state. Returns the ring's size in bytes (-1: no such ring); buf may be NULL to ask for the size. which: 0 Temporal, 1 Depth.
 GGML_API int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int layer, int kv, void * buf, int64_t nbytes, int write);
+// the bytes of the Temporal transformer's K / V rings over all layers and columns, on a model of any kind: 2 x num_layers x dim x context x B BF16 values,
+// or 34 / 64 of that with kv_q8 = 1 (Q8_0 blocks of 34 bytes per 32 values)
+GGML_API int64_t moshi_hot_kv_bytes(moshi_hot_model_t * m);
 // Parity probe: ONE transformer layer (moshi_streaming_transformer_layer, transformer.h:910-1039) of the Temporal (which = 0) or Depth
 // (which = 1, with weight set `weight_set`) stack on the scratch context, fed x_in F32[dim] at stream position `offset` (mask row, RoPE
 // phase and ring slot as transformer.h:1182-1215 computes them), over the model's own weights and KV ring of that layer (the new K / V

@@ -68,7 +68,7 @@ class Stats(C.Structure):
                                          "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan",
                                          "state_copy_launches_in_last_plan", "state_copy_jobs_in_last_plan",
                                          "f32_matrix_mms_in_last_plan", "convtr_matrix_groups_in_last_plan",
-                                         "conv_matrix_groups_in_last_plan")]
+                                         "q8_attention_blocks_in_last_plan", "conv_matrix_groups_in_last_plan")]
 
 
 class KernelProfile(C.Structure):

@@ -343,7 +343,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_conv_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_conv_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0, n_q8_attn_blocks = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -900,7 +900,8 @@ static bool match_norm_affine(const analysis & an, int pos, norm_affine_group & 
 //                     [D/2, T, 1, B] - one launch of H x T x B workgroups, k_attn_codec_slots (match_attention_codec_slots; the codec transformers' shape only)
 //      Refused today: several rows of several columns at once in any other shape, and a copy into rows from anything but a ring column.
 struct attn_group : group { attn_args a; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
-                          bool column = false; };   // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
+                          bool column = false;     // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
+                          bool q8 = false; };      // Q8_0 rings (match_attention_streams_q8): one k_attn_streams_q8 launch
 
 // rotated = concat(sub(mul(r, rotr), mul(i, roti)), add(mul(r, roti), mul(i, rotr))); returns the un-rotated source
 static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out, const ggml_tensor ** rotr_out, const ggml_tensor ** roti_out) {
@@ -931,27 +932,38 @@ static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out
 // kq = mul_mat(kc, qo), kc / vc = set_rows(ring, ko / vrow, idx). Guaranteed on return: kq, sm, pv and x1 have one consumer each; the rings are BF16 with
 // dense rows, of one shape [D, C, H] in their first three dimensions, written at one shared contiguous I32 index; D fits the kernels' lane layout; the mask
 // is contiguous F32 rows of C. What x2 is (cont, or a copy into rows) and every size beyond D, C, H is the caller's to check.
-struct attn_chain { const ggml_tensor * sm, * kq, * pv, * kc, * vc, * qo, * ko, * vrow, * x1, * x2, * mask, * idx; };
-static bool match_attention_chain(const analysis & an, int pos, attn_chain & c) {
+// q8 (match_attention_streams_q8 alone): the rings are Q8_0 with dense 34-byte blocks and dense rows, D is 64 or 128, and between the transpose and vc
+// stands vf = get_rows(vc, iota), the dequantised ring, with one consumer; iota is I32 of C rows per (head, column), a leaf or a view of one.
+struct attn_chain { const ggml_tensor * sm, * kq, * pv, * kc, * vc, * qo, * ko, * vrow, * x1, * x2, * mask, * idx, * vf = nullptr, * iota = nullptr; };
+static bool match_attention_chain(const analysis & an, int pos, attn_chain & c, bool q8 = false) {
+    const enum ggml_type ring_type = q8 ? GGML_TYPE_Q8_0 : GGML_TYPE_BF16;
     c.sm = an.g->nodes[pos];
     if (c.sm->op != GGML_OP_SOFT_MAX || !c.sm->src[1]) return false;
     c.kq = c.sm->src[0]; c.mask = c.sm->src[1];
     if (c.kq->op != GGML_OP_MUL_MAT || uses_of(an, c.kq) != 1 || uses_of(an, c.sm) != 1) return false;
     c.kc = c.kq->src[0]; c.qo = c.kq->src[1];
-    if (c.kc->op != GGML_OP_SET_ROWS || c.kc->type != GGML_TYPE_BF16) return false;
+    if (c.kc->op != GGML_OP_SET_ROWS || c.kc->type != ring_type) return false;
     c.pv = sole_consumer(an, c.sm);
     if (!c.pv || c.pv->op != GGML_OP_MUL_MAT || c.pv->src[1] != c.sm) return false;
     const ggml_tensor * vt = c.pv->src[0];
     if (vt->op != GGML_OP_CONT || vt->src[0]->op != GGML_OP_TRANSPOSE) return false;
     c.vc = vt->src[0]->src[0];
-    if (c.vc->op != GGML_OP_SET_ROWS || c.vc->type != GGML_TYPE_BF16) return false;
+    if (q8) {
+        c.vf = c.vc;
+        if (c.vf->op != GGML_OP_GET_ROWS || c.vf->type != GGML_TYPE_F32 || uses_of(an, c.vf) != 1) return false;
+        c.vc = c.vf->src[0]; c.iota = c.vf->src[1];
+        const ggml_tensor * root = c.iota->view_src ? c.iota->view_src : c.iota;
+        if (c.iota->type != GGML_TYPE_I32 || c.iota->ne[0] != c.vc->ne[1] || c.iota->ne[1] != c.vc->ne[2] || c.iota->ne[2] != c.vc->ne[3] || pos_of(an, root) >= 0) return false;
+    }
+    if (c.vc->op != GGML_OP_SET_ROWS || c.vc->type != ring_type) return false;
     c.x1 = sole_consumer(an, c.pv);
     if (!c.x1 || c.x1->op != GGML_OP_PERMUTE) return false;
     c.x2 = sole_consumer(an, c.x1);
     if (!c.x2) return false;
     const int64_t D = c.kc->ne[0];
-    if (c.vc->ne[0] != D || c.vc->ne[1] != c.kc->ne[1] || c.vc->ne[2] != c.kc->ne[2] || c.kc->nb[0] != 2 || c.vc->nb[0] != 2) return false;
-    if (D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
+    if (c.vc->ne[0] != D || c.vc->ne[1] != c.kc->ne[1] || c.vc->ne[2] != c.kc->ne[2]) return false;
+    if (q8) { if ((D != 64 && D != 128) || c.kc->nb[0] != 34 || c.vc->nb[0] != 34 || (int64_t) c.kc->nb[1] != D / 32 * 34 || (int64_t) c.vc->nb[1] != D / 32 * 34) return false; }
+    else if (c.kc->nb[0] != 2 || c.vc->nb[0] != 2 || D % 8 != 0 || 64 % (D / 8) != 0 || D > 256) return false;
     if (c.mask->type != GGML_TYPE_F32 || c.mask->ne[0] != c.kc->ne[1] || !ggml_is_contiguous(c.mask)) return false;
     c.idx = c.kc->src[1];
     if (c.vc->src[1] != c.idx || c.idx->type != GGML_TYPE_I32 || !ggml_is_contiguous(c.idx)) return false;
@@ -976,7 +988,7 @@ static bool match_rope_pair(const attn_chain & c, rope_pair & r) {
 // to the previous job). Guaranteed: every member is one of the listed ops and stands at most 200 nodes before the soft_max; the block holds exactly two
 // mul_mats, one soft_max and two set_rows; and no interior value is consumed outside the block (x2 is its output): every consumer of a member is a
 // member - counted from the members' side (the analysis holds every tensor's number of consuming nodes), so a graph of many blocks is not walked once per block.
-static bool collect_attention_interior(const analysis & an, int pos, const attn_chain & c, const rope_pair & r, bool into_rows, std::vector<int> & members) {
+static bool collect_attention_interior(const analysis & an, int pos, const attn_chain & c, const rope_pair & r, bool into_rows, std::vector<int> & members) {   // (c.vf: the Q8_0 form's get_rows is a member, its index an input)
     std::vector<const ggml_tensor *> stack = { c.x2 };
     std::unordered_map<const ggml_tensor *, bool> seen;
     int n_mm = 0, n_sm = 0, n_sr = 0;
@@ -987,7 +999,7 @@ static bool collect_attention_interior(const analysis & an, int pos, const attn_
         seen[t] = true;
         const int p = pos_of(an, t);
         if (p < 0) continue;                                  // leaf: cache, mask, indices, weights
-        if (t == c.mask || t == c.idx || t == r.rotr || t == r.roti) continue;
+        if (t == c.mask || t == c.idx || t == r.rotr || t == r.roti || (c.iota && t == c.iota)) continue;
         if ((const char *) t->data == nullptr) return false;
         // the projection output (and anything before it) is an input of the block, not part of it
         const bool is_input = (t->op == GGML_OP_MUL_MAT && t != c.kq && t != c.pv) || t->op == GGML_OP_TIMESTEP_EMBEDDING;
@@ -1000,6 +1012,7 @@ static bool collect_attention_interior(const analysis & an, int pos, const attn_
             case GGML_OP_VIEW: case GGML_OP_RESHAPE: case GGML_OP_PERMUTE: case GGML_OP_TRANSPOSE: case GGML_OP_CONT:
             case GGML_OP_MUL: case GGML_OP_SUB: case GGML_OP_ADD: case GGML_OP_CONCAT: break;
             case GGML_OP_CPY: if (t != c.x2 || !into_rows) return false; break;
+            case GGML_OP_GET_ROWS: if (t != c.vf) return false; break;
             default: return false;
         }
         members.push_back(p);
@@ -1091,9 +1104,9 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
 }
 
 // the lockstep and slots forms: one row of B > 1 columns; what is per stream (mask row, ring slot, RoPE row) gets a stride, what is shared gets 0
-static bool match_attention_streams(const analysis & an, int pos, attn_group & grp) {
+static bool match_attention_streams(const analysis & an, int pos, attn_group & grp, bool q8 = false) {
     attn_chain c; rope_pair r;
-    if (!match_attention_chain(an, pos, c) || c.x2->op != GGML_OP_CONT) return false;
+    if (!match_attention_chain(an, pos, c, q8) || c.x2->op != GGML_OP_CONT) return false;
     const ggml_tensor * kc = c.kc, * vc = c.vc, * mask = c.mask, * idx = c.idx, * x2 = c.x2;
     const int64_t D = kc->ne[0], C = kc->ne[1], H = kc->ne[2], B = kc->ne[3];
     if (B < 2 || c.qo->ne[0] != D || c.qo->ne[1] != 1 || c.qo->ne[2] != H || c.qo->ne[3] != B || vc->ne[3] != B || mask->ne[1] != 1) return false;
@@ -1128,6 +1141,14 @@ static bool match_attention_streams(const analysis & an, int pos, attn_group & g
     grp.sa.mask_bs = mask_per_stream ? C : 0;
     grp.sa.rot_bs = rot_bs;
     grp.sa.index_bs = index_per_stream ? 1 : 0;
+    return true;
+}
+
+// the same two forms over Q8_0 rings (moshi_hot_config::kv_q8): the block of match_attention_streams with set_rows into GGML_TYPE_Q8_0 rings and the
+// dequantising get_rows in front of the transpose - one k_attn_streams_q8 launch. The BF16 forms never see a Q8_0 ring and this one takes nothing else.
+static bool match_attention_streams_q8(const analysis & an, int pos, attn_group & grp) {
+    if (!match_attention_streams(an, pos, grp, true) || grp.mask_node || !k_attn_streams_q8_supported(grp.sa)) return false;   // (a mask copy is not bypassed here: the row is read once)
+    grp.q8 = true;
     return true;
 }
 
@@ -2704,7 +2725,7 @@ static void pass_attention(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
         attn_group grp;
-        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp) && !match_attention_codec_slots(pl.an, i, grp)) continue;
+        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp) && !match_attention_codec_slots(pl.an, i, grp) && !match_attention_streams_q8(pl.an, i, grp)) continue;
         if (claim_group(pl, grp)) pl.attn_groups.push_back(grp);
     }
     // mask copies that every consumer now bypasses (NOT the claim rule: the copy is no matcher's member, and it is marked and counted as it always was,
@@ -3225,6 +3246,12 @@ static void emit_attention_groups(planner & pl) {
             pl.p->n_codec_attn_launches++;
             continue;
         }
+        if (ag.q8) {      // lockstep streams or slots over Q8_0 rings
+            const attn_streams_args sa = ag.sa;
+            at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams_q8(s, sa); });
+            pl.p->n_q8_attn_blocks++;
+            continue;
+        }
         if (ag.B > 1) {   // lockstep streams: one launch for every (head, stream)
             const attn_streams_args sa = ag.sa;
             at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams(s, sa, err); });
@@ -3449,6 +3476,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
     c->stats.state_copy_launches_in_last_plan = p->n_state_copy_launches; c->stats.state_copy_jobs_in_last_plan = p->n_state_copy_jobs;
+    c->stats.q8_attention_blocks_in_last_plan = p->n_q8_attn_blocks;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
@@ -3589,6 +3617,8 @@ static bool hip_supports_op(ggml_backend_t, const struct ggml_tensor * op) {
                        (op->type == GGML_TYPE_Q8_0 || op->type == GGML_TYPE_Q4_0 || op->type == GGML_TYPE_Q4_K) && op->src[0]->ne[0] % ggml_blck_size(op->type) == 0;
             }
             return true;
+        case GGML_OP_SET_ROWS:   // float rings, or Q8_0 ones (kv_q8): whole blocks of 32 per row
+            return !ggml_is_quantized(op->type) || (op->type == GGML_TYPE_Q8_0 && op->src[0]->ne[0] % 32 == 0);
         case GGML_OP_MUL_MAT:
             switch (op->src[0]->type) { case GGML_TYPE_F32: case GGML_TYPE_F16: case GGML_TYPE_BF16: case GGML_TYPE_Q4_0: case GGML_TYPE_Q8_0: case GGML_TYPE_Q4_K: return true; default: return false; }
         default: return op->op < GGML_OP_COUNT;

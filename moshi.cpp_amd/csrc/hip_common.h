@@ -241,6 +241,12 @@ void k_attn_decode(hipStream_t s, const attn_args & a, void * ws = nullptr, unsi
 // stream (stream slots, moshi_hot_create_slots: mask_bs = C, rot_bs = D floats, index_bs = 1), each workgroup then scanning its own stream's mask row.
 struct attn_streams_args { attn_args a; int B; int64_t q_bs, k_bs, v_bs, kc_bs, vc_bs, out_bs, mask_bs, rot_bs, index_bs; };
 void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err = nullptr);
+// The same block over Q8_0 rings [D, C, H, B] (moshi_hot_config::kv_q8; hip_attn_q8.h): the new rows are quantised as set_rows into a Q8_0
+// ring does, the scores are vec_dot_q8_0_q8_0's integer dots against the quantised query, P x V runs over the dequantised rows with p unrounded. Same
+// argument struct and strides as k_attn_streams (kc_bs / vc_bs and the ring strides in bytes of Q8_0 rows: k_nb1 = v_nb1 = D / 32 * 34). D 64 or 128,
+// C <= 4096, B >= 2, T = 1; one workgroup per (head, column), none waits for another, no workspace.
+bool k_attn_streams_q8_supported(const attn_streams_args & a);
+void k_attn_streams_q8(hipStream_t s, const attn_streams_args & a);
 // Decoder slots (moshi_hot_create_codec_slots): the codec transformer's attention block of B columns, T = 2 new rows each at the column's own position -
 // one workgroup per (head, row, column), each doing exactly what attn_ring256_kernel's workgroup (head, row) does for a single column (attn_ring256_body:
 // it rotates both new rows, workgroup (h, 0, b) writes them into column b's ring, row t attends over the column's own ring under its own mask row). `a`

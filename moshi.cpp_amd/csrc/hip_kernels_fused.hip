@@ -1861,6 +1861,9 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
     else      attn_streams_kernel<ATTN_NW_BASE><<<grid, ATTN_NW_BASE * 64, smem, s>>>(sa, w);
 }
 
+// Lockstep streams and stream slots over Q8_0 rings: a kernel of its own (row format, score arithmetic and ring walk all differ from attn_decode_body)
+#include "hip_attn_q8.h"
+
 // Decoder slots: workgroup (h, t, b) is attn_ring256_kernel's workgroup (h, t) over column b - its own q / k / v rows, ring column, mask rows, RoPE rows,
 // ring slots and output rows - so a column's two rows are computed exactly as the single-column launch computes them. Only workgroup (h, 0, b) writes
 // column b's ring rows; nothing of another column is read or written.

@@ -524,8 +524,35 @@ __global__ void set_rows_kernel(tdesc dst, tdesc src, tdesc idx) {
     const int es = elem_size(dst.type);
     for (int64_t k = threadIdx.x; k < src.ne[0]; k += blockDim.x) st_from_f32(out + k * es, dst.type, sp[k]);
 }
+// rows into a Q8_0 destination (K / V rings of a kv_q8 model): quantize_row_q8_0 per row, as convert_rows_kernel does it - one wave per row, a half-wave per block
+__global__ void __launch_bounds__(64) set_rows_q80_kernel(tdesc dst, tdesc src, tdesc idx) {
+    const int64_t i = blockIdx.x, i02 = blockIdx.y, i03 = blockIdx.z;
+    const char * ip = at(idx, i, i02 % idx.ne[1], i03 % idx.ne[2], 0);
+    const int64_t r = idx.type == GGML_TYPE_I64 ? *(const int64_t *) ip : (int64_t) *(const int32_t *) ip;
+    if (r < 0 || r >= dst.ne[1]) return;
+    const float * sp = (const float *) at(src, 0, i, i02, i03);
+    block_q8_0 * out = (block_q8_0 *) at(dst, 0, r, i02, i03);
+    const int64_t K = src.ne[0];
+    for (int64_t base = 0; base < K; base += 64) {
+        const int64_t k = base + threadIdx.x;
+        const float v = k < K ? sp[k] : 0.f;
+        float amax = fabsf(v);
+        for (int o = 16; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+        const float d = amax / 127.f;
+        const float id = d ? 1.0f / d : 0.0f;
+        if (k < K) {
+            out[k / 32].qs[k % 32] = (int8_t) roundf(v * id);
+            if (k % 32 == 0) out[k / 32].d = f2h(d);
+        }
+    }
+}
 void k_set_rows(hipStream_t s, tdesc dst, tdesc src, tdesc idx) {
     if (td_nelements(src) == 0) return;
+    if (dst.type == GGML_TYPE_Q8_0) {
+        GGML_ASSERT(src.ne[0] % 32 == 0 && src.nb[0] == 4 && dst.nb[0] == 34);
+        set_rows_q80_kernel<<<dim3((unsigned) src.ne[1], (unsigned) src.ne[2], (unsigned) src.ne[3]), 64, 0, s>>>(dst, src, idx);
+        return;
+    }
     GGML_ASSERT(!ggml_is_quantized((enum ggml_type) dst.type));
     const int bs = src.ne[0] >= 256 ? 256 : 64;
     set_rows_kernel<<<dim3((unsigned) src.ne[1], (unsigned) src.ne[2], (unsigned) src.ne[3]), bs, 0, s>>>(dst, src, idx);

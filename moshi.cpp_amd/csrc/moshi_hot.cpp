@@ -424,7 +424,7 @@ struct Layer {
     std::vector<T> gate_in, gate_out;          // gated FFN (silu) weight sets
     T linear1 = nullptr, linear2 = nullptr;    // plain FFN (gelu)
     T layer_scale_1 = nullptr, layer_scale_2 = nullptr;
-    T kcache = nullptr, vcache = nullptr;      // state: BF16 [D, C, H]
+    T kcache = nullptr, vcache = nullptr;      // state: BF16 [D, C, H]; GGML_TYPE_Q8_0 [D, C, H, B] in the Temporal transformer of a kv_q8 model
     // cross-attention (tts): LayerNorm eps 0, in_proj [dim, 3 dim] used through row views, cached F32 K/V [D, Tc, H]
     Norm norm_cross; T cross_in = nullptr, cross_out = nullptr, k_cross = nullptr, v_cross = nullptr;
 };
@@ -439,6 +439,9 @@ struct Transformer {
     // cached-graph inputs (transformer.h:1101-1109)
     T g_bias = nullptr, g_offset = nullptr, g_indices = nullptr;
     int offset = 0;
+    // Q8_0 rings (moshi_hot_config::kv_q8), one each for all layers: the row indices 0 .. C-1 of get_rows, and the storage of the two F32 interiors of
+    // the P x V product (the dequantised V ring and its transpose), which a layer has consumed before the next layer writes them
+    T kv_iota = nullptr, kv_vf = nullptr, kv_vt = nullptr;
     ~Transformer() { for (auto & p : pats) { ggml_backend_buffer_free(p.second.buf); ggml_free(p.second.ctx); } }
 };
 
@@ -499,7 +502,16 @@ T attention(Builder & c, const Transformer & tr, Layer & L, int wi, T indices, T
     const float scale = 1.f / sqrtf((float) q->ne[0]);
     T w = ggml_mul_mat(c, k, q);
     w = ggml_soft_max_ext(c, w, attn_bias, scale, 0.0f);
-    v = ggml_cont(c, ggml_transpose(c, v));
+    if (v->type == GGML_TYPE_Q8_0) {
+        // Q8_0 rings: mul_mat above is vec_dot_q8_0_q8_0 against the quantised q; P x V runs over the dequantised ring, get_rows(v, 0 .. C-1) -
+        // F32 x F32, p unrounded. The two large interiors live in the transformer's shared work tensors, not in the graph buffer.
+        T iota = ggml_view_3d(c, tr.kv_iota, v->ne[1], v->ne[2], v->ne[3], 0, 0, 0);   // [C, H, B]: the same C indices for every head and column
+        T vf = ggml_get_rows(c, v, iota);
+        vf->data = tr.kv_vf->data; vf->buffer = tr.kv_vf->buffer;
+        v = ggml_cont(c, ggml_transpose(c, vf));
+        v->data = tr.kv_vt->data; v->buffer = tr.kv_vt->buffer;
+    } else
+        v = ggml_cont(c, ggml_transpose(c, v));
     T o = ggml_mul_mat(c, v, w);
     T o2 = ggml_cont(c, ggml_permute(c, o, 0, 2, 1, 3));
     o = ggml_reshape_3d(c, o2, o2->ne[0] * o2->ne[1], o2->ne[2], o2->ne[3]);
@@ -1043,8 +1055,9 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
             }
         }
         if (m->n_streams > 1) {   // moshi_kv_cache_state with batch_size = B (transformer.h:155-171); decoder slots: the codec transformer's rings too
-            L.kcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
-            L.vcache = state4(m, GGML_TYPE_BF16, dim / heads, capacity, heads, m->n_streams);
+            const enum ggml_type ring_type = m->cfg.kv_q8 && &tr == &m->temporal ? GGML_TYPE_Q8_0 : GGML_TYPE_BF16;   // (kv_q8: the Temporal rings alone)
+            L.kcache = state4(m, ring_type, dim / heads, capacity, heads, m->n_streams);
+            L.vcache = state4(m, ring_type, dim / heads, capacity, heads, m->n_streams);
         } else {
             L.kcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
             L.vcache = state(m, GGML_TYPE_BF16, dim / heads, capacity, heads);
@@ -1054,7 +1067,7 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
                              W.add(p + "norm_cross.bias", GGML_TYPE_F32, dim, 1, 1, [](T t, Rng & r, std::vector<uint8_t> & o) { gen_normal(t, r, o, 0.02f); }) };
             L.cross_in = W.add(p + "cross_attention.in_projs.0.weight", wtype, dim, 3 * dim, 1, qgen(s_in));
             L.cross_out = W.add(p + "cross_attention.out_projs.0.weight", wtype, dim, dim, 1, qgen(s_in * upd));   // a residual update like out_proj / linear_out
-            if (m->n_streams > 1) {   // one condition per column
+            if (m->n_streams > 1) {   // one condition per column (F32 whatever kv_q8 says)
                 L.k_cross = state4(m, GGML_TYPE_F32, dim / heads, cross_len, heads, m->n_streams);
                 L.v_cross = state4(m, GGML_TYPE_F32, dim / heads, cross_len, heads, m->n_streams);
             } else {
@@ -1062,6 +1075,11 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
                 L.v_cross = state(m, GGML_TYPE_F32, dim / heads, cross_len, heads);
             }
         }
+    }
+    if (m->n_streams > 1 && m->cfg.kv_q8 && &tr == &m->temporal && !norms_only) {
+        tr.kv_iota = state(m, GGML_TYPE_I32, capacity);   // filled with 0 .. C-1 once the state buffer exists (create_model)
+        tr.kv_vf = state4(m, GGML_TYPE_F32, dim / heads, capacity, heads, m->n_streams);
+        tr.kv_vt = state4(m, GGML_TYPE_F32, capacity, dim / heads, heads, m->n_streams);
     }
 }
 
@@ -1485,6 +1503,15 @@ extern "C" int moshi_hot_tensor_file_name(const char * checkpoint_name, char * o
 }
 static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct moshi_hot_config * cfg, uint64_t seed, const char * gguf_path, int n_streams,
                                         ModelKind kind) {
+    if (cfg->kv_q8) {   // Q8_0 K / V rings: B-column LM models alone, whole blocks of 32 per head row, on a backend that can store rows into such a ring
+        if (n_streams < 2 || (kind != ModelKind::lockstep && kind != ModelKind::slots) || cfg->persona_columns || cfg->personaplex || !cfg->enable_lm ||
+            cfg->num_heads < 1 || cfg->dim % cfg->num_heads != 0 || (cfg->dim / cfg->num_heads) % 32 != 0) return nullptr;
+        struct ggml_context * pc = ggml_init({ ggml_tensor_overhead() * 8, NULL, true });
+        T ring = ggml_new_tensor_2d(pc, GGML_TYPE_Q8_0, 32, 1), row = ggml_new_tensor_2d(pc, GGML_TYPE_F32, 32, 1), at = ggml_new_tensor_1d(pc, GGML_TYPE_I32, 1);
+        const bool ok = ggml_backend_supports_op(backend, ggml_set_rows(pc, ring, row, at));
+        ggml_free(pc);
+        if (!ok) return nullptr;
+    }
     moshi_hot_model * m = new moshi_hot_model;
     m->cfg = *cfg;
     m->be = backend;
@@ -1660,6 +1687,11 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     }
     GGML_ASSERT(m->st_buf);
     ggml_backend_buffer_clear(m->st_buf, 0);   // every state starts as zeros (64 columns of moshika rings are 100 GB: cleared in place)
+    if (m->temporal.kv_iota) {
+        std::vector<int32_t> iota((size_t) m->temporal.capacity);
+        for (size_t i = 0; i < iota.size(); i++) iota[i] = (int32_t) i;
+        ggml_backend_tensor_set(m->temporal.kv_iota, iota.data(), 0, iota.size() * 4);
+    }
     m->tokens_tmp.resize((size_t) (c.n_q + 1 + 32));
     m->pipe_codes.resize((size_t) (c.n_q + 1 + 32)); m->pipe_tokens.resize((size_t) (c.n_q + 1 + 32));
     ggml_backend_synchronize(backend);   // weights and zeroed states are in place before any other stream touches them
@@ -2913,7 +2945,7 @@ void cut_passes(moshi_hot_model * m, int n_jobs, const int32_t * slots, const in
 // replay: moshi_hot_slots_replay - the same passes over history frames of a tts-shaped model (which has no provided frames: needed_tokens == 0,
 // lm.h:807-809), and of no other; the prefill calls keep refusing that shape.
 int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end, bool replay = false) {
-    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams) return -1;
+    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;   // (batched passes over Q8_0 rings are not built)
     const int ncb = m->cfg.n_q + 1;
     const int64_t C = m->temporal.capacity;
     int total = 0;
@@ -3008,7 +3040,7 @@ void slots_persona_pass(moshi_hot_model * m, std::vector<PassJob> & jobs, const 
 }
 
 int slots_persona(moshi_hot_model * m, int n_jobs, const int32_t * slots, const moshi_hot_persona * personas, int chunk) {
-    if (m->kind != ModelKind::slots || !persona_shape(m) || m->cfg.n_q + 1 != PERSONAPLEX_PROMPT_COLUMNS || n_jobs < 0 || n_jobs > m->n_streams || (n_jobs > 0 && (!slots || !personas))) return -1;
+    if (m->kind != ModelKind::slots || !persona_shape(m) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16 || m->cfg.n_q + 1 != PERSONAPLEX_PROMPT_COLUMNS || n_jobs < 0 || n_jobs > m->n_streams || (n_jobs > 0 && (!slots || !personas))) return -1;
     const int64_t C = m->temporal.capacity;
     std::vector<int32_t> n_rows((size_t) n_jobs);
     int total = 0;
@@ -3233,7 +3265,7 @@ void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const vo
 // full: the _full calls, which take a tts-shaped model (and are the plain calls on any other); the plain calls refuse it
 int slot_fork(moshi_hot_model_t * m, int src, int dst, bool full) {
     moshi_hot_model::Column * a = slot(m, src), * b = slot(m, dst);
-    if (!a || !b || src == dst || !a->open || b->open || (tts_shape(m) && !full)) return -1;
+    if (!a || !b || src == dst || !a->open || b->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
     slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr, tts_shape(m));
     *b = *a;
     b->held = false;
@@ -3536,6 +3568,13 @@ extern "C" int64_t moshi_hot_ring_bytes(moshi_hot_model_t * m, int which, int la
         if (write) ggml_backend_tensor_set(t, buf, 0, n); else ggml_backend_tensor_get(t, buf, 0, n);
     }
     return size;
+}
+
+// the bytes of the Temporal transformer's K / V rings, all layers and columns (any model kind; 0 without an LM)
+extern "C" int64_t moshi_hot_kv_bytes(moshi_hot_model_t * m) {
+    int64_t n = 0;
+    for (const Layer & L : m->temporal.layers) for (T t : { L.kcache, L.vcache }) if (t) n += (int64_t) ggml_nbytes(t);
+    return n;
 }
 
 // identical pseudo-random BF16 rows in every slot of the K / V rings (tests: long-context attention against the oracle over a known cache)

@@ -20,7 +20,7 @@ class Config(C.Structure):
                [("dep_schedule", C.c_int32 * MAX_CB), ("update_scale", C.c_float),
                 ("dep_shard_rank", C.c_int32), ("dep_shard_world", C.c_int32), ("depth_only", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_world", C.c_int32), ("codec_stream", C.c_int32), ("chain_depth", C.c_int32),
-                ("wide_streams", C.c_int32), ("persona_columns", C.c_int32), ("f32_matrix", C.c_int32), ("float_accumulate", C.c_int32)]
+                ("wide_streams", C.c_int32), ("persona_columns", C.c_int32), ("kv_q8", C.c_int32), ("f32_matrix", C.c_int32), ("float_accumulate", C.c_int32)]
 
     @property
     def io_dep_q(self):
@@ -164,6 +164,7 @@ SIGNATURES = {
     "moshi_hot_set_context_fill": (None, [P, C.c_int64]),
     "moshi_hot_fill_ring": (None, [P, C.c_int, C.c_int, C.c_uint64, C.c_float]),
     "moshi_hot_ring_bytes": (C.c_int64, [P, C.c_int, C.c_int, C.c_int, P, C.c_int64, C.c_int]),
+    "moshi_hot_kv_bytes": (C.c_int64, [P]),
     "moshi_hot_host_ring": (C.c_int, [P, P, C.c_int]),
     "moshi_hot_force_last": (None, [P, C.c_int32, P]),
     "moshi_hot_set_timing": (None, [P, C.c_int]),
