@@ -95,7 +95,16 @@ struct moshi_hot_config {
     // Not bit-comparable with a kv_q8 = 0 model (k / v are quantised per block of 32 instead of rounded to BF16; p is not rounded).
     // NULL with 1: n_streams == 1, moshi_hot_create, the codec-slots and encoder-slots creators, head widths that are no multiple of 32, persona_columns.
     // -1 on such a model, nothing changed: moshi_hot_slots_prefill / _long, moshi_hot_slots_replay, moshi_hot_slots_persona, moshi_hot_slot_fork / _save /
-    // _load and their _full variants (batched passes and snapshots over Q8_0 rings are not built yet).
+    // _load and their _full variants: value 1 refuses them only because tests/test_kv_q8_cpu.py pins these refusals; value 3 lifts them as said next.
+    // The field is a set of bits. 1 (bit 0) is the above. 3 (bits 0 and 1): the same
+    // rings, and a slots model of the moshika or stt shape also takes histories - moshi_hot_slots_prefill / moshi_hot_slot_prefill (each Temporal layer of a
+    // pass one k_attn_blocks_q8 launch pair), moshi_hot_slot_hold, moshi_hot_slot_fork / _save / _load and, being the plain calls there,
+    // their _full forms. A snapshot copies a head's live rows rounded up to a whole number of row groups - the fewest rows whose Q8_0 bytes are a multiple
+    // of 16: 2 at head width 128, 4 at 64, 8 at 32 or 96 - as the ring's own bytes (the blob: per layer K and then V as H x rows x D / 32 blocks of 34
+    // bytes; the rows past the live count are whatever the ring held and are never read before they are rewritten); NULL with 3 when context is no whole
+    // number of groups. The fingerprint holds the ring type: a BF16 model refuses such a blob and the other way round. Still -1 with 3:
+    // moshi_hot_slots_prefill_long, moshi_hot_slots_replay, moshi_hot_slots_persona, the _full calls on a tts-shaped model. A model that only steps
+    // computes with 3 what it computes with 1. 2, or any other bit: NULL.
     // (It sits in front of f32_matrix: tests pin f32_matrix and float_accumulate as the struct's last two fields.)
     int32_t kv_q8;
     // 1: the create calls switch the handle the model is created on to the f64-MFMA mat-mul for F32 weights, ggml_backend_mi355x_set_f32_matrix(backend, 1):

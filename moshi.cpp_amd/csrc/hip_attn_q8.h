@@ -91,6 +91,31 @@ template <int D> __device__ __forceinline__ void attn_q8_store(const attn_q8_u32
 
 template <int CTRL> __device__ __forceinline__ float attn_q8_quad(float v) { return dpp_f32<CTRL>(v); }
 
+// A lane's four consecutive outputs of one head row, eight neighbouring lanes holding a block of 32 (every lane of the wave runs this: the block maximum
+// travels by DPP). rotate: apply_rope's rotation of the pairs (in0, in1) by (rc, rs), `upper` for the outputs of the row's second half; otherwise in0 is
+// the row. Then quantize_block_q80's arithmetic. -> the four quants, packed; dh: the block's scale as F16
+__device__ __forceinline__ uint32_t attn_q8_rope_quant(const float (&in0)[4], const float (&in1)[4], const float (&rc)[4], const float (&rs)[4], bool rotate, bool upper, uint16_t & dh) {
+    float v[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (rotate) {
+            const float x0 = in0[i] * rc[i], x1 = in1[i] * rs[i], y0 = in0[i] * rs[i], y1 = in1[i] * rc[i];
+            v[i] = upper ? y0 + y1 : x0 - x1;
+        } else v[i] = in0[i];
+    }
+    float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    amax = fmaxf(amax, dpp_f32<DPP_QUAD_XOR1>(amax));
+    amax = fmaxf(amax, dpp_f32<DPP_QUAD_XOR2>(amax));
+    amax = fmaxf(amax, dpp_f32<DPP_HALF_MIRROR>(amax));                 // the 8 lanes of one 32-wide block
+    const float d = amax / 127.f;
+    const float id = d != 0.f ? 1.0f / d : 0.0f;
+    int q[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) q[i] = (int) roundf(v[i] * id);
+    dh = f2h(d);
+    return (uint32_t) (q[0] & 0xff) | ((uint32_t) (q[1] & 0xff) << 8) | ((uint32_t) (q[2] & 0xff) << 16) | ((uint32_t) (q[3] & 0xff) << 24);
+}
+
 template <int D>
 __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_streams_q8_kernel(attn_streams_args sa) {
     typedef attn_q8_shape<D> S;
@@ -150,25 +175,8 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_streams_q8_kernel(attn_s
 
     // ---- RoPE and the three quantisers -----------------------------------------------------------------------------------------------------------
     if (wave < 3) {
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if (wave < 2 && a.rot) {
-                const float x0 = in0[i] * rc[i], x1 = in1[i] * rs[i], y0 = in0[i] * rs[i], y1 = in1[i] * rc[i];
-                v[i] = j0 < half ? x0 - x1 : y0 + y1;
-            } else v[i] = in0[i];
-        }
-        float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        amax = fmaxf(amax, dpp_f32<DPP_QUAD_XOR1>(amax));
-        amax = fmaxf(amax, dpp_f32<DPP_QUAD_XOR2>(amax));
-        amax = fmaxf(amax, dpp_f32<DPP_HALF_MIRROR>(amax));                 // the 8 lanes of one 32-wide block
-        const float d = amax / 127.f;
-        const float id = d != 0.f ? 1.0f / d : 0.0f;
-        int q[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) q[i] = (int) roundf(v[i] * id);
-        const uint32_t packed = (uint32_t) (q[0] & 0xff) | ((uint32_t) (q[1] & 0xff) << 8) | ((uint32_t) (q[2] & 0xff) << 16) | ((uint32_t) (q[3] & 0xff) << 24);
-        const uint16_t dh = f2h(d);
+        uint16_t dh;
+        const uint32_t packed = attn_q8_rope_quant(in0, in1, rc, rs, wave < 2 && a.rot, j0 >= half, dh);
         if (row_lane) {
             if (wave == 0) {
                 *(uint32_t *) (qq + j0) = packed;

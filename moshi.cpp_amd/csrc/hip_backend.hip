@@ -901,7 +901,7 @@ static bool match_norm_affine(const analysis & an, int pos, norm_affine_group & 
 //      Refused today: several rows of several columns at once in any other shape, and a copy into rows from anything but a ring column.
 struct attn_group : group { attn_args a; const ggml_tensor * mask_node; int B = 1; attn_streams_args sa;   // B > 1: match_attention_streams
                           bool column = false;     // the rings are one column of [D, C, H, B] rings (slot prefill): the group is a job of a k_attn_blocks launch pair
-                          bool q8 = false; };      // Q8_0 rings (match_attention_streams_q8): one k_attn_streams_q8 launch
+                          bool q8 = false; };      // Q8_0 rings: one k_attn_streams_q8 launch (match_attention_streams_q8), or with `column` a job of a k_attn_blocks_q8 launch pair
 
 // rotated = concat(sub(mul(r, rotr), mul(i, roti)), add(mul(r, roti), mul(i, rotr))); returns the un-rotated source
 static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out, const ggml_tensor ** rotr_out, const ggml_tensor ** roti_out) {
@@ -932,7 +932,7 @@ static bool match_rope(const ggml_tensor * rotated, const ggml_tensor ** src_out
 // kq = mul_mat(kc, qo), kc / vc = set_rows(ring, ko / vrow, idx). Guaranteed on return: kq, sm, pv and x1 have one consumer each; the rings are BF16 with
 // dense rows, of one shape [D, C, H] in their first three dimensions, written at one shared contiguous I32 index; D fits the kernels' lane layout; the mask
 // is contiguous F32 rows of C. What x2 is (cont, or a copy into rows) and every size beyond D, C, H is the caller's to check.
-// q8 (match_attention_streams_q8 alone): the rings are Q8_0 with dense 34-byte blocks and dense rows, D is 64 or 128, and between the transpose and vc
+// q8 (match_attention_streams_q8 and the ring-column form of match_attention): the rings are Q8_0 with dense 34-byte blocks and dense rows, D is 64 or 128, and between the transpose and vc
 // stands vf = get_rows(vc, iota), the dequantised ring, with one consumer; iota is I32 of C rows per (head, column), a leaf or a view of one.
 struct attn_chain { const ggml_tensor * sm, * kq, * pv, * kc, * vc, * qo, * ko, * vrow, * x1, * x2, * mask, * idx, * vf = nullptr, * iota = nullptr; };
 static bool match_attention_chain(const analysis & an, int pos, attn_chain & c, bool q8 = false) {
@@ -1074,16 +1074,16 @@ static void fill_attention_group(const analysis & an, const attn_chain & c, cons
 }
 
 // the single-column and ring-column forms: T rows of one column
-static bool match_attention(const analysis & an, int pos, attn_group & grp) {
+static bool match_attention(const analysis & an, int pos, attn_group & grp, bool q8 = false) {
     attn_chain c; rope_pair r;
-    if (!match_attention_chain(an, pos, c)) return false;
+    if (!match_attention_chain(an, pos, c, q8)) return false;
     const ggml_tensor * kc = c.kc, * vc = c.vc, * x2 = c.x2;
     // the block's output: a dense copy of its own, or (slot prefill) a copy into the block's row range of a wider [D, H, T] tensor
     const bool into_rows = x2->op == GGML_OP_CPY && x2->src[0] == c.x1 && x2->type == GGML_TYPE_F32;
     if (x2->op != GGML_OP_CONT && !into_rows) return false;
     // the rings: whole [D, C, H] tensors, or (slot prefill) [D, C, H] views of one column of [D, C, H, B] rings
     const bool column = kc->ne[3] == 1 && kc->view_src && kc->view_src->ne[3] > 1;
-    if (column != (vc->ne[3] == 1 && vc->view_src && vc->view_src->ne[3] > 1) || (into_rows && !column)) return false;
+    if (column != (vc->ne[3] == 1 && vc->view_src && vc->view_src->ne[3] > 1) || (into_rows && !column) || (q8 && !column)) return false;
 
     const int64_t D = kc->ne[0], H = kc->ne[2], Tn = c.qo->ne[1];
     if (c.qo->ne[0] != D || Tn < 1 || Tn > 64 || c.qo->ne[2] != H || c.qo->ne[3] != 1) return false;   // B == 1; blocks longer than 4 rows (prompt prefill) run as consecutive launches of 4
@@ -1100,6 +1100,14 @@ static bool match_attention(const analysis & an, int pos, attn_group & grp) {
     grp.a.T = (int) Tn;
     grp.a.q_ts = qs.nb[1] / 4; grp.a.k_ts = ks.nb[1] / 4; grp.a.v_ts = vs.nb[1] / 4;
     grp.column = column;
+    if (q8) {   // slot prefill over Q8_0 rings (moshi_hot_config::kv_q8 = 3): what a k_attn_blocks_q8 pair takes as a job
+        attn_blocks_args one;
+        memset(&one, 0, sizeof(one));
+        one.a = grp.a; one.n_jobs = 1;
+        one.job[0].kcache = grp.a.kcache; one.job[0].vcache = grp.a.vcache; one.job[0].T = grp.a.T;
+        if (!k_attn_blocks_q8_supported(one)) return false;
+        grp.q8 = true;
+    }
     return true;
 }
 
@@ -2725,7 +2733,8 @@ static void pass_attention(planner & pl) {
     for (int i = 0; i < pl.g->n_nodes; i++) {
         if (pl.an.skip[(size_t) i] || pl.g->nodes[i]->op != GGML_OP_SOFT_MAX) continue;
         attn_group grp;
-        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp) && !match_attention_codec_slots(pl.an, i, grp) && !match_attention_streams_q8(pl.an, i, grp)) continue;
+        if (!match_attention(pl.an, i, grp) && !match_attention_streams(pl.an, i, grp) && !match_attention_codec_slots(pl.an, i, grp) && !match_attention_streams_q8(pl.an, i, grp) &&
+            !match_attention(pl.an, i, grp, true)) continue;
         if (claim_group(pl, grp)) pl.attn_groups.push_back(grp);
     }
     // mask copies that every consumer now bypasses (NOT the claim rule: the copy is no matcher's member, and it is marked and counted as it always was,
@@ -3116,7 +3125,7 @@ static void pass_column_attention_rows(planner & pl) {
     if (no_attn_rows()) return;
     std::vector<attn_group> & groups = pl.attn_groups;
     std::vector<size_t> order;   // the column groups in emit order (the order their outputs stand in the graph)
-    for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1) order.push_back(i);
+    for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1 && !groups[i].q8) order.push_back(i);   // (k_attn_rows reads BF16 rings)
     std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return groups[x].emit_pos < groups[y].emit_pos; });
     auto same_shape = [](const attn_args & a, const attn_args & b) { return b.T == 1 && same_attention_shape(a, b); };   // rows: one-row groups only
     auto stride = [](const void * a, const void * b) { return (int64_t) ((const char *) b - (const char *) a); };
@@ -3185,7 +3194,8 @@ static void pass_column_attention_rows(planner & pl) {
 }
 
 // slot prefill: the column groups of one layer of one pass (consecutive groups of one shape with nothing but layout nodes and their own members
-// between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase
+// between their outputs) become ONE pair of k_attn_blocks launches, emitted where the last of them stood: a write phase, then an attend phase.
+// Groups over Q8_0 rings become a k_attn_blocks_q8 pair the same way; a pair holds groups of one ring type.
 static void merge_column_attention_blocks(planner & pl) {
     std::vector<attn_group> & attn_groups = pl.attn_groups;
     for (size_t gi = 0; gi < attn_groups.size(); ) {
@@ -3199,7 +3209,7 @@ static void merge_column_attention_blocks(planner & pl) {
         while (ge < attn_groups.size() && ge - gi < ATTN_BLOCKS_MAX) {
             const attn_group & n = attn_groups[ge];
             const attn_args & b = n.a;
-            if (!n.column || n.emit_pos < 0 || !same_attention_shape(a0, b) || (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts))) break;
+            if (!n.column || n.emit_pos < 0 || n.q8 != attn_groups[gi].q8 || !same_attention_shape(a0, b) || (b.T > 1 && rows && (b.q_ts != rows->q_ts || b.k_ts != rows->k_ts || b.v_ts != rows->v_ts))) break;
             // a launch pair never holds two groups of one ring column: it writes every job's rows before any job attends, so a second group of a column
             // (a ring-ordered row after its predecessor, where pass_column_attention_rows is off or has declined the run) must start a launch of its own
             bool column_taken = false;
@@ -3218,6 +3228,7 @@ static void merge_column_attention_blocks(planner & pl) {
         ba.a = a0;
         if (rows) { ba.a.q_ts = rows->q_ts; ba.a.k_ts = rows->k_ts; ba.a.v_ts = rows->v_ts; }
         ba.n_jobs = (int) (ge - gi);
+        const bool q8 = attn_groups[gi].q8;
         for (size_t k = gi; k < ge; k++) {
             const attn_args & b = attn_groups[k].a;
             ba.job[k - gi] = { b.q, b.k, b.v, b.kcache, b.vcache, b.mask, b.rot, b.index, b.out, b.T };
@@ -3225,8 +3236,8 @@ static void merge_column_attention_blocks(planner & pl) {
         }
         unsigned * err = pl.c->err_dev;
         auto & at = pl.at_pos[hi];
-        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 0; k_attn_blocks(s, b, err); });
-        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 1; k_attn_blocks(s, b, err); });
+        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 0; if (q8) k_attn_blocks_q8(s, b); else k_attn_blocks(s, b, err); });
+        at.insert(at.begin(), [=](hipStream_t s) { attn_blocks_args b = ba; b.write_only = 1; if (q8) k_attn_blocks_q8(s, b); else k_attn_blocks(s, b, err); });
         pl.p->n_attn_block_launches += 2; pl.p->n_attn_block_jobs += ba.n_jobs;
         gi = ge;
     }

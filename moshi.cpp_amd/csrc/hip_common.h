@@ -264,6 +264,12 @@ void k_attn_codec_slots(hipStream_t s, const attn_streams_args & a);
 struct attn_block_job { const float * q, * k, * v; char * kcache, * vcache; const float * mask, * rot; const int32_t * index; float * out; int T; };
 struct attn_blocks_args { attn_args a; int n_jobs, write_only; attn_block_job job[ATTN_BLOCKS_MAX]; };
 void k_attn_blocks(hipStream_t s, const attn_blocks_args & a, unsigned * err = nullptr);
+// The same pair over Q8_0 rings (moshi_hot_config::kv_q8 = 3; hip_attn_q8_blocks.h): the same table, the ring strides in bytes of Q8_0 rows
+// (k_nb1 = v_nb1 = D / 32 * 34). write_only = 1 quantises every job's k / v rows into their ring slots as set_rows into a Q8_0 ring does; 0 attends, a
+// workgroup per 16 query rows of a (job, head): scores as v_mfma_i32_16x16x32_i8 block dots against the quantised queries, P x V on the f64 matrix
+// pipe over the dequantised rows. D 64 or 128, C <= 4096, 1 <= T_j <= 64; no workgroup waits for another, no workspace.
+bool k_attn_blocks_q8_supported(const attn_blocks_args & a);
+void k_attn_blocks_q8(hipStream_t s, const attn_blocks_args & a);
 // Slot prefill past the ring's end (moshi_hot_slots_prefill_long): the RING-ORDERED rows of one layer of one pass. Job j = n_j consecutive one-row
 // attention sequences on ONE ring column: row t has its own q / k / v row, mask row, RoPE row, ring slot and output row, each at the job's base plus t
 // times a byte stride. Workgroup (h, j) walks job j's rows in order and runs attn_decode_body on each with T = 1 - write the row's K / V at its ring slot,

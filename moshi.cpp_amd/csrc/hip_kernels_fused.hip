@@ -1863,6 +1863,8 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
 
 // Lockstep streams and stream slots over Q8_0 rings: a kernel of its own (row format, score arithmetic and ring walk all differ from attn_decode_body)
 #include "hip_attn_q8.h"
+// Slot prefill over the same rings: T new rows per job as a write launch and an int8-MFMA attend launch
+#include "hip_attn_q8_blocks.h"
 
 // Decoder slots: workgroup (h, t, b) is attn_ring256_kernel's workgroup (h, t) over column b - its own q / k / v rows, ring column, mask rows, RoPE rows,
 // ring slots and output rows - so a column's two rows are computed exactly as the single-column launch computes them. Only workgroup (h, 0, b) writes

@@ -444,6 +444,23 @@ struct Transformer {
     T kv_iota = nullptr, kv_vf = nullptr, kv_vt = nullptr;
     ~Transformer() { for (auto & p : pats) { ggml_backend_buffer_free(p.second.buf); ggml_free(p.second.ctx); } }
 };
+// Q8_0 rings with histories (kv_q8 = 3): the smallest count of D-wide ring rows whose bytes are a multiple of 16 - a row is D / 32 blocks of 34 bytes, so
+// 2 rows at D = 128 (136 bytes each), 4 at D = 64 (68), 8 at D = 32 or 96. Snapshots copy a head's rows in whole groups (the device copy moves 16-byte
+// pieces); a model whose context is no whole number of groups is refused at create.
+static int64_t kv_q8_row_group(int64_t D) {
+    const int64_t rowb = D / 32 * 34;
+    int64_t g = 1;
+    while ((g * rowb) % 16 != 0) g *= 2;
+    return g;
+}
+// The Q8_0 ring paths hand ggml two tensors it did not lay out itself. Both rest on what this ggml does: a tensor's type, ne and nb are read as they
+// stand (nothing re-derives strides from the type, or checks a view against the type of its view_src), and the graph allocator leaves a tensor alone
+// whose data is already set.
+//   place_in    `t`, a fresh op result, computes into `store` at byte offset `off` instead of into the graph buffer
+//   words_view  `v`, a [D, 1, H] view of a quantised ring column, becomes I32 [words, 1, H]: per head one run of `words` 32-bit words from the head's
+//               first row on (nb[2] stays the ring's head stride) - whole ring rows moved as a plain type
+static T place_in(T t, T store, size_t off) { t->data = (char *) store->data + off; t->buffer = store->buffer; return t; }
+static T words_view(T v, int64_t words) { v->type = GGML_TYPE_I32; v->ne[0] = words; v->nb[0] = 4; v->nb[1] = (size_t) words * 4; return v; }
 
 // create_bias_pattern(capacity, t, hi = 0, lo = -inf) (torch.h:170-203)
 T create_bias_pattern(ggml_backend_t be, Transformer & tr, int Tn) {
@@ -506,10 +523,8 @@ T attention(Builder & c, const Transformer & tr, Layer & L, int wi, T indices, T
         // Q8_0 rings: mul_mat above is vec_dot_q8_0_q8_0 against the quantised q; P x V runs over the dequantised ring, get_rows(v, 0 .. C-1) -
         // F32 x F32, p unrounded. The two large interiors live in the transformer's shared work tensors, not in the graph buffer.
         T iota = ggml_view_3d(c, tr.kv_iota, v->ne[1], v->ne[2], v->ne[3], 0, 0, 0);   // [C, H, B]: the same C indices for every head and column
-        T vf = ggml_get_rows(c, v, iota);
-        vf->data = tr.kv_vf->data; vf->buffer = tr.kv_vf->buffer;
-        v = ggml_cont(c, ggml_transpose(c, vf));
-        v->data = tr.kv_vt->data; v->buffer = tr.kv_vt->buffer;
+        T vf = place_in(ggml_get_rows(c, v, iota), tr.kv_vf, 0);
+        v = place_in(ggml_cont(c, ggml_transpose(c, vf)), tr.kv_vt, 0);
     } else
         v = ggml_cont(c, ggml_transpose(c, v));
     T o = ggml_mul_mat(c, v, w);
@@ -1055,7 +1070,7 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
             }
         }
         if (m->n_streams > 1) {   // moshi_kv_cache_state with batch_size = B (transformer.h:155-171); decoder slots: the codec transformer's rings too
-            const enum ggml_type ring_type = m->cfg.kv_q8 && &tr == &m->temporal ? GGML_TYPE_Q8_0 : GGML_TYPE_BF16;   // (kv_q8: the Temporal rings alone)
+            const enum ggml_type ring_type = (m->cfg.kv_q8 & 1) && &tr == &m->temporal ? GGML_TYPE_Q8_0 : GGML_TYPE_BF16;   // (kv_q8: the Temporal rings alone)
             L.kcache = state4(m, ring_type, dim / heads, capacity, heads, m->n_streams);
             L.vcache = state4(m, ring_type, dim / heads, capacity, heads, m->n_streams);
         } else {
@@ -1076,7 +1091,7 @@ void make_transformer(moshi_hot_model * m, Transformer & tr, const std::string &
             }
         }
     }
-    if (m->n_streams > 1 && m->cfg.kv_q8 && &tr == &m->temporal && !norms_only) {
+    if (m->n_streams > 1 && (m->cfg.kv_q8 & 1) && &tr == &m->temporal && !norms_only) {
         tr.kv_iota = state(m, GGML_TYPE_I32, capacity);   // filled with 0 .. C-1 once the state buffer exists (create_model)
         tr.kv_vf = state4(m, GGML_TYPE_F32, dim / heads, capacity, heads, m->n_streams);
         tr.kv_vt = state4(m, GGML_TYPE_F32, capacity, dim / heads, heads, m->n_streams);
@@ -1395,6 +1410,9 @@ extern "C" moshi_hot_model_t * moshi_hot_create_slots(ggml_backend_t backend, co
 // snapshot calls refuse it (moshi_hot_slots_replay, moshi_hot_slot_fork_full / _save_full / _load_full take it)
 // (PersonaPlex's 16 / 16 is not it: 8 of its codebooks are inputs, it has provided frames and no conditions - prefill and the plain snapshot calls take it)
 static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m->cfg.n_q == m->cfg.dep_q && !m->cfg.personaplex; }
+// kv_q8: the Temporal rings are Q8_0 (bit 0); may a slot be given a history - block-form prefill, fork, save, load (BF16 rings always, Q8_0 rings with bit 1)
+static bool kv_q8_rings(const moshi_hot_model * m) { return m->temporal.layers[0].kcache->type == GGML_TYPE_Q8_0; }
+static bool kv_histories(const moshi_hot_model * m) { return !kv_q8_rings(m) || (m->cfg.kv_q8 & 2); }
 // the PersonaPlex shape of a B > 1 model (create_columns admits it with persona_columns alone)
 static bool persona_shape(const moshi_hot_model * m) { return m->n_streams > 1 && m->cfg.personaplex; }
 // slot b of a slots model, or NULL (a bad index or a model of another kind)
@@ -1506,6 +1524,10 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     if (cfg->kv_q8) {   // Q8_0 K / V rings: B-column LM models alone, whole blocks of 32 per head row, on a backend that can store rows into such a ring
         if (n_streams < 2 || (kind != ModelKind::lockstep && kind != ModelKind::slots) || cfg->persona_columns || cfg->personaplex || !cfg->enable_lm ||
             cfg->num_heads < 1 || cfg->dim % cfg->num_heads != 0 || (cfg->dim / cfg->num_heads) % 32 != 0) return nullptr;
+        // the field is a set of bits: 1 the ring type, 2 histories (prefill and snapshots) over such rings; 2 alone and any other bit mean nothing
+        if (cfg->kv_q8 != 1 && cfg->kv_q8 != 3) return nullptr;
+        // snapshots copy whole 16-byte pieces of a head's rows (kv_snapshot_rows): the ring must hold a whole number of such row groups
+        if ((cfg->kv_q8 & 2) && cfg->context % kv_q8_row_group(cfg->dim / cfg->num_heads) != 0) return nullptr;
         struct ggml_context * pc = ggml_init({ ggml_tensor_overhead() * 8, NULL, true });
         T ring = ggml_new_tensor_2d(pc, GGML_TYPE_Q8_0, 32, 1), row = ggml_new_tensor_2d(pc, GGML_TYPE_F32, 32, 1), at = ggml_new_tensor_1d(pc, GGML_TYPE_I32, 1);
         const bool ok = ggml_backend_supports_op(backend, ggml_set_rows(pc, ring, row, at));
@@ -2789,7 +2811,13 @@ T attention_jobs(Builder & c, const Transformer & tr, Layer & L, T x, const std:
         v = ggml_set_rows(c, vring, v, j.indices);
         T w = ggml_mul_mat(c, k, q);
         w = ggml_soft_max_ext(c, w, j.mask, 1.f / sqrtf((float) D), 0.0f);
-        v = ggml_cont(c, ggml_transpose(c, v));
+        if (v->type == GGML_TYPE_Q8_0) {
+            // Q8_0 rings (attention() above has the form): the two F32 interiors of P x V live in column b_j's slice of the transformer's shared work
+            // tensors, so the jobs of a pass - each on a column of its own - do not overwrite each other where the nodes run one by one
+            T vf = place_in(ggml_get_rows(c, v, ggml_view_2d(c, tr.kv_iota, C, H, 0, 0)), tr.kv_vf, (size_t) j.b * tr.kv_vf->nb[3]);
+            v = place_in(ggml_cont(c, ggml_transpose(c, vf)), tr.kv_vt, (size_t) j.b * tr.kv_vt->nb[3]);
+        } else
+            v = ggml_cont(c, ggml_transpose(c, v));
         T o = ggml_mul_mat(c, v, w);
         T dst = ggml_view_3d(c, out, D, H, j.n, (size_t) D * 4, out_row, (size_t) ((int64_t) (j.row - out_at) * (int64_t) out_row));
         out = ggml_cpy(c, ggml_permute(c, o, 0, 2, 1, 3), dst);
@@ -2945,7 +2973,7 @@ void cut_passes(moshi_hot_model * m, int n_jobs, const int32_t * slots, const in
 // replay: moshi_hot_slots_replay - the same passes over history frames of a tts-shaped model (which has no provided frames: needed_tokens == 0,
 // lm.h:807-809), and of no other; the prefill calls keep refusing that shape.
 int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end, bool replay = false) {
-    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;   // (batched passes over Q8_0 rings are not built)
+    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams || !kv_histories(m) || (kv_q8_rings(m) && (past_end || replay))) return -1;   // (over Q8_0 rings: block-form passes alone)
     const int ncb = m->cfg.n_q + 1;
     const int64_t C = m->temporal.capacity;
     int total = 0;
@@ -3117,8 +3145,18 @@ struct Fingerprint {
     uint64_t h = 0xcbf29ce484222325ull;
     void mix(int64_t v) { for (int i = 0; i < 8; i++) h = (h ^ (uint8_t) ((uint64_t) v >> (8 * i))) * 0x100000001b3ull; }
 };
-// the K / V part of a blob: per layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous)
-int64_t ring_bytes(const Transformer & tr, int64_t n_rows) { return 2 * (int64_t) tr.layers.size() * (int64_t) tr.dim * n_rows * 2; }
+// the ring rows a snapshot of n live rows copies per head: n, or over Q8_0 rings n rounded up to whole row groups (kv_q8_row_group: the device copy moves
+// 16-byte pieces and a Q8_0 row is 136 or 68 bytes). The rows past n are whatever the ring held - never read before the conversation rewrites them.
+int64_t kv_snapshot_rows(const Transformer & tr, int64_t n) {
+    if (tr.layers[0].kcache->type != GGML_TYPE_Q8_0) return n;
+    const int64_t g = kv_q8_row_group(tr.dim / tr.heads);
+    return (n + g - 1) / g * g;
+}
+// the K / V part of a blob: per layer K and then V as H x n_rows x D BF16 (what a [D, n_rows, H] view of the slot's ring column holds, made contiguous);
+// over Q8_0 rings as H x kv_snapshot_rows(n_rows) rows of D / 32 Q8_0 blocks, the ring's own bytes
+int64_t ring_bytes(const Transformer & tr, int64_t n_rows) {
+    return 2 * (int64_t) tr.layers.size() * (int64_t) tr.heads * kv_snapshot_rows(tr, n_rows) * (int64_t) ggml_row_size(tr.layers[0].kcache->type, tr.dim / tr.heads);
+}
 
 // column b of a state tensor: its first `dims` dimensions at b * nb[batch_dim]. In a blob and in the staging tensor a column is padded to 16 bytes.
 struct ColumnCopy { T t; int dims, batch_dim; };
@@ -3149,12 +3187,20 @@ void state_graph(moshi_hot_model * m, const Transformer & tr, int64_t n, const s
     Builder & s = *m->scratch;
     const int64_t H = tr.heads, D = tr.dim / H;
     const bool staged = src < 0 || dst < 0;
-    T stage = staged && n > 0 ? s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size()) : nullptr;
+    // Q8_0 rings: a head's rows travel as the words they are stored in - I32 [words, 1, H] views of the ring column and of an I32 staging tensor, the
+    // same run of bytes per head as the BF16 form's [D, n, H] views (a copy of one plain type on every backend, one k_ring_copy job on the device)
+    const bool q8 = n > 0 && tr.layers[0].kcache->type == GGML_TYPE_Q8_0;
+    const int64_t words = q8 ? kv_snapshot_rows(tr, n) * (int64_t) ggml_row_size(GGML_TYPE_Q8_0, D) / 4 : 0;
+    T stage = !(staged && n > 0) ? nullptr : q8 ? s.tensor(GGML_TYPE_I32, words, 1, H, 2 * (int64_t) tr.layers.size()) : s.tensor(GGML_TYPE_BF16, D, n, H, 2 * (int64_t) tr.layers.size());
     T col_stage = staged ? s.tensor(GGML_TYPE_F32, staged_bytes(copies) / 4) : nullptr;
-    auto ring_rows_of = [&](T ring, int b) { return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]); };
+    auto ring_rows_of = [&](T ring, int b) {
+        if (!q8) return ggml_view_3d(s, ring, D, n, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]);
+        return words_view(ggml_view_3d(s, ring, D, 1, H, ring->nb[1], ring->nb[2], (size_t) b * ring->nb[3]), words);
+    };
     int64_t j = 0;
     if (n > 0) for (const Layer & L : tr.layers) for (T ring : { L.kcache, L.vcache }) {
-        T part = stage ? ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]) : nullptr;
+        T part = !stage ? nullptr : q8 ? ggml_view_3d(s, stage, words, 1, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3])
+                                       : ggml_view_3d(s, stage, D, n, H, stage->nb[1], stage->nb[2], (size_t) j * stage->nb[3]);
         j++;
         s.expand(ggml_cpy(s, src >= 0 ? ring_rows_of(ring, src) : part, dst >= 0 ? ring_rows_of(ring, dst) : part));
     }
@@ -3265,7 +3311,7 @@ void slot_state_graph(moshi_hot_model * m, int src, int dst, int64_t n, const vo
 // full: the _full calls, which take a tts-shaped model (and are the plain calls on any other); the plain calls refuse it
 int slot_fork(moshi_hot_model_t * m, int src, int dst, bool full) {
     moshi_hot_model::Column * a = slot(m, src), * b = slot(m, dst);
-    if (!a || !b || src == dst || !a->open || b->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!a || !b || src == dst || !a->open || b->open || (tts_shape(m) && !full) || !kv_histories(m) || (kv_q8_rings(m) && tts_shape(m))) return -1;
     slot_state_graph(m, src, dst, slot_live_rows(m, *a), nullptr, nullptr, nullptr, nullptr, tts_shape(m));
     *b = *a;
     b->held = false;
@@ -3276,7 +3322,7 @@ int slot_fork(moshi_hot_model_t * m, int src, int dst, bool full) {
 
 int64_t slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes, bool full) {
     const moshi_hot_model::Column * col = slot(m, b);
-    if (!col || !col->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || !col->open || (tts_shape(m) && !full) || !kv_histories(m) || (kv_q8_rings(m) && tts_shape(m))) return -1;
     const int64_t n = slot_live_rows(m, *col), host = slot_host_bytes(m);
     SlotBlobHeader h;
     memset(&h, 0, sizeof(h));
@@ -3299,7 +3345,7 @@ int64_t slot_save(moshi_hot_model_t * m, int b, void * buf, int64_t nbytes, bool
 
 int slot_load(moshi_hot_model_t * m, int b, const void * buf, int64_t nbytes, bool full) {
     moshi_hot_model::Column * col = slot(m, b);
-    if (!col || col->open || (tts_shape(m) && !full) || m->temporal.layers[0].kcache->type != GGML_TYPE_BF16) return -1;
+    if (!col || col->open || (tts_shape(m) && !full) || !kv_histories(m) || (kv_q8_rings(m) && tts_shape(m))) return -1;
     SlotBlobHeader h;
     const int32_t * ring = (const int32_t *) blob_load_begin(buf, nbytes, SLOT_BLOB_MAGIC, slot_version(m), slot_fingerprint(m), h);
     if (!ring) return -1;
