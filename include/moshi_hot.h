@@ -104,7 +104,10 @@ struct moshi_hot_config {
     // bytes; the rows past the live count are whatever the ring held and are never read before they are rewritten); NULL with 3 when context is no whole
     // number of groups. The fingerprint holds the ring type: a BF16 model refuses such a blob and the other way round. Still -1 with 3:
     // moshi_hot_slots_prefill_long, moshi_hot_slots_replay, moshi_hot_slots_persona, the _full calls on a tts-shaped model. A model that only steps
-    // computes with 3 what it computes with 1. 2, or any other bit: NULL.
+    // computes with 3 what it computes with 1. 7 (bits 0, 1 and 2): everything 3 does and, under 3's conditions at create, histories that pass the
+    // ring's end - moshi_hot_slots_prefill_long / moshi_hot_slot_prefill_long on the moshika and stt shapes, with the arguments, return values and
+    // remaining refusals they have over BF16 rings; the ring-ordered rows of each Temporal layer of a pass are one k_attn_rows_q8 launch.
+    // moshi_hot_slots_replay, moshi_hot_slots_persona and the _full calls on a tts-shaped model stay -1 with 7. 2, 4, 5, 6, or any other bit: NULL.
     // (It sits in front of f32_matrix: tests pin f32_matrix and float_accumulate as the struct's last two fields.)
     int32_t kv_q8;
     // 1: the create calls switch the handle the model is created on to the f64-MFMA mat-mul for F32 weights, ggml_backend_mi355x_set_f32_matrix(backend, 1):

@@ -28,6 +28,7 @@
 //             dim 16 dt + r (the product of an F16 and an int8 is exact in float), D[row g + 4 q][dim 16 dt + r] in register q. The D / 16 dim tiles
 //             are dealt to the waves (two each at D = 128, one at 64); each accumulates over ALL slots in ascending order; one rounding to float.
 //   A slot past a row's own live end carries p = 0 through the mask; a row with no live slot writes zeros. A row's bits depend on its own job alone.
+//   Everything behind the head is attn_q8b_walks, a function: the rows form (hip_attn_q8_rows.h) runs the same walks with an overlay of new rows.
 #pragma once
 
 #define ATTN_Q8B_ROWS 16   // query rows of a workgroup: the M of both matrix instructions
@@ -42,6 +43,16 @@ template <int D> struct attn_q8b_shape {
     static constexpr int SMEM = O_REDI + 16;
     static_assert(SMEM <= 64 * 1024 && O_KIMG % 16 == 0 && O_REDD % 8 == 0 && PITCH % 8 == 0, "LDS of the attend launch: under the 64 KB every launch may have");
 };
+
+// what the three walks work in (LDS): the two raw tile buffers, the aligned K image and its scales, the probability tile, the quantised query rows and
+// their scales, the reduction rows, the row maxima and reciprocal sums
+struct attn_q8b_lds { char * buf0, * buf1, * kimg; uint16_t * kd; float * P; const char * qq; const float * qd; double * redd; float * redf, * rmax, * rinv; };
+// the rows form's overlay (hip_attn_q8_rows.h): n <= 16 new rows that stand in LDS and not yet in the ring - K as an aligned image (row j at kimg + j * PITCH,
+// scales kd[j * NBLK + block]), V in ggml's row format, slot[j] the ring slot row j will take (-1: none; 16 entries)
+struct attn_q8b_overlay { const char * kimg = nullptr; const uint16_t * kd = nullptr; const char * vrows = nullptr; const int * slot = nullptr; int n = 0; };
+template <int D, bool OV>
+__device__ __forceinline__ void attn_q8b_walks(const attn_q8b_lds & m, const attn_q8b_overlay & ov, const char * kring, const char * vring, const float * (&mrow)[4],
+                                               int nrows, int n_end, int C, float scale, float * out, int64_t out_ts);
 
 // ---- write launch ------------------------------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -112,13 +123,12 @@ template <int D> __device__ __forceinline__ void attn_q8b_repack(const char * bu
     }
 }
 
-// the scores of rows 4 g + q, q = 0 .. 3, of the workgroup against slot c = c0 + 16 grp + r of the tile in the K image: sv[q], masked and scaled
-// (mrow[q]: the mask row of row 4 g + q, NULL for a row past the job's end; a slot at or past C is masked)
-template <int D> __device__ __forceinline__ void attn_q8_tile_scores(const char * qq, const float * qd, const char * kimg, const uint16_t * kd, const float * (&mrow)[4],
-                                                                     int c0, int grp, int C, float scale, float (&sv)[4]) {
+// the block terms of rows 4 g + q, q = 0 .. 3, of the workgroup against slot sl = 16 grp + r of the K image, added in float in block order: sumf[q]
+template <int D> __device__ __forceinline__ void attn_q8_tile_dots(const char * qq, const float * qd, const char * kimg, const uint16_t * kd, int grp, float (&sumf)[4]) {
     constexpr int NBLK = attn_q8_shape<D>::NBLK, PITCH = attn_q8b_shape<D>::PITCH;
-    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, sl = 16 * grp + r, c = c0 + sl;
-    float sumf[4] = { 0.f, 0.f, 0.f, 0.f };
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4, sl = 16 * grp + r;
+#pragma unroll
+    for (int q = 0; q < 4; q++) sumf[q] = 0.f;
 #pragma unroll
     for (int j = 0; j < NBLK; j++) {
         const long aq = *(const long *) (qq + r * PITCH + 32 * j + 8 * g), bk = *(const long *) (kimg + sl * PITCH + 32 * j + 8 * g);
@@ -128,25 +138,35 @@ template <int D> __device__ __forceinline__ void attn_q8_tile_scores(const char 
 #pragma unroll
         for (int q = 0; q < 4; q++) sumf[q] += (float) dot[q] * (dk * qd[(4 * g + q) * NBLK + j]);
     }
+}
+// soft_max's input from the summed block terms and the mask value m of the (row, slot) pair (-inf: the pair is closed)
+__device__ __forceinline__ float attn_q8_masked_score(float sumf, float scale, float m) {
+    float sv = -INFINITY;
+    if (m > -INFINITY) { sv = sumf * scale; sv = sv + m; }
+    return sv;
+}
+// the scores of rows 4 g + q, q = 0 .. 3, of the workgroup against slot c = c0 + 16 grp + r of the tile in the K image: sv[q], masked and scaled
+// (mrow[q]: the mask row of row 4 g + q, NULL for a row past the job's end; a slot at or past C is masked)
+template <int D> __device__ __forceinline__ void attn_q8_tile_scores(const char * qq, const float * qd, const char * kimg, const uint16_t * kd, const float * (&mrow)[4],
+                                                                     int c0, int grp, int C, float scale, float (&sv)[4]) {
+    const int c = c0 + 16 * grp + (threadIdx.x & 15);
+    float sumf[4];
+    attn_q8_tile_dots<D>(qq, qd, kimg, kd, grp, sumf);
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float m = mrow[q] && c < C ? mrow[q][c] : -INFINITY;
-        sv[q] = -INFINITY;
-        if (m > -INFINITY) { sv[q] = sumf[q] * scale; sv[q] = sv[q] + m; }
-    }
+    for (int q = 0; q < 4; q++) sv[q] = attn_q8_masked_score(sumf[q], scale, mrow[q] && c < C ? mrow[q][c] : -INFINITY);
 }
 
 template <int D>
 __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(attn_blocks_args ba) {
     typedef attn_q8_shape<D> S;
     typedef attn_q8b_shape<D> L;
-    constexpr int NBLK = S::NBLK, ROWB = S::ROWB, TILE = ATTN_Q8_TILE, half = D / 2, PITCH = L::PITCH, PP = ATTN_Q8B_PP, R = ATTN_Q8B_ROWS, LPR = D / 4, NDT = D / 64;
+    constexpr int NBLK = S::NBLK, half = D / 2, PITCH = L::PITCH, R = ATTN_Q8B_ROWS, LPR = D / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const attn_block_job & jb = ba.job[blockIdx.z];
     const int r0 = (int) blockIdx.x * R;
     if (r0 >= jb.T) return;                                                 // (the grid is as wide as the longest job)
     const attn_args & a = ba.a;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4;
     const int h = blockIdx.y, C = a.C, nrows = jb.T - r0 < R ? jb.T - r0 : R;
 
     char * const buf0 = smem, * const buf1 = smem + S::BUF_Q8_BYTES;          // the two tile buffers
@@ -156,10 +176,8 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
     double * redd = (double *) (smem + L::O_REDD); float * redf = (float *) (smem + L::O_REDF);
     float * rmax = (float *) (smem + L::O_STAT), * rinv = rmax + R;
     int * redi = (int *) (smem + L::O_REDI);
-    auto buf_of = [&](int t) { return (t & 1) ? buf1 : buf0; };
 
     const char * kring = jb.kcache + (int64_t) h * a.k_nb2, * vring = jb.vcache + (int64_t) h * a.v_nb2;
-    const int koff = (int) ((uintptr_t) kring & 15), voff = (int) ((uintptr_t) vring & 15);   // (a tile is a multiple of 16 bytes: every tile of a ring has its alignment)
     float * out = jb.out + (int64_t) r0 * a.out_ts + (int64_t) h * D;
 
     // ---- head: the q rows, rotated and quantised; the live end of the tile's rows ----------------------------------------------------------------
@@ -202,11 +220,78 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
         for (int i = tid; i < nrows * D; i += ATTN_Q8_THREADS) out[(int64_t) (i / D) * a.out_ts + i % D] = 0.f;
         return;
     }
-    const int NT = (n_end + TILE - 1) / TILE;
-    auto tile_end = [&](int t) { const int e = (t + 1) * TILE; return e < n_end ? e : n_end; };
     const float * mrow[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) mrow[q] = 4 * g + q < nrows ? jb.mask + (int64_t) (r0 + 4 * g + q) * C : nullptr;
+    const attn_q8b_lds m = { buf0, buf1, kimg, kd, P, qq, qd, redd, redf, rmax, rinv };
+    attn_q8b_walks<D, false>(m, attn_q8b_overlay(), kring, vring, mrow, nrows, n_end, C, a.scale, out, a.out_ts);
+}
+
+// THE THREE WALKS of a workgroup whose 16 query rows stand quantised in LDS (m.qq, m.qd), over slots [0, n_end) of the head's ring column, n_end >= 1:
+// row r of the workgroup (r < nrows) under its mask row mrow, its output row at out + r * out_ts. Shared with the rows form (hip_attn_q8_rows.h), which
+// instantiates OV: ring slots one of its overlay rows has rewritten are switched off per (row, slot) pair and the overlay is one more 16-slot group
+// behind the last tile, through the same score function in all three walks. Without OV this is the attend launch's code, instruction for instruction.
+template <int D, bool OV>
+__device__ __forceinline__ void attn_q8b_walks(const attn_q8b_lds & m, const attn_q8b_overlay & ov, const char * kring, const char * vring, const float * (&mrow)[4],
+                                               int nrows, int n_end, int C, float scale, float * out, int64_t out_ts) {
+    typedef attn_q8_shape<D> S;
+    constexpr int ROWB = S::ROWB, TILE = ATTN_Q8_TILE, PP = ATTN_Q8B_PP, R = ATTN_Q8B_ROWS, NDT = D / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
+    char * const buf0 = m.buf0, * const buf1 = m.buf1, * const kimg = m.kimg;
+    uint16_t * const kd = m.kd;
+    float * const P = m.P, * const redf = m.redf, * const rmax = m.rmax, * const rinv = m.rinv;
+    double * const redd = m.redd;
+    auto buf_of = [&](int t) { return (t & 1) ? buf1 : buf0; };
+    const int koff = (int) ((uintptr_t) kring & 15), voff = (int) ((uintptr_t) vring & 15);   // (a tile is a multiple of 16 bytes: every tile of a ring has its alignment)
+    const int NT = (n_end + TILE - 1) / TILE;
+    auto tile_end = [&](int t) { const int e = (t + 1) * TILE; return e < n_end ? e : n_end; };
+    int ovs[OV ? R : 1];   // OV: the overlay rows' ring slots (-1: none)
+    if constexpr (OV) {
+#pragma unroll
+        for (int j = 0; j < R; j++) ovs[j] = ov.slot[j];
+    }
+    // a tile's scores (attn_q8_tile_scores); OV: a pair whose ring slot an overlay row j <= row has rewritten is closed
+    auto scores = [&](int c0, int grp, float (&sv)[4]) {
+        attn_q8_tile_scores<D>(m.qq, m.qd, kimg, kd, mrow, c0, grp, C, scale, sv);
+        if constexpr (OV) {
+            const int c = c0 + 16 * grp + r;
+            int first = R;
+#pragma unroll
+            for (int j = R - 1; j >= 0; j--) if (ovs[j] == c) first = j;
+#pragma unroll
+            for (int q = 0; q < 4; q++) if (4 * g + q >= first) sv[q] = -INFINITY;
+        }
+    };
+    // OV: the overlay as a 16-slot group - overlay row r against the workgroup's rows; row i sees it from i = r on until a later overlay row takes its slot
+    auto overlay_scores = [&](float (&sv)[4]) {
+        const int cj = ov.slot[r];
+        int next = R;
+#pragma unroll
+        for (int j = R - 1; j > 0; j--) if (j > r && ovs[j] == cj) next = j;
+        float sumf[4];
+        attn_q8_tile_dots<D>(m.qq, m.qd, ov.kimg, ov.kd, 0, sumf);
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int i = 4 * g + q;
+            sv[q] = attn_q8_masked_score(sumf[q], scale, cj >= 0 && r <= i && i < next && mrow[q] ? mrow[q][cj] : -INFINITY);
+        }
+    };
+    // P x V over `nslots` slots of V rows in ggml's row format at vrows, their probabilities in P's columns 0 .. nslots - 1
+    auto pv_steps = [&](const char * vrows, int nslots, f64x4_t (&acc)[NDT]) {
+        const int steps = (nslots + 3) / 4;
+        for (int s = 0; s < steps; s++) {
+            const int sl = 4 * s + g;
+            const double pa = (double) P[r * PP + sl];
+            const char * vrow = vrows + sl * ROWB;
+#pragma unroll
+            for (int i = 0; i < NDT; i++) {
+                const int dim = 16 * (wave * NDT + i) + r;
+                const char * blk = vrow + (dim >> 5) * 34;
+                const float v = sl < nslots ? h2f(*(const uint16_t *) blk) * (float) *(const int8_t *) (blk + 2 + (dim & 31)) : 0.f;   // (exact: 11 x 8 significant bits)
+                acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa, (double) v, acc[i], 0, 0, 0);
+            }
+        }
+    };
 
     attn_q8_u32x4 regs[S::NPIECE], vregs[S::NPIECE];   // a tile's pieces between their request and their store to LDS
     uint32_t edge, vedge;
@@ -228,7 +313,7 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 float sv[4];
-                attn_q8_tile_scores<D>(qq, qd, kimg, kd, mrow, t * TILE, 2 * wave + i, C, a.scale, sv);
+                scores(t * TILE, 2 * wave + i, sv);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     if (walk == 0) mx[q] = fmaxf(mx[q], sv[q]);
@@ -237,6 +322,15 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
             }
             if (t + 1 < NT) attn_q8_store<D>(regs, edge, buf_of(t + 1), kring, (t + 1) * TILE, tile_end(t + 1));
             __syncthreads();
+        }
+        if constexpr (OV) if (wave == 0) {   // the overlay group: wave 0's lanes add it behind their ring slots
+            float sv[4];
+            overlay_scores(sv);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                if (walk == 0) mx[q] = fmaxf(mx[q], sv[q]);
+                else ds[q] += (double) (sv[q] > -INFINITY ? expf(sv[q] - rm[q]) : 0.f);
+            }
         }
         // a row's value over the sixteen lanes that hold its slots, then over the waves in index order
 #pragma unroll
@@ -285,7 +379,7 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             float sv[4];
-            attn_q8_tile_scores<D>(qq, qd, kimg, kd, mrow, c0, 2 * wave + i, C, a.scale, sv);
+            scores(c0, 2 * wave + i, sv);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const float e = sv[q] > -INFINITY ? expf(sv[q] - rm[q]) : 0.f;
@@ -293,19 +387,7 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
             }
         }
         __syncthreads();
-        const int steps = (c_hi - c0 + 3) / 4;
-        for (int s = 0; s < steps; s++) {
-            const int sl = 4 * s + g;
-            const double pa = (double) P[r * PP + sl];
-            const char * vrow = buf1 + voff + sl * ROWB;
-#pragma unroll
-            for (int i = 0; i < NDT; i++) {
-                const int dim = 16 * (wave * NDT + i) + r;
-                const char * blk = vrow + (dim >> 5) * 34;
-                const float v = c0 + sl < c_hi ? h2f(*(const uint16_t *) blk) * (float) *(const int8_t *) (blk + 2 + (dim & 31)) : 0.f;   // (exact: 11 x 8 significant bits)
-                acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa, (double) v, acc[i], 0, 0, 0);
-            }
-        }
+        pv_steps(buf1 + voff, c_hi - c0, acc);
         __syncthreads();
         if (t + 1 < NT) {
             attn_q8_store<D>(regs, edge, buf0, kring, (t + 1) * TILE, tile_end(t + 1));
@@ -313,12 +395,25 @@ __global__ void __launch_bounds__(ATTN_Q8_THREADS) attn_blocks_q8_attend_kernel(
             __syncthreads();
         }
     }
+    if constexpr (OV) {   // the overlay group behind the last tile (the barrier above: the probability tile is free)
+        if (wave == 0) {
+            float sv[4];
+            overlay_scores(sv);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float e = sv[q] > -INFINITY ? expf(sv[q] - rm[q]) : 0.f;
+                P[(4 * g + q) * PP + r] = e * ri[q];
+            }
+        }
+        __syncthreads();
+        pv_steps(ov.vrows, ov.n, acc);
+    }
 #pragma unroll
     for (int i = 0; i < NDT; i++)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int row = g + 4 * q;
-            if (row < nrows) out[(int64_t) row * a.out_ts + 16 * (wave * NDT + i) + r] = (float) acc[i][q];
+            if (row < nrows) out[(int64_t) row * out_ts + 16 * (wave * NDT + i) + r] = (float) acc[i][q];
         }
 }
 

@@ -3120,24 +3120,29 @@ static void pass_norm_affine(planner & pl) {
 // pass takes leaves the list of groups to emit (emit_pos = -1) and belongs to one rows job only. A run that cannot be proven regular is declined: it
 // stays with merge_column_attention_blocks, which never puts two groups of one ring column into a launch pair - a declined row shares a pair only with
 // groups of other columns and the pairs run in node order: correct, only slower. A lone one-row group is a block of one row and stays with the block launches. Runs before merge_column_attention_blocks.
+// Q8_0 RINGS (moshi_hot_config::kv_q8 = 7): the same runs, at most ATTN_ROWS_Q8_MAX_N rows each and only where k_attn_rows_q8_supported holds, become jobs of
+// a k_attn_rows_q8 launch (row-parallel: the job's rows attend at once, hip_attn_q8_rows.h); a launch holds jobs of one ring type. The ring slots are an
+// uploaded index the plan cannot read: the kernel applies the visibility rule to the slots it finds there, whatever they are.
 static bool no_attn_rows() { static const bool off = getenv("MI355X_NO_ATTN_ROWS") != nullptr; return off; }
 static void pass_column_attention_rows(planner & pl) {
     if (no_attn_rows()) return;
     std::vector<attn_group> & groups = pl.attn_groups;
     std::vector<size_t> order;   // the column groups in emit order (the order their outputs stand in the graph)
-    for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1 && !groups[i].q8) order.push_back(i);   // (k_attn_rows reads BF16 rings)
+    for (size_t i = 0; i < groups.size(); i++) if (groups[i].column && groups[i].emit_pos >= 0 && groups[i].B == 1) order.push_back(i);
     std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return groups[x].emit_pos < groups[y].emit_pos; });
     auto same_shape = [](const attn_args & a, const attn_args & b) { return b.T == 1 && same_attention_shape(a, b); };   // rows: one-row groups only
     auto stride = [](const void * a, const void * b) { return (int64_t) ((const char *) b - (const char *) a); };
     attn_rows_args ra;
     int launch_hi = -1;           // emit position of the launch being filled (ra.n_jobs > 0)
+    bool launch_q8 = false;       // its ring type: a launch holds jobs of one
     std::set<int> rows_inside;    // the members of the rows jobs of that launch
     auto flush = [&]() {
         if (!ra.n_jobs) return;
         const attn_rows_args la = ra;
         unsigned * err = pl.c->err_dev;
+        const bool q8 = launch_q8;
         auto & at = pl.at_pos[launch_hi];
-        at.insert(at.begin(), [=](hipStream_t s) { k_attn_rows(s, la, err); });
+        at.insert(at.begin(), [=](hipStream_t s) { if (q8) k_attn_rows_q8(s, la); else k_attn_rows(s, la, err); });
         pl.p->n_attn_row_launches++; pl.p->n_attn_row_jobs += la.n_jobs;
         for (int j = 0; j < la.n_jobs; j++) pl.p->n_attn_row_rows += la.job[j].n;
         ra.n_jobs = 0;
@@ -3152,10 +3157,10 @@ static void pass_column_attention_rows(planner & pl) {
         attn_rows_job jb;
         memset(&jb, 0, sizeof(jb));
         if (a0.T == 1) {
-            while (oe < order.size() && oe - oi < 64) {
+            while (oe < order.size() && oe - oi < (size_t) (g0.q8 ? ATTN_ROWS_Q8_MAX_N : 64)) {
                 const attn_group & gn = groups[order[oe]];
                 const attn_args & b = gn.a, & prev = groups[order[oe - 1]].a;
-                if (!same_shape(a0, b) || b.kcache != a0.kcache || b.vcache != a0.vcache) break;
+                if (gn.q8 != g0.q8 || !same_shape(a0, b) || b.kcache != a0.kcache || b.vcache != a0.vcache) break;
                 const int64_t d[7] = { stride(prev.q, b.q), stride(prev.k, b.k), stride(prev.v, b.v), stride(prev.mask, b.mask), b.rot ? stride(prev.rot, b.rot) : 0,
                                        stride(prev.index, b.index), stride(prev.out, b.out) };
                 if (oe == oi + 1) { jb.q_rs = d[0]; jb.k_rs = d[1]; jb.v_rs = d[2]; jb.mask_rs = d[3]; jb.rot_rs = d[4]; jb.index_rs = d[5]; jb.out_rs = d[6]; }
@@ -3170,9 +3175,17 @@ static void pass_column_attention_rows(planner & pl) {
         }
         const int n = (int) (oe - oi);
         if (n < 2) { flush(); oi = oe; continue; }   // a block-form job (or a lone row): not this pass's; it also ends the layer's run of rows jobs
-        // a further rows job of the same launch: same shape, another column, nothing foreign between the launch so far and this job
+        jb.q = (const char *) a0.q; jb.k = (const char *) a0.k; jb.v = (const char *) a0.v; jb.kcache = a0.kcache; jb.vcache = a0.vcache;
+        jb.mask = (const char *) a0.mask; jb.rot = (const char *) a0.rot; jb.index = (const char *) a0.index; jb.out = (char *) a0.out; jb.n = n;
+        if (g0.q8) {   // Q8_0 rings: what k_attn_rows_q8 takes as a job; a run it does not take stays with the block launches
+            attn_rows_args one;
+            memset(&one, 0, sizeof(one));
+            one.a = a0; one.n_jobs = 1; one.job[0] = jb;
+            if (!k_attn_rows_q8_supported(one)) { flush(); oi = oe; continue; }
+        }
+        // a further rows job of the same launch: same shape and ring type, another column, nothing foreign between the launch so far and this job
         if (ra.n_jobs) {
-            bool joins = ra.n_jobs < ATTN_ROWS_MAX && same_shape(ra.a, a0);
+            bool joins = ra.n_jobs < ATTN_ROWS_MAX && launch_q8 == g0.q8 && same_shape(ra.a, a0);
             for (int j = 0; j < ra.n_jobs && joins; j++) joins = ra.job[j].kcache != a0.kcache && ra.job[j].vcache != a0.vcache;
             if (joins) {
                 std::set<int> both = inside;
@@ -3181,9 +3194,7 @@ static void pass_column_attention_rows(planner & pl) {
             }
             if (!joins) flush();
         }
-        if (!ra.n_jobs) { ra.a = a0; rows_inside.clear(); }
-        jb.q = (const char *) a0.q; jb.k = (const char *) a0.k; jb.v = (const char *) a0.v; jb.kcache = a0.kcache; jb.vcache = a0.vcache;
-        jb.mask = (const char *) a0.mask; jb.rot = (const char *) a0.rot; jb.index = (const char *) a0.index; jb.out = (char *) a0.out; jb.n = n;
+        if (!ra.n_jobs) { ra.a = a0; launch_q8 = g0.q8; rows_inside.clear(); }
         ra.job[ra.n_jobs++] = jb;
         rows_inside.insert(inside.begin(), inside.end());
         launch_hi = hi;

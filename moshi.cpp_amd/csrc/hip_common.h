@@ -280,6 +280,14 @@ struct attn_rows_job { const char * q, * k, * v; char * kcache, * vcache; const 
                        int64_t q_rs, k_rs, v_rs, mask_rs, rot_rs, index_rs, out_rs; int n; };   // *_rs: bytes from one row to the next
 struct attn_rows_args { attn_args a; int n_jobs; attn_rows_job job[ATTN_ROWS_MAX]; };
 void k_attn_rows(hipStream_t s, const attn_rows_args & a, unsigned * err = nullptr);
+// The same jobs over Q8_0 rings (moshi_hot_config::kv_q8 = 7; hip_attn_q8_rows.h): the same table, the ring strides in bytes of Q8_0 rows.
+// ROW-PARALLEL: workgroup (h, j) quantises the job's n_j rows, attends with all of them at once - a ring slot that a row j <= i of the job takes comes
+// from that row's quantised K / V in LDS, every other slot from the ring as the launch found it, so row i sees what stepping the rows one by one would
+// show it - and writes the rows to their ring slots afterwards. D 64 or 128, C <= 4096, 2 <= n_j <= 16 and n_j <= C, strides multiples of 4; one
+// launch, no workgroup waits for another, no workspace.
+#define ATTN_ROWS_Q8_MAX_N 16   // rows of a job: the query rows of one matrix instruction
+bool k_attn_rows_q8_supported(const attn_rows_args & a);
+void k_attn_rows_q8(hipStream_t s, const attn_rows_args & a);
 // rows consecutive rows of n floats, row r copied from its own source src[r] (stream slots: the B mask rows, each a window of the bias table at the
 // slot's own column, transformer.h:1259-1289) - one launch instead of one per row
 #define COPY_ROWS_MAX 64   // (64 pointers by value: 512 bytes of kernel arguments)

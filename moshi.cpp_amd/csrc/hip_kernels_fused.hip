@@ -1865,6 +1865,8 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
 #include "hip_attn_q8.h"
 // Slot prefill over the same rings: T new rows per job as a write launch and an int8-MFMA attend launch
 #include "hip_attn_q8_blocks.h"
+// Slot prefill past the ring's end over the same rings: a job's ring-ordered rows attend at once in one launch, then are written
+#include "hip_attn_q8_rows.h"
 
 // Decoder slots: workgroup (h, t, b) is attn_ring256_kernel's workgroup (h, t) over column b - its own q / k / v rows, ring column, mask rows, RoPE rows,
 // ring slots and output rows - so a column's two rows are computed exactly as the single-column launch computes them. Only workgroup (h, 0, b) writes

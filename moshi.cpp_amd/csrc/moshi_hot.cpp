@@ -1413,6 +1413,8 @@ static bool tts_shape(const moshi_hot_model * m) { return m->cfg.dep_q > 0 && m-
 // kv_q8: the Temporal rings are Q8_0 (bit 0); may a slot be given a history - block-form prefill, fork, save, load (BF16 rings always, Q8_0 rings with bit 1)
 static bool kv_q8_rings(const moshi_hot_model * m) { return m->temporal.layers[0].kcache->type == GGML_TYPE_Q8_0; }
 static bool kv_histories(const moshi_hot_model * m) { return !kv_q8_rings(m) || (m->cfg.kv_q8 & 2); }
+// ... and one that passes the ring's end - ring-ordered rows (BF16 rings always, Q8_0 rings with bit 2)
+static bool kv_long_histories(const moshi_hot_model * m) { return !kv_q8_rings(m) || (m->cfg.kv_q8 & 4); }
 // the PersonaPlex shape of a B > 1 model (create_columns admits it with persona_columns alone)
 static bool persona_shape(const moshi_hot_model * m) { return m->n_streams > 1 && m->cfg.personaplex; }
 // slot b of a slots model, or NULL (a bad index or a model of another kind)
@@ -1524,8 +1526,9 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     if (cfg->kv_q8) {   // Q8_0 K / V rings: B-column LM models alone, whole blocks of 32 per head row, on a backend that can store rows into such a ring
         if (n_streams < 2 || (kind != ModelKind::lockstep && kind != ModelKind::slots) || cfg->persona_columns || cfg->personaplex || !cfg->enable_lm ||
             cfg->num_heads < 1 || cfg->dim % cfg->num_heads != 0 || (cfg->dim / cfg->num_heads) % 32 != 0) return nullptr;
-        // the field is a set of bits: 1 the ring type, 2 histories (prefill and snapshots) over such rings; 2 alone and any other bit mean nothing
-        if (cfg->kv_q8 != 1 && cfg->kv_q8 != 3) return nullptr;
+        // the field is a set of bits: 1 the ring type, 2 histories (prefill and snapshots) over such rings, 4 histories past the ring's end
+        // (the _prefill_long calls); a bit without the ones below it and any other bit mean nothing
+        if (cfg->kv_q8 != 1 && cfg->kv_q8 != 3 && cfg->kv_q8 != 7) return nullptr;
         // snapshots copy whole 16-byte pieces of a head's rows (kv_snapshot_rows): the ring must hold a whole number of such row groups
         if ((cfg->kv_q8 & 2) && cfg->context % kv_q8_row_group(cfg->dim / cfg->num_heads) != 0) return nullptr;
         struct ggml_context * pc = ggml_init({ ggml_tensor_overhead() * 8, NULL, true });
@@ -2973,7 +2976,7 @@ void cut_passes(moshi_hot_model * m, int n_jobs, const int32_t * slots, const in
 // replay: moshi_hot_slots_replay - the same passes over history frames of a tts-shaped model (which has no provided frames: needed_tokens == 0,
 // lm.h:807-809), and of no other; the prefill calls keep refusing that shape.
 int slots_prefill(moshi_hot_model * m, int n_jobs, const int32_t * slots, const int32_t * const * tokens, const int32_t * n_frames, int chunk, bool past_end, bool replay = false) {
-    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams || !kv_histories(m) || (kv_q8_rings(m) && (past_end || replay))) return -1;   // (over Q8_0 rings: block-form passes alone)
+    if (m->kind != ModelKind::slots || tts_shape(m) != replay || n_jobs < 0 || n_jobs > m->n_streams || !kv_histories(m) || (past_end && !kv_long_histories(m)) || (kv_q8_rings(m) && replay)) return -1;   // (over Q8_0 rings: ring-ordered rows with kv_q8 = 7 alone, no replay)
     const int ncb = m->cfg.n_q + 1;
     const int64_t C = m->temporal.capacity;
     int total = 0;
