@@ -142,6 +142,7 @@ struct ggml_mi355x_stats {
     int64_t f32_matrix_mms_in_last_plan;        // k_mm_f32_batched launches of the last plan (F32 weights against 2..128 activation rows on f64 MFMA tiles, set_f32_matrix)
     int64_t convtr_matrix_groups_in_last_plan;  // B-column transposed-convolution groups of the last plan that are ONE k_convtr_cols_mfma launch (f64 MFMA tiles, no workspace; bit 1 of set_f32_matrix) - a subset of convtr_column_groups_in_last_plan
     int64_t q8_attention_blocks_in_last_plan;   // k_attn_streams_q8 launches of the last plan (B-column self-attention blocks over Q8_0 K / V rings, moshi_hot_config::kv_q8; in front of conv_matrix_groups_in_last_plan, which tests/test_conv_matrix_cpu.py pins as the last field)
+    int64_t q8_attention_split_blocks_in_last_plan;   // the same blocks of the last plan that run as the k_attn_streams_q8_split launch pair (each (head, column) split along the ring, ggml_backend_mi355x_set_attn_q8_split; 2 launches each, not counted in q8_attention_blocks_in_last_plan)
     int64_t conv_matrix_groups_in_last_plan;    // B-column convolution groups of the last plan that are ONE k_conv_cols_mfma launch ([elu] [concat + tail copy] im2col, product, bias [residual] on F16 MFMA tiles; bit 2 of set_f32_matrix)
 };
 GGML_API void ggml_backend_mi355x_get_stats(ggml_backend_t backend, struct ggml_mi355x_stats * stats);
@@ -213,6 +214,14 @@ GGML_API void ggml_backend_mi355x_set_float_accumulate(ggml_backend_t backend, i
 // padding; F32 weights, the single-column form and anything else keep today's launches. 4..7 combine it with the bits below; MI355X_MMF32=4..7
 // likewise. Bits above bit 2 are ignored.
 GGML_API void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t backend, int on);
+// The single-token self-attention block of B columns over Q8_0 K / V rings (moshi_hot_config::kv_q8, k_attn_streams_q8: one workgroup per (head, column)
+// walks the whole live ring) split along the ring: with n != 0 such a block is planned as the k_attn_streams_q8_split launch pair - S workgroups per
+// (head, column), a scores launch and a values launch with a last-arriver merge, no workgroup waiting for another - where S >= 2. 0 (a fresh handle):
+// never. 1: S = min(ceil(C / 256), 16, usable compute units / (H x B)) - one workgroup per compute unit; few columns over a long ring split, wide batches
+// keep the one launch. n >= 2: S = min(n, ceil(C / 256), 16), for tests and A/B runs. Ring bytes, scores and probabilities are the unsplit launch's
+// bits; the output differs in the grouping of its double sums alone and depends neither on S nor on B. A change drops the handle's cached plans;
+// ggml_backend_mi355x_init_stream inherits the value. Nothing to do on any other backend.
+GGML_API void ggml_backend_mi355x_set_attn_q8_split(ggml_backend_t backend, int n);
 // HIP stream the backend launches on (void* = hipStream_t) so callers can bracket it with HIP events
 GGML_API void * ggml_backend_mi355x_get_stream(ggml_backend_t backend);
 // Makes the backend's HIP device current on the calling thread. A caller that talks to another HIP-based library itself on this backend's stream (RCCL:

@@ -107,7 +107,12 @@ struct moshi_hot_config {
     // computes with 3 what it computes with 1. 7 (bits 0, 1 and 2): everything 3 does and, under 3's conditions at create, histories that pass the
     // ring's end - moshi_hot_slots_prefill_long / moshi_hot_slot_prefill_long on the moshika and stt shapes, with the arguments, return values and
     // remaining refusals they have over BF16 rings; the ring-ordered rows of each Temporal layer of a pass are one k_attn_rows_q8 launch.
-    // moshi_hot_slots_replay, moshi_hot_slots_persona and the _full calls on a tts-shaped model stay -1 with 7. 2, 4, 5, 6, or any other bit: NULL.
+    // moshi_hot_slots_replay, moshi_hot_slots_persona and the _full calls on a tts-shaped model stay -1 with 7. 2, 4, 5, 6: NULL.
+    // 8 (bit 3) beside one of the three values - 9, 11, 15: the create calls also set ggml_backend_mi355x_set_attn_q8_split(backend, 1) on the handle the
+    // model is created on (the handle's setting, as f32_matrix below; ignored on any other backend): a Temporal layer's step attention runs as the
+    // k_attn_streams_q8_split launch pair where the device has two compute units or more per (head, column) - few conversations over long rings
+    // (DESIGN.md 38). Everything else about the model is that of the value without the bit; ring bytes, scores and probabilities keep their bits, the
+    // output differs in the grouping of its double sums. 8, 10, 12, 13, 14 and anything above 15: NULL.
     // (It sits in front of f32_matrix: tests pin f32_matrix and float_accumulate as the struct's last two fields.)
     int32_t kv_q8;
     // 1: the create calls switch the handle the model is created on to the f64-MFMA mat-mul for F32 weights, ggml_backend_mi355x_set_f32_matrix(backend, 1):

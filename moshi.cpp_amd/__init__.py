@@ -68,7 +68,8 @@ class Stats(C.Structure):
                                          "vq_column_levels_in_last_plan", "code_gather_columns_in_last_plan",
                                          "state_copy_launches_in_last_plan", "state_copy_jobs_in_last_plan",
                                          "f32_matrix_mms_in_last_plan", "convtr_matrix_groups_in_last_plan",
-                                         "q8_attention_blocks_in_last_plan", "conv_matrix_groups_in_last_plan")]
+                                         "q8_attention_blocks_in_last_plan", "q8_attention_split_blocks_in_last_plan",
+                                         "conv_matrix_groups_in_last_plan")]
 
 
 class KernelProfile(C.Structure):
@@ -150,6 +151,7 @@ SIGNATURES = {
     "ggml_backend_mi355x_get_stats": (None, [P, C.POINTER(Stats)]), "ggml_backend_mi355x_set_flags": (None, [P, I]), "ggml_backend_mi355x_set_capture": (None, [P, I]), "ggml_backend_mi355x_set_max_columns": (None, [P, I]),
     "ggml_backend_mi355x_set_float_accumulate": (None, [P, I]),
     "ggml_backend_mi355x_set_f32_matrix": (None, [P, I]),
+    "ggml_backend_mi355x_set_attn_q8_split": (None, [P, I]),
     "ggml_backend_mi355x_get_stream": (P, [P]),
     "ggml_backend_mi355x_make_current": (None, [P]),
     "ggml_backend_mi355x_init_stream": (P, [P]),

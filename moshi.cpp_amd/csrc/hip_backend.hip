@@ -89,7 +89,8 @@ struct hip_ctx {
     std::deque<async_get> aget_pending;
     uint64_t aget_seq = 0;
     bool in_use = false;         // stream contexts only: handed out by ggml_backend_mi355x_init_stream, returned by ggml_backend_free
-    int usable_cus = 0;          // compute units this context's stream may use: the device's count, or MI355X_STREAM_CUS of them (CU-masked stream)
+    int attn_q8_split = 0;       // ggml_backend_mi355x_set_attn_q8_split: 0 the Q8_0-ring step attention is one k_attn_streams_q8 launch, 1 the k_attn_streams_q8_split pair where usable_cus / (H x B) gives 2 slices or more, n >= 2 that many slices
+    int usable_cus = 0;         // compute units this context's stream may use: the device's count, or MI355X_STREAM_CUS of them (CU-masked stream)
     ggml_backend_device dev_obj;
 };
 
@@ -343,7 +344,7 @@ struct plan_t {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     uint64_t hash = 0;
-    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_conv_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0, n_q8_attn_blocks = 0;
+    int n_nodes = 0, n_fused = 0, n_chained = 0, n_attn_folded = 0, n_step_programs = 0, n_vq_chained = 0, n_attn_block_launches = 0, n_attn_block_jobs = 0, n_generic_attn_nodes = 0, n_ring_copy_launches = 0, n_ring_copy_jobs = 0, n_attn_row_launches = 0, n_attn_row_jobs = 0, n_attn_row_rows = 0, n_cross_block_launches = 0, n_cross_block_jobs = 0, n_float_batched_mms = 0, n_float_acc_mms = 0, n_f32_matrix_mms = 0, n_pass_input_launches = 0, n_pass_input_rows = 0, n_convtr_column_groups = 0, n_convtr_matrix_groups = 0, n_conv_matrix_groups = 0, n_codec_attn_launches = 0, n_vq_column_levels = 0, n_code_gather_columns = 0, n_state_copy_launches = 0, n_state_copy_jobs = 0, n_q8_attn_blocks = 0, n_q8_attn_split_blocks = 0;
 };
 
 static void plan_free(hip_ctx * c, plan_t * p) {
@@ -2655,6 +2656,7 @@ struct planner {
     std::map<int, std::vector<pstep>> at_pos;   // fused groups, keyed by the position at which they are emitted
     std::vector<attn_group> attn_groups;        // pass_attention's groups: emitted after pass_matvecs, which absorbs some (emit_pos = -1)
     std::unordered_map<const void *, float *> paired_gate;   // storage of a linear_in output h (never materialised) -> g = silu(h_l) * h_r
+    void * q8_split_ws = nullptr; size_t q8_split_ws_bytes = 0;   // the plan's one k_attn_streams_q8_split workspace (emit_attention_groups)
 };
 
 // THE CLAIM RULE. A group takes its nodes only if every member is a node of the graph (no negative position) and none is claimed already - `self`, the
@@ -3270,6 +3272,20 @@ static void emit_attention_groups(planner & pl) {
         }
         if (ag.q8) {      // lockstep streams or slots over Q8_0 rings
             const attn_streams_args sa = ag.sa;
+            if (const int S = k_attn_streams_q8_split_slices(sa, c->attn_q8_split, c->usable_cus); S >= 2) {
+                // split along the ring (set_attn_q8_split): a scores launch and a values launch. ONE workspace per plan - the blocks of a plan are
+                // serial on the stream and each pair leaves the arrival counters at zero
+                const size_t n = k_attn_streams_q8_split_ws_size(sa);
+                if (n > pl.q8_split_ws_bytes) {
+                    pl.q8_split_ws = pl.em.ws(n); pl.q8_split_ws_bytes = n;
+                    HIP_CHECK(hipMemsetAsync(pl.q8_split_ws, 0, n, c->stream));   // stream-ordered behind the block's previous user (plans are built outside capture)
+                }
+                void * ws = pl.q8_split_ws;
+                at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams_q8_split(s, sa, S, ws, 1); });
+                at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams_q8_split(s, sa, S, ws, 0); });
+                pl.p->n_q8_attn_split_blocks++;
+                continue;
+            }
             at.insert(at.begin(), [=](hipStream_t s) { k_attn_streams_q8(s, sa); });
             pl.p->n_q8_attn_blocks++;
             continue;
@@ -3498,7 +3514,7 @@ static void publish_plan_stats(hip_ctx * c, const plan_t * p) {
     c->stats.convtr_column_groups_in_last_plan = p->n_convtr_column_groups; c->stats.codec_attn_launches_in_last_plan = p->n_codec_attn_launches;
     c->stats.vq_column_levels_in_last_plan = p->n_vq_column_levels; c->stats.code_gather_columns_in_last_plan = p->n_code_gather_columns;
     c->stats.state_copy_launches_in_last_plan = p->n_state_copy_launches; c->stats.state_copy_jobs_in_last_plan = p->n_state_copy_jobs;
-    c->stats.q8_attention_blocks_in_last_plan = p->n_q8_attn_blocks;
+    c->stats.q8_attention_blocks_in_last_plan = p->n_q8_attn_blocks; c->stats.q8_attention_split_blocks_in_last_plan = p->n_q8_attn_split_blocks;
 }
 
 static enum ggml_status hip_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
@@ -3660,8 +3676,8 @@ static ggml_backend_t hip_dev_init(ggml_backend_dev_t d, const char *) {
     ctx_init_lazy(c);
     // a fresh backend handle starts from default flags, the default sampler width and zeroed counters (the device context is shared)
     const int float_acc0 = mmf_env() == 2 ? 1 : 0;   // MI355X_MMF=2: the float-accumulating mat-mul from the start
-    if (c->flags != 0 || c->max_columns != 16 || c->float_acc != float_acc0 || c->f32_matrix != mmf32_env()) {
-        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16; c->float_acc = float_acc0; c->f32_matrix = mmf32_env();
+    if (c->flags != 0 || c->max_columns != 16 || c->float_acc != float_acc0 || c->f32_matrix != mmf32_env() || c->attn_q8_split != 0) {
+        HIP_CHECK(hipStreamSynchronize(c->stream)); for (auto & kv : c->plans) plan_free(c, kv.second); c->plans.clear(); c->flags = 0; c->max_columns = 16; c->float_acc = float_acc0; c->f32_matrix = mmf32_env(); c->attn_q8_split = 0;
     }
     c->stats = {};
     auto * b = new ggml_backend;
@@ -3730,6 +3746,16 @@ extern "C" void ggml_backend_mi355x_set_f32_matrix(ggml_backend_t b, int on) {
     c->plans.clear();
     c->f32_matrix = on;
 }
+extern "C" void ggml_backend_mi355x_set_attn_q8_split(ggml_backend_t b, int n) {
+    if (!b || b->iface.get_name != hip_backend_name) return;   // any other backend: nothing to do
+    hip_ctx * c = (hip_ctx *) b->context;
+    n = n < 0 ? 0 : n;
+    if (n == c->attn_q8_split) return;
+    if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
+    for (auto & kv : c->plans) plan_free(c, kv.second);   // the plans hold the other form's launches
+    c->plans.clear();
+    c->attn_q8_split = n;
+}
 extern "C" void ggml_backend_mi355x_set_flags(ggml_backend_t b, int flags) {
     hip_ctx * c = ctx_of(b);
     if (c->stream) { flush_uploads(c); HIP_CHECK(hipStreamSynchronize(c->stream)); }
@@ -3770,5 +3796,6 @@ extern "C" ggml_backend_t ggml_backend_mi355x_init_stream(ggml_backend_t base) {
     c->max_columns = b0->max_columns;
     c->float_acc = b0->float_acc;     // (a fresh handle holds no plans yet)
     c->f32_matrix = b0->f32_matrix;
+    c->attn_q8_split = b0->attn_q8_split;
     return b;
 }

@@ -247,6 +247,17 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & a, unsigned * err =
 // C <= 4096, B >= 2, T = 1; one workgroup per (head, column), none waits for another, no workspace.
 bool k_attn_streams_q8_supported(const attn_streams_args & a);
 void k_attn_streams_q8(hipStream_t s, const attn_streams_args & a);
+// The same block with every (head, column) split along the ring over S workgroups (hip_attn_q8_split.h): a launch pair of S x H x B
+// workgroups each - scores into the workspace, then soft_max, P x V per chunk of 256 slots and a last-arriver merge in chunk order. No workgroup waits
+// for another (the launch boundary is the only ordering), so nothing here depends on residency. Ring bytes, scores and p are k_attn_streams_q8's bits;
+// the output differs in the grouping of the double sums alone and does not depend on S. ws: k_attn_streams_q8_split_ws_size bytes whose arrival
+// counters (the whole block, for simplicity) are zero before the first launch; the kernels leave them at zero. 2 <= S <= min(16, ceil(C / 256)).
+// k_attn_streams_q8_split_slices: S under the handle's setting (0: never; 1: usable_cus / (H x B), one workgroup per compute unit; n >= 2: n), cut to
+// the ring's chunks and to 16 - below 2 the block keeps the unsplit launch.
+bool   k_attn_streams_q8_split_supported(const attn_streams_args & a);
+size_t k_attn_streams_q8_split_ws_size(const attn_streams_args & a);
+int    k_attn_streams_q8_split_slices(const attn_streams_args & a, int setting, int usable_cus);
+void   k_attn_streams_q8_split(hipStream_t s, const attn_streams_args & a, int S, void * ws, int launch = -1);   // launch: 0 the scores launch alone, 1 the values launch alone (the planner's two steps), -1 the pair
 // Decoder slots (moshi_hot_create_codec_slots): the codec transformer's attention block of B columns, T = 2 new rows each at the column's own position -
 // one workgroup per (head, row, column), each doing exactly what attn_ring256_kernel's workgroup (head, row) does for a single column (attn_ring256_body:
 // it rotates both new rows, workgroup (h, 0, b) writes them into column b's ring, row t attends over the column's own ring under its own mask row). `a`

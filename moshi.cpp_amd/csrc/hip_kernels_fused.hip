@@ -1863,6 +1863,8 @@ void k_attn_streams(hipStream_t s, const attn_streams_args & sa, unsigned * err)
 
 // Lockstep streams and stream slots over Q8_0 rings: a kernel of its own (row format, score arithmetic and ring walk all differ from attn_decode_body)
 #include "hip_attn_q8.h"
+// ... and the same block split along the ring over S workgroups per (head, column): a scores launch and a values launch, nobody waits
+#include "hip_attn_q8_split.h"
 // Slot prefill over the same rings: T new rows per job as a write launch and an int8-MFMA attend launch
 #include "hip_attn_q8_blocks.h"
 // Slot prefill past the ring's end over the same rings: a job's ring-ordered rows attend at once in one launch, then are written

@@ -1527,8 +1527,10 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
         if (n_streams < 2 || (kind != ModelKind::lockstep && kind != ModelKind::slots) || cfg->persona_columns || cfg->personaplex || !cfg->enable_lm ||
             cfg->num_heads < 1 || cfg->dim % cfg->num_heads != 0 || (cfg->dim / cfg->num_heads) % 32 != 0) return nullptr;
         // the field is a set of bits: 1 the ring type, 2 histories (prefill and snapshots) over such rings, 4 histories past the ring's end
-        // (the _prefill_long calls); a bit without the ones below it and any other bit mean nothing
-        if (cfg->kv_q8 != 1 && cfg->kv_q8 != 3 && cfg->kv_q8 != 7) return nullptr;
+        // (the _prefill_long calls); a bit without the ones below it and any other bit mean nothing. 8 beside them: the handle's split step
+        // attention (set_attn_q8_split below), nothing about the model
+        const int rings = cfg->kv_q8 & ~8;
+        if (rings != 1 && rings != 3 && rings != 7) return nullptr;
         // snapshots copy whole 16-byte pieces of a head's rows (kv_snapshot_rows): the ring must hold a whole number of such row groups
         if ((cfg->kv_q8 & 2) && cfg->context % kv_q8_row_group(cfg->dim / cfg->num_heads) != 0) return nullptr;
         struct ggml_context * pc = ggml_init({ ggml_tensor_overhead() * 8, NULL, true });
@@ -1545,6 +1547,7 @@ static moshi_hot_model_t * create_model(ggml_backend_t backend, const struct mos
     if (n_streams > MOSHI_HOT_DEFAULT_MAX_STREAMS) ggml_backend_mi355x_set_max_columns(backend, n_streams);   // its samplers stay one launch per site
     if (cfg->float_accumulate) ggml_backend_mi355x_set_float_accumulate(backend, 1);   // the handle's setting (a sibling stream inherits it); never lowered here
     if (cfg->f32_matrix) ggml_backend_mi355x_set_f32_matrix(backend, cfg->f32_matrix);   // likewise, bits: 1 the F32 linears of the codec transformers at B columns, 2 the transposed convolutions, 4 the convolution groups
+    if (cfg->kv_q8 & 8) ggml_backend_mi355x_set_attn_q8_split(backend, 1);   // likewise: the Q8_0-ring step attention split along the ring where the device has the compute units for it
     m->sampling.assign((size_t) n_streams, { { 0, cfg->temp, cfg->temp_text, cfg->top_k, cfg->top_k_text }, false });
     const moshi_hot_config & c = m->cfg;
     m->W = new Weights(backend, seed, 4096);
